@@ -28,8 +28,8 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-PEAK_BF16 = 2.5e15  # dense MFMA bf16, /opt/skills/guides/MI355X_MICROARCH.md
-PEAK_FP8 = 5.0e15   # dense MFMA fp8 (MX-scaled K=128), same guide
+PEAK_BF16 = 2.5e15  # dense MFMA bf16 of the MI355X
+PEAK_FP8 = 5.0e15   # dense MFMA fp8 (MX-scaled K=128) of the MI355X
 PEAK_HBM = 8.0e12
 
 
@@ -481,6 +481,30 @@ def cpu_baseline(reps=3, budget_s=100.0):
                                             "the workload of the GPU line; an extrapolation, not a measurement" % (d1k, s1k)))
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of `arrays` (name -> host tensor) as <out_dir>/<name>.npy, float32 (float64 stays float64).  When the
+    arrays together exceed `limit` bytes, each one is cut to the same fraction of its elements: the values at a sorted choice of flat
+    indices drawn from a fixed seed, so the sample is the same in any run with the same shapes.  Returns a record for the JSON line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: (v.double() if v.dtype == torch.float64 else v.float()).numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    frac = min(1.0, limit / total) if total else 1.0
+    rec = {}
+    for name, a in host.items():
+        shape = list(a.shape)
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=max(1, int(a.size * frac)), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        rec[name] = dict(shape=shape, dtype=str(a.dtype), elements=int(a.size),
+                         sample="flat indices: sorted numpy default_rng(0).choice without replacement" if frac < 1.0 else None)
+    return dict(dir=out_dir, arrays=rec)
+
+
 def _free_port():
     import socket
     with socket.socket() as sk:
@@ -546,10 +570,18 @@ def main(argv=None):
                          "launcher with --nproc-per-node 1, or plain): exercises the N > 1 code path on a one-GPU box")
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="CPU stand-in workload over gloo: exercises the launcher / collective / timing / JSON path without a GPU (tests only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; at most 64 MB in all, "
+                         "a fixed seeded sample beyond that): latents.npy = the unpacked latents [B, 16, size/8, size/8], or with several "
+                         "ranks the all-gathered packed latents [ranks, B, (size/16)^2, 64].  Inputs are seeded: equal arguments, equal inputs")
     args = ap.parse_args(argv)
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     launched = "WORLD_SIZE" in os.environ
     if not args.selftest_launcher and torch.cuda.is_available() and args.gpus > torch.cuda.device_count():
         raise SystemExit("bench.py: --gpus %d but this node shows %d GPU(s); refusing to start ranks that have no device of their own"
@@ -624,7 +656,8 @@ def main(argv=None):
                     prm.data.copy_(v)
                 nets.append(net)
             pipe = FluxPipeline(model, FlowMatchEulerDiscreteScheduler(shift=3.0, use_dynamic_shifting=True), control_nets=nets)
-            hint = (torch.rand((B, 3, args.size, args.size), device=dev) * 2 - 1).bfloat16()
+            gh = torch.Generator(device=dev).manual_seed(300 + rank)
+            hint = (torch.rand((B, 3, args.size, args.size), device=dev, generator=gh) * 2 - 1).bfloat16()
         else:
             model = FluxTransformer2DModel(device=dev).init_random_(seed=1234)  # every rank holds the SAME weight replica
             pipe = FluxPipeline(model, FlowMatchEulerDiscreteScheduler())  # schnell / shuttle-3 schedule: shift 1.0
@@ -658,7 +691,7 @@ def main(argv=None):
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_pass()
+        out = one_pass()
     sync()
     if use_dist:
         dist.barrier()
@@ -673,6 +706,9 @@ def main(argv=None):
         dt = max(float(x.item()) for x in allt)          # MAX over ranks
     if ops is not None:
         ops.streamk_check(sync=True)   # outside the timed region: a stream-K segment that gave up = undefined results = no line
+    dumped = None
+    if args.dump_outputs and rank == 0:   # the last timed step's result, copied out before anything below launches the path again
+        dumped = dump_outputs({"latents": (torch.stack(out) if use_dist else out).cpu()}, args.dump_outputs)
 
     if rank == 0:
         ms_pass = dt / args.steps * 1e3
@@ -696,6 +732,8 @@ def main(argv=None):
             "model_tflops_per_gpu": fl * N / (ms_pass * 1e-3) / 1e12,
             "model_frac_of_bf16_peak": fl * N / (ms_pass * 1e-3) / PEAK_BF16,
         }
+        if dumped:
+            line["dump_outputs"] = dumped
         if stub:
             line.update({"metric": "LAUNCHER SELF-TEST (CPU stand-in workload, gloo) -- not a benchmark figure", "dtype": "f32",
                          "data": "launcher self-test: no GPU work", "model_tflops_per_gpu": None, "model_frac_of_bf16_peak": None,
