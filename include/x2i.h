@@ -465,7 +465,7 @@ int x2i_zero_if_nonfinite_bf16(void* g, int64_t n, const float* term, x2i_stream
  *   Q, K, V, dO  bf16 [B,H,Spad,128] (row-major per head, zero beyond S)      QT, KT, dOT  bf16 [B,H,128,Spad] (their transposes)
  *   D  f32 [B,H,Spad] = rowsum(dO * O) (x2i_attention_bwd_prep_bf16 from the token-major dO / O)     lse2  f32 [B,H,Spad] scratch
  * Three launches: log2-sum-exp statistics into lse2 (skipped when have_lse != 0: lse2 then is an input), dQ (persistent query blocks),
- * dK / dV (persistent key blocks); no atomics. */
+ * dK / dV (persistent key blocks); no atomics.  Only rows < S of dQ, dK and dV are stored: their padding rows keep what the caller left there. */
 int x2i_attention_bwd_bf16(const void* Q, const void* K, const void* V, const void* QT, const void* KT, const void* dO, const void* dOT, float* lse2,
                            const float* D, void* dQ, void* dK, void* dV, int32_t B, int32_t H, int32_t S, int32_t Spad, float scale,
                            int32_t have_lse, x2i_stream_t stream);

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import attn_ref as R
 from tests.util import rel_l2, seeded
 
 pytestmark = pytest.mark.gpu
@@ -453,9 +454,10 @@ def test_fused_attention_backward_vs_autograd(ops, B, H, S):
     ops.attention_bwd(Qg, Kg, Vg, QT, KT, dOh, dOT, lse, Dv, dQ, dK, dV, B, H, S, Spad, scale)
     ref_lse = torch.logsumexp(scale * q.detach() @ k.detach().transpose(-1, -2), dim=-1) * 1.4426950408889634
     assert rel_l2(lse[:, :, :S], ref_lse) < 1e-4
-    eq, ek, ev = rel_l2(dQ[:, :, :S], q.grad), rel_l2(dK[:, :, :S], k.grad), rel_l2(dV[:, :, :S], v.grad)
-    print(f"fused attention backward B={B} H={H} S={S}: dQ {eq:.3e} dK {ek:.3e} dV {ev:.3e}")
-    assert eq < 1.5e-2 and ek < 1.5e-2 and ev < 1.5e-2
+    # every 64-row tile of every head (tests/attn_ref.py: the bounds the float64 tests at the model length use)
+    eq, ek, ev = (R.check_tiles(n, t, want, bound) for n, t, want, bound in (("dQ", dQ, q.grad, R.TOL_DQ), ("dK", dK, k.grad, R.TOL_DK),
+                                                                             ("dV", dV, v.grad, R.TOL_DV)))
+    print(f"fused attention backward B={B} H={H} S={S}: worst tile dQ {eq:.3e} dK {ek:.3e} dV {ev:.3e}")
     # the forward kernel can hand over the statistics itself (x2i_attention_lse_bf16): same output as x2i_attention_bf16, same lse, and the
     # backward without its statistics pass gives the same gradients
     VT = ops.transpose(Vg.view(B * H, Spad, 128)).view(B, H, 128, Spad)
