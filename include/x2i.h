@@ -19,7 +19,8 @@
  *     x2i_groupnorm_scratch_floats, x2i_streamk_workspace_bytes (x2i_gemm_args.workspace, x2i_attention_vp_ws_bf16).  Process-wide state, all of it
  *     mutex-protected: the option table below and a per-kernel "dynamic LDS size already raised" cache.  (The measurement library additionally keeps one
  *     side stream with two events per device for the two-stream A/B form of the attention backward.)
- *   - ABI version 5 (x2i_abi_version; 5 adds x2i_attention_vp_ws_bf16 -- no struct changed; 4 appended `w_group` to x2i_gemm_args, 0 = what version 3 did, and added the *_grouped entry points).  Since version 1: x2i_gemm_args grew `workspace` / `workspace_bytes`, x2i_qkv_desc `q_scale`
+ *   - ABI version 5 (x2i_abi_version; 5 adds x2i_attention_vp_ws_bf16 -- no struct changed; x2i_conv3x3_image_bf16 and x2i_vae_posterior_bf16
+ *     (the VAE encoder) were added under the same version: new entry points only, no struct or existing signature changed; 4 appended `w_group` to x2i_gemm_args, 0 = what version 3 did, and added the *_grouped entry points).  Since version 1: x2i_gemm_args grew `workspace` / `workspace_bytes`, x2i_qkv_desc `q_scale`
  *     and x2i_conv_desc a ninth field (version 2); version 3 re-defines that field as `pad_w_p1` (0 = same padding as `pad`, so that a
  *     zero-initialised descriptor means what it meant in version 1), appends `out_w`, `out_h`, `out_row_pitch` (0 = computed / dense) and the `moments` fields (NULL = off) to it, gives `up` the value 2, and appends `vt_perm` to x2i_qkv_desc (0 = the old layout).  A caller built against another version must not load this
  *     library (x2i_amd/_lib.py checks).
@@ -218,6 +219,25 @@ int64_t x2i_conv_moments_scratch_floats(int32_t M, int32_t N, int32_t batch);
  * (csrc/conv_narrow.hip) -- as an implicit GEMM three channels would pay for a 128-column tile. */
 int x2i_conv3x3_narrow_bf16(const void* x, const void* w, const void* bias, void* y, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                             int32_t ldy, x2i_stream_t stream);
+
+/* The VAE ENCODER's image stem (diffusers Encoder.conv_in, 3 -> 128; reached from vae.encode(pixel_values) at
+ * lightcontrol/train_lightcontrol.py:678): Conv2d(Cin -> Cout, k=3, stride=1, pad=1) reading the NCHW bf16 image planes
+ * x [B][Cin][H][W] directly (1 <= Cin <= 4) and writing NHWC bf16 y [B][H][W][Cout] (Cout % 16 == 0, 16 .. 128; 16-byte aligned).  w bf16
+ * [Cout][Cin][3][3] = the nn.Conv2d weight as it is; bias bf16 [Cout] or NULL.  f32 accumulation, one rounding.  moments: NULL, or f32 [B][Cout][2]
+ * in exactly the layout and fixed-order reduction of x2i_conv_desc.moments (channel-quad sums of the bf16 outputs), with moments_scratch of
+ * x2i_conv_moments_scratch_floats(H * W, Cout, B) floats (16-byte aligned).  Deterministic (csrc/vae_encode.hip). */
+int x2i_conv3x3_image_bf16(const void* x, const void* w, const void* bias, void* y, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout,
+                           float* moments, float* moments_scratch, x2i_stream_t stream);
+
+/* The VAE encoder's posterior, diffusers DiagonalGaussianDistribution (vae.encode(pixel_values).latent_dist.sample() and the
+ * (z - shift_factor) * scaling_factor behind it, lightcontrol/train_lightcontrol.py:678-679).  params: NHWC bf16 [B][h][w][ldp] (the encoder's
+ * conv_out; channels 0 .. C-1 = mean, C .. 2C-1 = logvar; ldp >= 2 C).  z = mean                               (eps == NULL: mode())
+ *                                                                              z = mean + exp(0.5 clamp(logvar, -30, 20)) eps  (sample(); eps NCHW bf16 [B][C][h][w])
+ * then, with scale_shift = 1, z = (z - shift) * scale; f32 arithmetic, one rounding to bf16.  Writes out_nchw [B][C][h][w] and / or out_packed
+ * [B][(h / 2)(w / 2)][4 C] = FluxPipeline._pack_latents of it (h, w even; the layout lightcontrol/train_lightcontrol.py packs the latent into);
+ * either may be NULL, not both.  One thread per output element (coalesced writes), deterministic. */
+int x2i_vae_posterior_bf16(const void* params, int32_t ldp, const void* eps, void* out_nchw, void* out_packed, int32_t B, int32_t C, int32_t h,
+                           int32_t w, int32_t scale_shift, float shift, float scale, x2i_stream_t stream);
 
 /* Conv2d(3 -> Cout, k=3, stride=2, pad=1) on an NHWC bf16 image (lightcontrol_flux.py:594); w f32 [Cout][3][3][3]
  * (ky,kx,ci), bias f32 [Cout]; y NHWC bf16 [B][H/2][W/2][Cout], Cout % 16 == 0 and <= 64. */

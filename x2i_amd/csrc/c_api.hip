@@ -251,6 +251,16 @@ int x2i_conv3x3_narrow_bf16(const void* x, const void* w, const void* bias, void
   return x2i_launch_conv3x3_narrow(x, w, bias, y, B, H, W, Cin, Cout, ldy, (hipStream_t)stream);
 }
 
+int x2i_conv3x3_image_bf16(const void* x, const void* w, const void* bias, void* y, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout,
+                           float* moments, float* moments_scratch, x2i_stream_t stream) {
+  return x2i_launch_conv3x3_image(x, w, bias, y, B, Cin, H, W, Cout, moments, moments_scratch, (hipStream_t)stream);
+}
+
+int x2i_vae_posterior_bf16(const void* params, int32_t ldp, const void* eps, void* out_nchw, void* out_packed, int32_t B, int32_t C, int32_t h,
+                           int32_t w, int32_t scale_shift, float shift, float scale, x2i_stream_t stream) {
+  return x2i_launch_vae_posterior(params, ldp, eps, out_nchw, out_packed, B, C, h, w, scale_shift, shift, scale, (hipStream_t)stream);
+}
+
 int x2i_conv_stem_bf16(const void* x, const float* w, const float* bias, void* y, int32_t B, int32_t H, int32_t W, int32_t Cout,
                        x2i_stream_t stream) {
   return x2i_launch_conv_stem(x, w, bias, y, B, H, W, Cout, (hipStream_t)stream);

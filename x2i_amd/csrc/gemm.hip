@@ -271,22 +271,26 @@ long long x2i_conv_moments_scratch(int M, int N, int batch) {   // row blocks of
 }
 
 static int pad_w_of(const x2i_conv_desc* cd) { return cd->pad_w_p1 <= 0 ? cd->pad : cd->pad_w_p1 - 1; }
-// behind a convolution launch: the per-row-block partial moments (`blocks` row blocks per batch item) -> x2i_conv_desc.moments
-static int conv_moments_tail(const x2i_gemm_args* a, const x2i_conv_desc* cd, hipStream_t stream, int blocks) {
-  int rc = x2i_check_launch("conv");
-  if (rc || !cd->moments) return rc;
-  const int n2 = a->N / 2;
+// the per-row-block partial moments f32 [batch][blocks][N / 4][2] at the start of `scratch` -> moments f32 [batch][N][2] (also the image stem's,
+// vae_encode.hip)
+int x2i_conv_moments_reduce(float* scratch, float* moments, int batch, int blocks, int N, int accumulate, hipStream_t stream) {
+  const int n2 = N / 2;
   if (blocks <= 128) {   // few row blocks (small images / small batches live here): the finishing block adds them itself, in the same fixed tree
-    hipLaunchKernelGGL(conv_moments_finish_kernel, dim3(a->batch), dim3(256), 0, stream, (const float*)cd->moments_scratch, cd->moments, blocks, n2,
-                       cd->moments_accumulate ? 1 : 0);
+    hipLaunchKernelGGL(conv_moments_finish_kernel, dim3(batch), dim3(256), 0, stream, (const float*)scratch, moments, blocks, n2, accumulate);
     return x2i_check_launch("conv_moments_finish");
   }
-  float* tmp = cd->moments_scratch + (long long)a->batch * blocks * n2;
-  hipLaunchKernelGGL(conv_moments_slabs_kernel, dim3(MOM_SLABS, a->batch), dim3(256), 0, stream, (const float*)cd->moments_scratch, tmp, blocks, n2);
-  rc = x2i_check_launch("conv_moments_slabs");
+  float* tmp = scratch + (long long)batch * blocks * n2;
+  hipLaunchKernelGGL(conv_moments_slabs_kernel, dim3(MOM_SLABS, batch), dim3(256), 0, stream, (const float*)scratch, tmp, blocks, n2);
+  const int rc = x2i_check_launch("conv_moments_slabs");
   if (rc) return rc;
-  hipLaunchKernelGGL(conv_moments_finish_kernel, dim3(a->batch), dim3(256), 0, stream, (const float*)tmp, cd->moments, MOM_SLABS, n2, cd->moments_accumulate ? 1 : 0);
+  hipLaunchKernelGGL(conv_moments_finish_kernel, dim3(batch), dim3(256), 0, stream, (const float*)tmp, moments, MOM_SLABS, n2, accumulate);
   return x2i_check_launch("conv_moments_finish");
+}
+// behind a convolution launch: the per-row-block partial moments (`blocks` row blocks per batch item) -> x2i_conv_desc.moments
+static int conv_moments_tail(const x2i_gemm_args* a, const x2i_conv_desc* cd, hipStream_t stream, int blocks) {
+  const int rc = x2i_check_launch("conv");
+  if (rc || !cd->moments) return rc;
+  return x2i_conv_moments_reduce(cd->moments_scratch, cd->moments, a->batch, blocks, a->N, cd->moments_accumulate ? 1 : 0, stream);
 }
 
 // One launch of a persistent convolution kernel (gemm256c.hip / gemm512c.hip) per CHUNK of batch items whose images fit the kernel's single 2 GB

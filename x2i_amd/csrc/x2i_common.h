@@ -73,6 +73,8 @@ bool x2i_side_stream(hipStream_t main, hipStream_t* side, hipEvent_t* fork, hipE
 struct x2i_gemm_args;
 bool x2i_streamk_workspace(const x2i_gemm_args* a, float** slabs, unsigned** flags, int* rc);  // the caller's workspace, validated
 long long x2i_conv_moments_scratch(int M, int N, int batch);   // gemm.hip: floats of x2i_conv_desc.moments_scratch
+// gemm.hip: partial moments f32 [batch][blocks][N / 4][2] at the start of `scratch` -> moments f32 [batch][N][2] (fixed order; the slab sums go behind them)
+int x2i_conv_moments_reduce(float* scratch, float* moments, int batch, int blocks, int N, int accumulate, hipStream_t stream);
 int x2i_gemm_sk_slabs();                          // slabs per workspace (2 x max tiles: FX double buffer)
 int x2i_gemm_sk_max_tiles();                      // (gemm.hip: the constants of gemm_device.h)
 long long x2i_gemm_sk_slab_bytes();

@@ -18,6 +18,10 @@ int x2i_launch_conv3x3_narrow(const void* x, const void* w, const void* bias, vo
                               hipStream_t stream);   // conv_narrow.hip
 int x2i_launch_conv_stem(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int Cout,
                          hipStream_t stream);
+int x2i_launch_conv3x3_image(const void* x, const void* w, const void* bias, void* y, int B, int Cin, int H, int W, int Cout, float* moments,
+                             float* moments_scratch, hipStream_t stream);   // vae_encode.hip
+int x2i_launch_vae_posterior(const void* params, int ldp, const void* eps, void* out_nchw, void* out_packed, int B, int C, int h, int w, int scale_shift,
+                             float shift, float scale, hipStream_t stream);   // vae_encode.hip
 long long x2i_groupnorm_scratch(int B, int G);
 int x2i_launch_groupnorm(const void* x, void* y, int B, long long HW, int C, int G, const void* w, const void* b, float eps,
                          int act, const float* pre_add, const void* post_add, float* partial, hipStream_t stream, int w_group = 0);

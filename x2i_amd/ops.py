@@ -523,6 +523,52 @@ def conv3x3_narrow(x, w_packed, bias, Cout, out=None, ldy=4):
     return out
 
 
+def conv3x3_image(x_nchw, w, bias, moments=None):
+    """Conv2d(Cin <= 4 -> Cout, 3 x 3, stride 1, padding 1) reading the NCHW bf16 image [B,Cin,H,W] directly (include/x2i.h:
+    x2i_conv3x3_image_bf16): returns NHWC bf16 [B,H,W,Cout].  w: the nn.Conv2d weight bf16 [Cout,Cin,3,3] as it is; bias bf16 [Cout] or None.
+    moments: f32 [B,Cout,2] that receives the channel-quad moments of the output, exactly as conv2d_nhwc(moments=...) leaves them."""
+    lib = _lib.load()
+    _req(x_nchw, torch.bfloat16, "x")
+    _req(w, torch.bfloat16, "w")
+    x_nchw, w = x_nchw.contiguous(), w.contiguous()
+    B, Cin, H, W = x_nchw.shape
+    Cout = w.shape[0]
+    out = torch.empty((B, H, W, Cout), device=x_nchw.device, dtype=torch.bfloat16)
+    mp = sp = None
+    if moments is not None:
+        _req(moments, torch.float32, "moments")
+        n = int(lib.x2i_conv_moments_scratch_floats(H * W, Cout, B))
+        key = (x_nchw.device, "conv_moments")
+        if key not in _gn_scratch or _gn_scratch[key].numel() < n:
+            _gn_scratch[key] = torch.empty(n, device=x_nchw.device, dtype=torch.float32)
+        mp, sp = moments.data_ptr(), _gn_scratch[key].data_ptr()
+    check(lib.x2i_conv3x3_image_bf16(_p(x_nchw), _p(w), _p(bias), _p(out), B, Cin, H, W, Cout, mp, sp, _stream()), "conv3x3_image")
+    return out
+
+
+def vae_posterior(params, C, eps=None, scale_shift=None, packed=False):
+    """diffusers DiagonalGaussianDistribution.mode() (eps None) / .sample() (eps: NCHW bf16 [B,C,h,w] noise) from the encoder's NHWC conv_out
+    params [B,h,w,>= 2C] (include/x2i.h: x2i_vae_posterior_bf16).  scale_shift: None or (shift_factor, scaling_factor): (z - shift) * scale.
+    Returns NCHW bf16 [B,C,h,w], or FLUX's packed tokens [B,(h/2)(w/2),4C] with packed=True."""
+    lib = _lib.load()
+    _req(params, torch.bfloat16, "params")
+    if params.stride(-1) != 1 or params.stride(1) != params.shape[2] * params.stride(2) or params.stride(0) != params.shape[1] * params.stride(1):
+        raise ValueError("vae_posterior: params must be NHWC with dense pixels (any pixel pitch), got strides %s" % (params.stride(),))
+    B, h, w, _ = params.shape
+    ldp = params.stride(2)
+    if eps is not None:
+        _req(eps, torch.bfloat16, "eps")
+        eps = eps.contiguous()
+        if tuple(eps.shape) != (B, C, h, w):
+            raise ValueError("vae_posterior: eps must be [B, C, h, w] = %s, got %s" % ((B, C, h, w), tuple(eps.shape)))
+    shape = (B, (h // 2) * (w // 2), 4 * C) if packed else (B, C, h, w)
+    out = torch.empty(shape, device=params.device, dtype=torch.bfloat16)
+    sh, sc = scale_shift if scale_shift is not None else (0.0, 1.0)
+    check(lib.x2i_vae_posterior_bf16(_p(params), ldp, _p(eps), None if packed else _p(out), _p(out) if packed else None, B, C, h, w,
+                                     1 if scale_shift is not None else 0, float(sh), float(sc), _stream()), "vae_posterior")
+    return out
+
+
 def conv_stem(x_nhwc, w, bias, Cout):
     """Conv2d(3->Cout, k3, s2, p1): x bf16 NHWC [B,H,W,3]; w f32 [Cout,3,3,3] (ky,kx,ci)."""
     lib = _lib.load()

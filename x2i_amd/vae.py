@@ -7,6 +7,12 @@ full checkpoint are ignored).  Activations are NHWC bf16; every conv is the impl
 nearest-neighbour upsampling of Upsample2D is fused into the gather), GroupNorm(32)+SiLU and residual adds are fused
 around them, the single-head 512-wide mid-block attention runs as two GEMMs around a row-softmax kernel
 (S = q k^T is materialised: 512 MiB per 1024^2 image, once per image).
+
+Opt-in encoder half (`AutoencoderKL(..., with_encoder=True)`): diffusers' FLUX `Encoder` with its key names (`encoder.*`) and
+`.encode(x).latent_dist.sample()` / `.mode()` -- the call that starts every LightControl training step
+(lightcontrol/train_lightcontrol.py:678-679).  The image stem reads the NCHW image directly (x2i_conv3x3_image_bf16), the ResnetBlock2D /
+Downsample2D / mid-block convs are the same implicit-GEMM kernels (Downsample2D's F.pad(x, (0, 1, 0, 1)) + stride-2 conv is the kernel's
+asymmetric padding, `out_h` / `out_w`), and the diagonal-Gaussian posterior is one element-wise kernel (x2i_vae_posterior_bf16).
 """
 import math
 import os
@@ -199,8 +205,127 @@ class _Decoder(nn.Module):
         self.conv_out = _Conv(rev[-1], cfg.out_channels, 3, device)
 
 
+class _Down(nn.Module):
+    def __init__(self, c, device):
+        super().__init__()
+        self.conv = _Conv(c, c, 3, device)
+
+
+class _DownBlock(nn.Module):
+    def __init__(self, cin, cout, n, downsample, device):
+        super().__init__()
+        self.resnets = _Seq({j: _Res(cin if j == 0 else cout, cout, device) for j in range(n)})
+        if downsample:
+            self.downsamplers = _Seq({0: _Down(cout, device)})
+
+
+class _Encoder(nn.Module):
+    """diffusers Encoder(double_z=True) with DownEncoderBlock2D blocks (layers_per_block resnets each, Downsample2D(padding=0) behind all but the
+    last) and UNetMidBlock2D(attention) -- the FLUX VAE's encoder: 106 tensors, 34.274 M parameters."""
+
+    def __init__(self, cfg, device):
+        super().__init__()
+        boc = cfg.block_out_channels
+        self.conv_in = _Conv(cfg.in_channels, boc[0], 3, device)
+        blocks, prev = {}, boc[0]
+        for i, co in enumerate(boc):
+            blocks[i] = _DownBlock(prev, co, cfg.layers_per_block, i != len(boc) - 1, device)
+            prev = co
+        self.down_blocks = _Seq(blocks)
+        self.mid_block = _Mid(boc[-1], device)
+        self.conv_norm_out = _Vec(boc[-1], device)
+        self.conv_out = _Conv(boc[-1], 2 * cfg.latent_channels, 3, device)
+
+
 class _Cfg(dict):
     __getattr__ = dict.__getitem__
+
+
+class DiagonalGaussianDistribution:
+    """diffusers' DiagonalGaussianDistribution over the encoder's conv_out: `mean, logvar = chunk(params, 2, dim=1)`, logvar clamped to
+    [-30, 20], std = exp(0.5 logvar), var = exp(logvar).  The parameters stay in the NHWC bf16 layout the encoder leaves; `mean` / `logvar` /
+    `std` / `var` are materialised by torch on first use (bf16, NCHW), `mode()` / `sample()` run the posterior kernel (f32, one rounding).
+    Project conveniences: scale_shift=True returns (z - shift_factor) * scaling_factor (lightcontrol/train_lightcontrol.py:679), packed=True FLUX's
+    packed tokens [B, (h/2)(w/2), 4 C] (FluxPipeline._pack_latents), both straight from the kernel."""
+
+    def __init__(self, params_nhwc, latent_channels, shift_factor, scaling_factor):
+        self._p = params_nhwc
+        self._c = latent_channels
+        self._ss = (shift_factor, scaling_factor)
+        self.parameters = params_nhwc.permute(0, 3, 1, 2)   # NCHW view of [B, h, w, 2 C] (diffusers' name)
+        self.deterministic = False
+        self._cache = {}
+
+    def _lazy(self, name, fn):
+        if name not in self._cache:
+            self._cache[name] = fn()
+        return self._cache[name]
+
+    @property
+    def mean(self):
+        return self._lazy("mean", lambda: self.parameters[:, :self._c].contiguous())
+
+    @property
+    def logvar(self):
+        return self._lazy("logvar", lambda: torch.clamp(self.parameters[:, self._c:2 * self._c], -30.0, 20.0).contiguous())
+
+    @property
+    def std(self):
+        return self._lazy("std", lambda: torch.exp(0.5 * self.logvar))
+
+    @property
+    def var(self):
+        return self._lazy("var", lambda: torch.exp(self.logvar))
+
+    def _out(self, eps, scale_shift, packed):
+        return ops.vae_posterior(self._p, self._c, eps=eps, scale_shift=self._ss if scale_shift else None, packed=packed)
+
+    @torch.no_grad()
+    def sample(self, generator=None, scale_shift=False, packed=False):
+        """mean + std * eps, eps drawn as diffusers' randn_tensor(mean.shape, generator, device, dtype=bf16) draws it: on the generator's device
+        (a CPU generator draws on the CPU, then the noise moves), a list of generators one sample each."""
+        B, h, w, _ = self._p.shape
+        shape, dev = (B, self._c, h, w), self._p.device
+        if isinstance(generator, (list, tuple)) and len(generator) == 1:
+            generator = generator[0]
+        if isinstance(generator, (list, tuple)):
+            eps = torch.cat([torch.randn((1,) + shape[1:], generator=g, device=g.device, dtype=torch.bfloat16) for g in generator]).to(dev)
+        else:
+            gdev = generator.device if generator is not None else dev
+            if generator is not None and gdev.type != dev.type and gdev.type != "cpu":
+                raise ValueError("Cannot generate a %s tensor from a generator of type %s." % (dev, gdev.type))
+            eps = torch.randn(shape, generator=generator, device=gdev, dtype=torch.bfloat16).to(dev)
+        return self._out(eps, scale_shift, packed)
+
+    @torch.no_grad()
+    def mode(self, scale_shift=False, packed=False):
+        return self._out(None, scale_shift, packed)
+
+    def kl(self, other=None):
+        raise NotImplementedError("x2i_amd VAE: DiagonalGaussianDistribution.kl is not implemented (encode serves sample / mode)")
+
+    def nll(self, sample, dims=(1, 2, 3)):
+        raise NotImplementedError("x2i_amd VAE: DiagonalGaussianDistribution.nll is not implemented (encode serves sample / mode)")
+
+
+def encode_flops(cfg, H, W):
+    """Algorithmic FLOPs of one `encode` of an [*, in_channels, H, W] image: 2 * Cin * Cout * k^2 per output pixel of every convolution
+    (Downsample2D's stride-2 conv at the halved resolution), 2 M N K of the mid-block attention's four linears and its two T x T products."""
+    boc = cfg.block_out_channels
+    conv = lambda ci, co, k, h, w: 2.0 * ci * co * k * k * h * w   # noqa: E731
+    res = lambda ci, co, h, w: conv(ci, co, 3, h, w) + conv(co, co, 3, h, w) + (conv(ci, co, 1, h, w) if ci != co else 0.0)   # noqa: E731
+    fl = conv(cfg.get("in_channels", 3), boc[0], 3, H, W)
+    prev = boc[0]
+    for i, co in enumerate(boc):
+        for j in range(cfg.layers_per_block):
+            fl += res(prev if j == 0 else co, co, H, W)
+        prev = co
+        if i != len(boc) - 1:
+            H, W = H // 2, W // 2
+            fl += conv(co, co, 3, H, W)
+    c, T = boc[-1], H * W
+    fl += 2 * res(c, c, H, W) + 4 * 2.0 * T * c * c + 2 * 2.0 * T * T * c
+    return fl + conv(c, 2 * cfg.latent_channels, 3, H, W)
 
 
 def decode_flops(cfg, H, W, up_phases=0):
@@ -225,10 +350,11 @@ def decode_flops(cfg, H, W, up_phases=0):
 
 
 class AutoencoderKL(nn.Module):
-    """Decoder half of diffusers' AutoencoderKL with the FLUX configuration as defaults."""
+    """diffusers' AutoencoderKL with the FLUX configuration as defaults: the decoder half, plus the encoder half with with_encoder=True."""
 
     def __init__(self, latent_channels=16, out_channels=3, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
-                 norm_num_groups=32, scaling_factor=0.3611, shift_factor=0.1159, device="cuda"):
+                 norm_num_groups=32, scaling_factor=0.3611, shift_factor=0.1159, device="cuda", with_encoder=False, in_channels=3,
+                 use_quant_conv=False):
         super().__init__()
         self.config = _Cfg(latent_channels=latent_channels, out_channels=out_channels, block_out_channels=tuple(block_out_channels),
                            layers_per_block=layers_per_block, norm_num_groups=norm_num_groups, scaling_factor=scaling_factor,
@@ -236,6 +362,14 @@ class AutoencoderKL(nn.Module):
         if any(c % 64 for c in block_out_channels):
             raise ValueError("x2i_amd VAE: block_out_channels must be multiples of 64 (implicit-GEMM conv)")
         self.decoder = _Decoder(self.config, device)
+        self.with_encoder = bool(with_encoder)
+        if self.with_encoder:
+            if use_quant_conv:
+                raise NotImplementedError("x2i_amd VAE: use_quant_conv=True is not supported (the FLUX VAE has no quant_conv)")
+            if not 1 <= in_channels <= 4 or block_out_channels[0] % 16 or block_out_channels[0] > 128:
+                raise ValueError("x2i_amd VAE encoder: needs in_channels <= 4 and block_out_channels[0] a multiple of 16, at most 128 (image stem kernel)")
+            self.config.update(in_channels=in_channels, use_quant_conv=False)
+            self.encoder = _Encoder(self.config, device)   # (registered after the decoder: init_random_ gives the decoder the same values either way)
         # X2I_VAE_UP_PHASES (read once, here): how Upsample2D's conv runs -- 2 (product): four 2 x 2 phase convolutions on the un-doubled image;
         # 1: two 3 x 2 column phases; 0: ONE 3 x 3 conv with the x2 upsampling in its gather.  Same result within the tolerance of one more
         # bf16 rounding of summed weights (_Conv.packed_up_phases; tests/test_vae_gpu.py)
@@ -257,11 +391,59 @@ class AutoencoderKL(nn.Module):
         return r
 
     def load_state_dict(self, sd, strict=True):
-        """Accepts a full AutoencoderKL checkpoint: encoder.* / quant_conv.* / post_quant_conv.* keys are ignored."""
+        """Accepts a full AutoencoderKL checkpoint: quant_conv.* / post_quant_conv.* keys are ignored, and so are encoder.* keys unless the
+        instance was built with_encoder=True (then decoder.* and encoder.* are loaded)."""
         if any(k.startswith("post_quant_conv.") for k in sd) and self.config.get("use_post_quant_conv", False):
             raise NotImplementedError("x2i_amd VAE: use_post_quant_conv=True is not supported (the FLUX VAE has none)")
-        dec = {k: v for k, v in sd.items() if k.startswith("decoder.")}
+        keep = ("decoder.", "encoder.") if self.with_encoder else ("decoder.",)
+        dec = {k: v for k, v in sd.items() if k.startswith(keep)}
         return super().load_state_dict(dec, strict=strict)
+
+    @torch.no_grad()
+    def encode(self, x, return_dict=True):
+        """diffusers AutoencoderKL.encode: x [B, in_channels, H, W] on the GPU, images in [-1, 1] (any float dtype, cast to bf16); H, W multiples
+        of 8 and (H / 8)(W / 8) a multiple of 8.  Returns an object with `.latent_dist` (a DiagonalGaussianDistribution), or (latent_dist,)."""
+        if not self.with_encoder:
+            raise RuntimeError("x2i_amd VAE: this AutoencoderKL is decoder-only; build it (or from_pretrained) with with_encoder=True to encode")
+        cfg, e = self.config, self.encoder
+        G = cfg.norm_num_groups
+        if x.dim() != 4 or x.shape[1] != cfg.in_channels:
+            raise ValueError("x2i_amd VAE encode: x must be [B, %d, H, W], got %s" % (cfg.in_channels, tuple(x.shape)))
+        if not x.is_floating_point():
+            raise ValueError("x2i_amd VAE encode: x must be a float tensor, got %s" % x.dtype)
+        B, _, H, W = x.shape
+        f = 2 ** (len(cfg.block_out_channels) - 1)
+        if H % f or W % f or H == 0 or W == 0:
+            raise ValueError("x2i_amd VAE encode: H and W must be positive multiples of %d, got %d x %d" % (f, H, W))
+        if ((H // f) * (W // f)) % 8:
+            raise ValueError("x2i_amd VAE encode: the mid-block token count (H/%d)(W/%d) = %d must be a multiple of 8 (row softmax kernel)"
+                             % (f, f, (H // f) * (W // f)))
+        boc = cfg.block_out_channels
+        x = x.to(torch.bfloat16).contiguous()
+        mom = _mom(x, boc[0])
+        h = ops.conv3x3_image(x, e.conv_in.weight, e.conv_in.bias, moments=mom)     # NCHW image -> NHWC, + the moments norm1 needs
+        for i, co in enumerate(boc):
+            blk = e.down_blocks[i]
+            for j in range(len(blk.resnets)):
+                h, mom = blk.resnets[j].run(h, H, W, G, mom, True)
+            if hasattr(blk, "downsamplers"):
+                # Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1)) + 3 x 3 stride-2 conv = top / left padding 0, the bottom / right zero row /
+                # column implied by out_h / out_w
+                w, b = blk.downsamplers[0].conv.packed()
+                mom = _mom(h, co)
+                h = ops.conv2d_nhwc(h, w, b, H, W, co, co, 3, 3, 2, 0, out_h=H // 2, out_w=W // 2, moments=mom)
+                H, W = H // 2, W // 2
+        c = boc[-1]
+        h, mom = e.mid_block.resnets[0].run(h, H, W, G, mom, True)
+        h = e.mid_block.attentions[0].run(h, H, W, G, mom)      # (a plain GEMM output: the next norm1 takes its own statistics)
+        h, mom = e.mid_block.resnets[1].run(h, H, W, G, None, True)
+        n = _gn(h, mom, e.conv_norm_out, G)
+        w, b = e.conv_out.packed()
+        params = ops.conv2d_nhwc(n, w, b, H, W, c, 2 * cfg.latent_channels, 3, 3, 1, 1)   # NHWC [B, h, w, 2 C]
+        dist = DiagonalGaussianDistribution(params, cfg.latent_channels, cfg.shift_factor, cfg.scaling_factor)
+        if not return_dict:
+            return (dist,)
+        return _Cfg(latent_dist=dist)
 
     @torch.no_grad()
     def decode(self, z, return_dict=True):
@@ -320,7 +502,7 @@ class AutoencoderKL(nn.Module):
 
     @classmethod
     def from_pretrained(cls, path, subfolder=None, torch_dtype=torch.bfloat16, device=None, **kw):
-        """diffusers directory layout: <path>/<subfolder>/config.json + *.safetensors (decoder.* keys are used)."""
+        """diffusers directory layout: <path>/<subfolder>/config.json + *.safetensors (decoder.* keys are used; encoder.* too with_encoder=True)."""
         import glob
         import json
         import os
@@ -335,7 +517,12 @@ class AutoencoderKL(nn.Module):
                 "shift_factor")
         if c.get("use_post_quant_conv", False):
             raise NotImplementedError("x2i_amd VAE: config has use_post_quant_conv=true; the decoder here starts at conv_in (FLUX)")
-        vae = cls(**{k: c[k] for k in keys if k in c}, device=device)
+        with_encoder = kw.get("with_encoder", False)
+        if with_encoder:
+            if c.get("use_quant_conv", False):
+                raise NotImplementedError("x2i_amd VAE: config has use_quant_conv=true; the encoder here ends at conv_out (FLUX)")
+            keys = keys + ("in_channels",)
+        vae = cls(**{k: c[k] for k in keys if k in c}, device=device, with_encoder=with_encoder)
         own = dict(vae.named_parameters())
         seen = set()
         for shard in sorted(glob.glob(os.path.join(d, "*.safetensors"))):
@@ -346,7 +533,7 @@ class AutoencoderKL(nn.Module):
                         seen.add(k)
         missing = set(own) - seen
         if missing:
-            raise KeyError("VAE checkpoint is missing decoder keys: %s ..." % sorted(missing)[:6])
+            raise KeyError("VAE checkpoint is missing %s keys: %s ..." % ("decoder / encoder" if with_encoder else "decoder", sorted(missing)[:6]))
         return vae.eval()
 
     @torch.no_grad()
