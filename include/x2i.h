@@ -17,8 +17,7 @@
  *     workspace_size query") -- weights are consumed in the reference's own nn.Linear [N,K] layout, fused only by
  *     row-concatenation on the host side, and every scratch buffer is a caller-owned argument sized by a query:
  *     x2i_groupnorm_scratch_floats, x2i_streamk_workspace_bytes (x2i_gemm_args.workspace, x2i_attention_vp_ws_bf16).  Process-wide state, all of it
- *     mutex-protected: the option table below and a per-kernel "dynamic LDS size already raised" cache.  (The measurement library additionally keeps one
- *     side stream with two events per device for the two-stream A/B form of the attention backward.)
+ *     mutex-protected: the option table below and a per-kernel "dynamic LDS size already raised" cache.
  *   - ABI version 5 (x2i_abi_version; 5 adds x2i_attention_vp_ws_bf16 -- no struct changed; x2i_conv3x3_image_bf16 and x2i_vae_posterior_bf16
  *     (the VAE encoder) were added under the same version: new entry points only, no struct or existing signature changed; 4 appended `w_group` to x2i_gemm_args, 0 = what version 3 did, and added the *_grouped entry points).  Since version 1: x2i_gemm_args grew `workspace` / `workspace_bytes`, x2i_qkv_desc `q_scale`
  *     and x2i_conv_desc a ninth field (version 2); version 3 re-defines that field as `pad_w_p1` (0 = same padding as `pad`, so that a
@@ -75,17 +74,17 @@ const char* x2i_last_error(void);
  * "train_rows_wg" (1: x2i_ln_mod_bwd_bf16 / x2i_gate_bwd_bf16 run a workgroup per row group with a thread per eight columns; 0: a wave per row --
  * same values up to the summation order of the row statistics),
  * "conv256" (1), "conv_w4" (1: convolutions with >= 256 output channels take the persistent four-wave kernel with the hand-scheduled K-loop,
- * csrc/gemm256c.hip; 0: the eight-wave one-tile form -- bit-identical), "attn_variant" (0 auto; 4 = 4-wave kernel, 8 = the 8-wave ping-pong
+ * csrc/gemm256c.hip; 0: the eight-wave one-tile form -- bit-identical), "attn_variant" (0 auto; 4 = 4-wave kernel, 5..8 = the 8-wave ping-pong
  * kernel, 9 = the hand-scheduled one-wave-per-SIMD kernel for any scale, 12 = the hand-scheduled kernel on 16x16x32 MFMAs (V^T span-permuted by the
- * caller -- tools and tests); the A/B forms 1..3, 5..7, 10, 11 exist only in the measurement library since round 6 and mean "automatic" here),
+ * caller -- tools and tests); any other value: the 4-wave kernel),
  * "conv5_variant" (0),
  * "fp8" (0; 2 = x2i_ln_modulate_fp8 keeps its per-row kernel at D = 3072, bit-identical A/B); "last_gemm_tile" is a read-back for tests: the tile edge of the kernel the
  * last GEMM / conv launch took (256, 128, 0 = generic kernel; +1000 = a peeled 128^2 tail launch followed).  Unknown names
  * return X2I_ERR_ARG.  Every setting selects between
  * kernels with identical results (bit-identical where the tests say so); the measurement-only kernels ("wrong results by
- * design" ablations) are NOT in this library -- they are compiled only into libx2i_hip_ablate.so (-DX2I_ABLATION), where
- * x2i_is_ablation_build() returns 1 and the extra options "gemm_lform", "gemm_ablate", "attn_ablate", "gemm_r2" (the "two residents" GEMM form,
- * csrc/gemm_r2.hip: measured 1.6x slower) exist together with the A/B attention forms (csrc/attention16.hip, the ping-pong schedules 0 / 1). */
+ * design" instruments) are NOT in this library -- they are compiled only into libx2i_hip_ablate.so (-DX2I_ABLATION), where
+ * x2i_is_ablation_build() returns 1, the persistent GEMM kernel carries the unit-timeline hooks of tools/gemm_unit_timeline.py (x2i_gemm_args.act2 /
+ * bias2) and the extra option "attn_ablate" (>= 100: the stream-K cut of the 16 x 16 x 32 attention kernel at key tile value - 100) exists. */
 int x2i_set_option(const char* name, int64_t value);
 int x2i_get_option(const char* name, int64_t* value);
 int x2i_is_ablation_build(void);

@@ -198,17 +198,6 @@ def test_attention_kernel_forms(ops, opt, variant, B, H, S, S0):
     assert _attention_case(ops, 1, 1, 640, 64, 300, spike=True) < 1e-2
 
 
-@pytest.mark.ablation
-@pytest.mark.parametrize("variant", [5, 6, 7, 10])
-@pytest.mark.parametrize("B,H,S,S0", _FORM_CASES)
-def test_attention_ab_forms_of_the_measurement_library(ops, opt, variant, B, H, S, S0):
-    """The A/B forms that live only in libx2i_hip_ablate.so since round 6: 5 / 6 = the ping-pong kernel's schedule 0 with / without defer-max,
-    7 = its schedule 1, 10 = the compiler-scheduled kernel on 16 x 16 x 32 MFMAs (attention16.hip)."""
-    opt("attn_variant", variant)
-    assert _attention_case(ops, B, H, S, S0, 200 + S) < 1e-2
-    assert _attention_case(ops, 1, 1, 640, 64, 300, spike=True) < 1e-2
-
-
 def test_attention_ping_pong_equals_four_wave_kernel_closely(ops, opt):
     """Same arithmetic per query row (tile order, defer-max rule, exp2 domain); only the wave -> row mapping differs, so the two
     kernels agree to the last bits of bf16 on the model's shape (B = 1, 24 heads, S = 4608)."""

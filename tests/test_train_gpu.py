@@ -483,13 +483,11 @@ def test_fused_attention_backward_vs_autograd(ops, B, H, S):
     assert torch.equal(dQ3, dQ2) and torch.equal(dK3, dK2) and torch.equal(dV3, dV2)
 
 
-@pytest.mark.ablation
 @pytest.mark.parametrize("S", [4608, 4600, 200, 640])
 def test_pipelined_attention_backward_bit_identical_at_model_length(ops, S):
-    """The software-pipelined dQ and dK / dV passes (the product's; one fused launch) against the round-2 phase-after-phase kernels, which live in the
-    measurement library (X2I_LIB_VARIANT=ablate: options attn_bwd_pipe / attn_bwd_dq64), at the model's sequence length (72 streamed tiles; S = 4600: a
-    ragged last tile, the masked form of the dQ pass) and at short ragged ones -- bit for bit, on random operands; also the 32-row dQ form and the
-    passes one after the other."""
+    """The software-pipelined dQ and dK / dV passes as the product launches them (one fused launch) against the same passes one after the other
+    (attn_bwd_overlap = 0), at the model's sequence length (72 streamed tiles; S = 4600: a ragged last tile, the masked form of the dQ pass) and at
+    short ragged ones -- bit for bit, on random operands, statistics pass included."""
     from x2i_amd import _lib
     B, H = 1, 2
     Spad = ops.pad128(S)
@@ -507,8 +505,7 @@ def test_pipelined_attention_backward_bit_identical_at_model_length(ops, S):
     Dv[:, :, :S] = torch.randn((B, H, S), device=DEV, generator=gen) * 0.1
     lse = torch.empty((B, H, Spad), device=DEV)
     outs = {}
-    forms = {"product": {}, "serial": {"attn_bwd_overlap": 0}, "round 2": {"attn_bwd_pipe": 0}, "round 2, 32-row dQ": {"attn_bwd_pipe": 0, "attn_bwd_dq64": 0},
-             "round 2, serial": {"attn_bwd_pipe": 0, "attn_bwd_overlap": 0}}
+    forms = {"product": {}, "serial": {"attn_bwd_overlap": 0}}
     for name, opts in forms.items():
         old = {k: _lib.set_option(k, v) for k, v in opts.items()}
         try:

@@ -28,24 +28,22 @@ def main():
     rnd = lambda *sh: torch.randn(sh, device="cuda").bfloat16()  # noqa: E731
     Q, K_, VT = rnd(B, H, Spad, 128), rnd(B, H, Spad, 128), rnd(B, H, 128, Spad)
     O = torch.empty((B, S, D), device="cuda", dtype=torch.bfloat16)
-    names = {4: "4-wave", 5: "ping-pong", 7: "ping-pong, DMA in vector phase", 8: "ping-pong, 4-deep rings + fragment prefetch",
-             9: "hand-scheduled, one wave per SIMD (attention_w4.hip)", 10: "4-wave organisation on 16x16x32 MFMAs (attention16.hip, A/B)"}
+    names = {4: "4-wave", 8: "ping-pong, 4-deep rings + fragment prefetch", 9: "hand-scheduled, one wave per SIMD (attention_w4.hip)",
+             12: "hand-scheduled, one wave per SIMD, 16x16x32 MFMAs (attention_w16.hip, V^T pre-permuted)"}
     ref = None
     perm = torch.tensor([16 * ((kk >> 2) & 1) + 4 * (kk >> 3) + (kk & 3) for kk in range(32)], device="cuda")
-    VTP = VT.view(B, H, 128, Spad // 32, 32)[..., perm].reshape(B, H, 128, Spad).contiguous()   # variant 11: keys permuted within 32-key spans
-    names[11] = "... with V^T pre-permuted (one 16-byte fragment read)"
-    names[12] = "hand-scheduled, one wave per SIMD, 16x16x32 MFMAs (attention_w16.hip, V^T pre-permuted)"
-    for var in (4, 10, 11, 12):   # the 16x16x32 A/B kernel against its 32x32x16 partner: same values up to rounding?
+    VTP = VT.view(B, H, 128, Spad // 32, 32)[..., perm].reshape(B, H, 128, Spad).contiguous()   # variant 12: keys permuted within 32-key spans
+    for var in (4, 12):   # the 16x16x32 kernel against the 32x32x16 4-wave kernel: same values up to rounding?
         _lib.set_option("attn_variant", var)
-        ops.attention(Q, K_, VTP if var >= 11 else VT, O, B, H, S, Spad, D, S * D, 1 / math.sqrt(128))
+        ops.attention(Q, K_, VTP if var == 12 else VT, O, B, H, S, Spad, D, S * D, 1 / math.sqrt(128))
         torch.cuda.synchronize()
         if ref is None:
             ref = O.float().clone()
         else:
             print(f"variant {var} vs variant 4: rel-L2 {float((O.float() - ref).norm() / ref.norm()):.3e}")
-    for var in (9, 12, 8, 4, 10, 11, 9, 12, 8, 4, 9, 12):
+    for var in (9, 12, 8, 4, 9, 12, 8, 4, 9, 12):
         _lib.set_option("attn_variant", var)
-        t = timeit(lambda: ops.attention(Q, K_, VTP if var >= 11 else VT, O, B, H, S, Spad, D, S * D, 1 / math.sqrt(128)))
+        t = timeit(lambda: ops.attention(Q, K_, VTP if var == 12 else VT, O, B, H, S, Spad, D, S * D, 1 / math.sqrt(128)))
         print(f"attention[{names[var]}] B={B}: {t*1e3:8.3f} ms  {4*B*H*S*S*128/t/1e12:8.1f} TFLOP/s")
     _lib.set_option("attn_variant", 0)
 
@@ -73,8 +71,7 @@ def backward_bench():
     # without the statistics pass (the training step hands over the forward kernel's statistics), per option set; passes one after the other
     # (attn_bwd_overlap = 0) so that each pass's own time shows
     fl7 = (3 + 4) * 2 * B * H * S * S * 128
-    abl = bool(_lib.load().x2i_is_ablation_build())   # the round-2 kernels (attn_bwd_pipe = 0) live in the measurement library: X2I_LIB_VARIANT=ablate
-    for opts in (({}, {"attn_bwd_pipe": 0}, {"attn_bwd_overlap": 0}, {"attn_bwd_overlap": 0, "attn_bwd_pipe": 0}, {}) if abl else ({}, {"attn_bwd_overlap": 0}, {})):
+    for opts in ({}, {"attn_bwd_overlap": 0}, {}):
         old = {k: _lib.set_option(k, v) for k, v in opts.items()}
         t = timeit(lambda: ops.attention_bwd(Q, K_, V, QT, KT, dOh, dOT, L, Dv, dQ, dK, dV, B, H, S, Spad, 1 / math.sqrt(128), have_lse=True))
         for k, v in old.items():

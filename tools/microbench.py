@@ -8,9 +8,6 @@ import os
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ABLATE = "--ablate" in sys.argv  # also time the attention ablation variants (needs the measurement-only library)
-if ABLATE:
-    os.environ["X2I_LIB_VARIANT"] = "ablate"
 from x2i_amd import _lib, ops  # noqa: E402
 
 DEV = "cuda"
@@ -56,20 +53,11 @@ def main():
     Q, K_ = rnd(B, H, Spad, 128), rnd(B, H, Spad, 128)
     VT = rnd(B, H, 128, Spad)
     O = torch.empty((B, S, D), device=DEV, dtype=torch.bfloat16)
-    for var, nm in (("4", "4-wave thr8"), ("1", "nw8 lockstep thr8"), ("2", "nw4 thr0"), ("5", "ping-pong thr8"), ("7", "ping-pong, DMA in vector phase"), ("5", "ping-pong thr8"), ("7", "ping-pong, DMA in vector phase"), ("4", "4-wave thr8")):
+    for var, nm in (("4", "4-wave"), ("8", "ping-pong"), ("9", "one wave per SIMD"), ("4", "4-wave"), ("8", "ping-pong")):
         _lib.set_option("attn_variant", int(var))
         t = timeit(lambda: ops.attention(Q, K_, VT, O, B, H, S, Spad, D, S * D, 1 / math.sqrt(128)))
         print(f"attention[{nm}] B={B} H={H} S={S}: {t*1e3:8.3f} ms  {4*B*H*S*S*128/t/1e12:8.1f} TFLOP/s")
     _lib.set_option("attn_variant", 0)
-    for abl, nm in (("0", "full"), ("1", "no softmax"), ("2", "no barrier/wait"), ("4", "no DMA"), ("7", "MFMA+LDS reads only"), ("0", "full"),
-                    ("32", "branchy loop (no peel)"), ("0", "full"), ("32", "branchy loop (no peel)"), ("0", "full")):
-        if not ABLATE:
-            break
-        _lib.set_option("attn_ablate", int(abl))
-        t = timeit(lambda: ops.attention(Q, K_, VT, O, B, H, S, Spad, D, S * D, 1 / math.sqrt(128)))
-        print(f"attention-ablate[{nm}]: {t*1e3:8.3f} ms  {4*B*H*S*S*128/t/1e12:8.1f} TFLOP/s")
-    if ABLATE:
-        _lib.set_option("attn_ablate", 0)
     # qkv split
     qkv = rnd(B * S, 3 * D)
     nw = rnd(128)

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # X2I_LIB_VARIANT=<name> (read once, at import) makes tools/ load libx2i_hip_<name>.so instead: "ablate" = the measurement-only build
-# (ablation kernels, k-half-unit GEMM form), anything else = a library built from another commit for a same-box A/B.  The product
+# (the GEMM unit-timeline hooks, the forced stream-K cut of the 16x16x32 attention), anything else = a library built from another commit for a same-box A/B.  The product
 # package never sets it.
 _VARIANT = os.environ.get("X2I_LIB_VARIANT", "")
 LIB_PATH = os.path.join(_HERE, "libx2i_hip_%s.so" % _VARIANT if _VARIANT else "libx2i_hip.so")

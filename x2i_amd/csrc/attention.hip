@@ -40,10 +40,8 @@ __device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-// ABL (measurement only, wrong results; tools/microbench.py): 1 = no softmax VALU, 2 = no barrier/wait after the first
-// tile, 4 = no DMA after the first tile.  ABL = 0 is the product kernel.
 // OUT8: the output is e4m3 (sat(o * oinv)), 8 bytes per lane and d-group -- the A operand of an fp8 projection (x2i_attention_e4m3out)
-template <int NW, int THR, int ABL = 0, bool OUT8 = false>
+template <int NW, int THR, bool OUT8 = false>
 __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                            const bf16_t* __restrict__ VT, bf16_t* __restrict__ O, int H, int S,
                                                            int Spad, int ldo, long long o_bs, float scale_log2, int nbatch,
@@ -124,10 +122,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const bf16_t* __re
   // One key/value tile.  LAST = false: a successor tile exists and every key is valid, so the prefetch and the score path
   // carry no branches (one basic block up to the rescale test); the final tile handles the ragged tail.
   auto kv_tile = [&](int t, auto last_c) {
-    constexpr int MODE = decltype(last_c)::value;  // 0 steady, 1 last, 2 general (runtime tests; A/B reference, ABL & 32)
-    constexpr bool LAST = MODE != 0;
+    constexpr bool LAST = decltype(last_c)::value;
     const int buf = t & 1;
-    if ((MODE == 0 || (MODE == 2 && t + 1 < ntiles)) && !((ABL & 4) && t > 0)) stage(buf ^ 1, (t + 1) * KVB);
+    if (!LAST) stage(buf ^ 1, (t + 1) * KVB);
     const char* kb = smem + buf * (KTILE + VTILE);
     const char* vb = kb + KTILE;
 
@@ -171,15 +168,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const bf16_t* __re
           if (key >= S) sacc[u][r] = NEG_BIG;
         }
     }
-    if (ABL & 1) {  // ablation: skip the softmax VALU work (keep the data dependence QK -> P -> PV)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; r += 4) sacc[u][r] = sacc[u][r] * 0.001f;
-    }
     // ---- online softmax (scores scaled into the exp2 domain)
     float mx = NEG_BIG;
-    if (!(ABL & 1)) {
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -207,7 +197,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const bf16_t* __re
         for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
     }
     m_run = m_new;
-    }
 
     // ---- P^T fragments (B operand): sub-tile u, k-step kt uses regs 8kt..8kt+7  (keys u*32+16kt+8hi+0..7)
     bf16x8_t pf[2][2];
@@ -243,17 +232,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const bf16_t* __re
       }
     }
 
-    if (!((ABL & 2) && t > 0)) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // next tile's DMA (issued by this wave) has landed
-      __syncthreads();
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // next tile's DMA (issued by this wave) has landed
+    __syncthreads();
   };
-  if (ABL & 32) {
-    for (int t = 0; t < ntiles; ++t) kv_tile(t, std::integral_constant<int, 2>{});
-  } else {
-    for (int t = 0; t < ntiles - 1; ++t) kv_tile(t, std::integral_constant<int, 0>{});
-    kv_tile(ntiles - 1, std::integral_constant<int, 1>{});
-  }
+  for (int t = 0; t < ntiles - 1; ++t) kv_tile(t, std::false_type{});
+  kv_tile(ntiles - 1, std::true_type{});
 
   // ---- epilogue: O[q][d] = O^T[d][q] / l ; lane (q = li, hi) holds d = db*32 + 8*(r>>2) + 4*hi + (r&3)
   l_run = xhalf_sum(l_run);
@@ -322,7 +305,7 @@ int x2i_launch_attention(const void* Q, const void* K, const void* VT, void* O, 
   const bool unit = fabsf(scale_log2 - 1.f) < 1e-6f;
   if (unit) scale_log2 = 1.f;
   const X2IOptions& opt = x2i_options();
-  const int var = opt.attn_variant;  // 0 = automatic; A/B: 1 = 8 lock-step waves, 2 = no defer-max, 3 = both, 4 = 4-wave kernel, 5 / 6 = ping-pong schedule 0 (defer-max / none), 7 / 8 = ping-pong schedules 1 / 2
+  const int var = opt.attn_variant;  // 0 = automatic; A/B: 5..8 = the ping-pong kernel, 9 = attention_w4.hip, 12 = attention_w16.hip, any other = the 4-wave kernel
   // a Q that already carries the scale and sequences long enough that ONE sample's 256-row workgroups fill half the chip: the
   // hand-scheduled one-wave-per-SIMD kernel (attention_w4.hip), whose softmax has no multiply.  The rule looks at the sequence, not at
   // the batch: this kernel rounds differently from the 4-wave / ping-pong pair (which are bit-identical to each other), and a
@@ -337,57 +320,24 @@ int x2i_launch_attention(const void* Q, const void* K, const void* VT, void* O, 
     const int rc = x2i_launch_attention_w16(Q, K, VT, O, B, H, S, Spad, ldo, o_bs, scale_log2, unit ? 0 : 1, stream, lse);
     if (rc != X2I_ERR_STATE) return rc;
   }
-#ifdef X2I_ABLATION   // (measurement library only since round 6)
-  if ((var == 10 || var == 11) && !out8) {   // (11: V^T arrives with the 32-key-span permutation of attention16.hip -- tools only)   // A/B: the 16 x 16 x 32 MFMA shape (attention16.hip; compare with variant 4, the same organisation on 32 x 32 x 16)
-    const int rc = x2i_launch_attention_16(Q, K, VT, O, B, H, S, Spad, ldo, o_bs, scale_log2, stream, lse, var == 11);
-    if (rc != X2I_ERR_STATE) return rc;
-  }
-#endif
   // the 8-wave ping-pong kernel (attention_pp.hip)
   if ((var == 0 && (long long)((S + 255) / 256) * H * B >= 256) || var == 5 || var == 6 || var == 7 || var == 8) {
-    const int rc = x2i_launch_attention_pp(Q, K, VT, O, B, H, S, Spad, ldo, o_bs, scale_log2, stream, out8, oinv, var == 6 ? 0 : 8, lse);
+    const int rc = x2i_launch_attention_pp(Q, K, VT, O, B, H, S, Spad, ldo, o_bs, scale_log2, stream, out8, oinv, lse);
     if (rc != X2I_ERR_STATE) return rc;  // X2I_ERR_STATE: shape / alignment not served by that kernel -> fall through
   }
-#define X2I_ATTN_LAUNCH(NW_, THR_)                                                                                          \
-  {                                                                                                                         \
-    const int rc_ = x2i_ensure_dynamic_smem((const void*)attn_fwd_kernel<NW_, THR_>, (int)shm);                             \
-    if (rc_) return rc_;                                                                                                    \
-    dim3 grid(((S + 32 * NW_ - 1) / (32 * NW_)) * H * B);                                                                   \
-    hipLaunchKernelGGL((attn_fwd_kernel<NW_, THR_>), grid, dim3(NW_ * 64), shm, stream, (const bf16_t*)Q, (const bf16_t*)K, \
-                       (const bf16_t*)VT, (bf16_t*)O, H, S, Spad, ldo, o_bs, scale_log2, B, 1.f, lse);                      \
-  }
+  // the 4-wave kernel
   if (out8) {
-    const int rc_ = x2i_ensure_dynamic_smem((const void*)attn_fwd_kernel<4, 8, 0, true>, (int)shm);
+    const int rc_ = x2i_ensure_dynamic_smem((const void*)attn_fwd_kernel<4, 8, true>, (int)shm);
     if (rc_) return rc_;
     dim3 grid(((S + 127) / 128) * H * B);
-    hipLaunchKernelGGL((attn_fwd_kernel<4, 8, 0, true>), grid, dim3(256), shm, stream, (const bf16_t*)Q, (const bf16_t*)K,
+    hipLaunchKernelGGL((attn_fwd_kernel<4, 8, true>), grid, dim3(256), shm, stream, (const bf16_t*)Q, (const bf16_t*)K,
                        (const bf16_t*)VT, (bf16_t*)O, H, S, Spad, ldo, o_bs, scale_log2, B, oinv, lse);
     return x2i_check_launch("attention");
   }
-#ifdef X2I_ABLATION
-  const int abl = opt.attn_ablate;  // measurement-only variants (tools/microbench.py), wrong results by design
-#define X2I_ATTN_LAUNCH_ABL(A_)                                                                                              \
-  {                                                                                                                          \
-    const int rc_ = x2i_ensure_dynamic_smem((const void*)attn_fwd_kernel<4, 8, A_>, (int)shm);                               \
-    if (rc_) return rc_;                                                                                                     \
-    dim3 grid(((S + 127) / 128) * H * B);                                                                                    \
-    hipLaunchKernelGGL((attn_fwd_kernel<4, 8, A_>), grid, dim3(256), shm, stream, (const bf16_t*)Q, (const bf16_t*)K,        \
-                       (const bf16_t*)VT, (bf16_t*)O, H, S, Spad, ldo, o_bs, scale_log2, B, 1.f, lse);                       \
-  }
-  if (abl == 1) X2I_ATTN_LAUNCH_ABL(1)
-  else if (abl == 2) X2I_ATTN_LAUNCH_ABL(2)
-  else if (abl == 4) X2I_ATTN_LAUNCH_ABL(4)
-  else if (abl == 7) X2I_ATTN_LAUNCH_ABL(7)
-  else if (abl == 32) X2I_ATTN_LAUNCH_ABL(32)
-  else
-#endif
-#ifdef X2I_ABLATION   // (A/B forms 1 = eight lock-step waves, 2 = no defer-max, 3 = both: measurement library only since round 6)
-  if (var == 1) X2I_ATTN_LAUNCH(8, 8)
-  else if (var == 2) X2I_ATTN_LAUNCH(4, 0)
-  else if (var == 3) X2I_ATTN_LAUNCH(8, 0)
-  else
-#endif
-  X2I_ATTN_LAUNCH(4, 8)
-#undef X2I_ATTN_LAUNCH
+  const int rc_ = x2i_ensure_dynamic_smem((const void*)attn_fwd_kernel<4, 8>, (int)shm);
+  if (rc_) return rc_;
+  dim3 grid(((S + 127) / 128) * H * B);
+  hipLaunchKernelGGL((attn_fwd_kernel<4, 8>), grid, dim3(256), shm, stream, (const bf16_t*)Q, (const bf16_t*)K,
+                     (const bf16_t*)VT, (bf16_t*)O, H, S, Spad, ldo, o_bs, scale_log2, B, 1.f, lse);
   return x2i_check_launch("attention");
 }

@@ -4,12 +4,12 @@
 // per wave held as MFMA B operands, v_mfma_f32_32x32x16_bf16 with the bit-2/3 row permutation that makes the probability registers
 // the next MFMA's B operand directly).
 //
-// With L2[q] = log2 sum_j exp(scale s_qj) (pass 2 below) and D[q] = sum_d dO[q][d] O[q][d] (attn_bwd_prep_kernel):
+// With L2[q] = log2 sum_j exp(scale s_qj) (attn_bwd_stats_kernel) and D[q] = sum_d dO[q][d] O[q][d] (attn_bwd_prep_kernel):
 //     P = exp2(scale_log2 S - L2),   dP = dO V^T,   dS = P * (dP - D),   dQ = scale dS K,   dK = scale dS^T Q,   dV = P^T dO
 //
-//   MODE 2  statistics : persistent 128-query block, streams K tiles, online max / sum            -> L2            (1 MFMA group / tile)
-//   MODE 0  dQ         : persistent queries (Q and dO rows as B operands), streams K, V, K^T      -> dQ            (3 groups / tile)
-//   MODE 1  dK, dV     : persistent keys (K and V rows as B operands), streams Q, dO, dO^T, Q^T   -> dV, dK        (4 groups / tile)
+//   statistics : persistent 128-query block, streams K tiles, online max / sum                     -> L2       (attn_bwd_stats_kernel)
+//   dQ         : persistent queries (Q and dO rows as B operands), streams K, V, K^T               -> dQ       (attn_bwd_dq_kernel)
+//   dK, dV     : persistent keys (K and V rows as B operands), streams Q, dO, dO^T, Q^T            -> dV, dK   (attn_bwd_dkdv_kernel)
 //
 // Two passes over the score matrix instead of atomics on dQ: deterministic, and each pass is the forward kernel's loop with other
 // operands.  Operand layouts: row-major [B,H,Spad,128] for Q, K, V, dO; transposed [B,H,128,Spad] for K^T, Q^T, dO^T -- produced
@@ -67,83 +67,6 @@ __device__ __forceinline__ void score_mma(const char* tb, const Geo& G, const bf
     __builtin_amdgcn_sched_barrier(0);
   }
 }
-// oacc[d-block] += transposed tile x probability-like fragments  (the forward's O^T += V^T P^T loop)
-__device__ __forceinline__ void accum_mma(const char* tb, const Geo& G, const bf16x8_t (&pf)[2][2], f32x16_t (&oacc)[4]) {
-  bf16x8_t fr[2][4];
-#pragma unroll
-  for (int db = 0; db < 4; ++db) fr[0][db] = col_frag(tb, G, 0, db);
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    if (g < 3) {
-#pragma unroll
-      for (int db = 0; db < 4; ++db) fr[(g + 1) & 1][db] = col_frag(tb, G, g + 1, db);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int db = 0; db < 4; ++db) oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[g & 1][db], pf[g >> 1][g & 1], oacc[db], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-// The two score products of a tile as ONE fragment pipeline (steps 0-3: rows of tile A x pa -> sa, steps 4-7: rows of tile B x pb -> sb):
-// no LDS-latency bubble between them.  NS = 4 runs the first product only.
-template <int NS>
-__device__ __forceinline__ void score_phase(const char* ta, const char* tb, const Geo& G, const bf16x8_t (&pa)[8], const bf16x8_t (&pb)[8],
-                                            f32x16_t (&sa)[2], f32x16_t (&sb)[2]) {
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { sa[u][r] = 0.f; sb[u][r] = 0.f; }
-  bf16x8_t fr[2][4];
-#pragma unroll
-  for (int f = 0; f < 4; ++f) fr[0][f] = row_frag(ta, G, 0, f);
-#pragma unroll
-  for (int st = 0; st < NS; ++st) {
-    if (st + 1 < NS) {
-#pragma unroll
-      for (int f = 0; f < 4; ++f) fr[(st + 1) & 1][f] = row_frag(st + 1 < 4 ? ta : tb, G, (st + 1) & 3, f);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const int g = st & 3;
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      if (st < 4) sa[f & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[st & 1][f], pa[2 * g + (f >> 1)], sa[f & 1], 0, 0, 0);
-      else sb[f & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[st & 1][f], pb[2 * g + (f >> 1)], sb[f & 1], 0, 0, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-// The accumulation products of a tile as one pipeline whose first fragments (`fr0`) were read BEFORE the element-wise section:
-// steps 0-3: transposed tile C x f0 -> o0; steps 4-7 (NS = 8): transposed tile D x f1 -> o1.
-template <int NS>
-__device__ __forceinline__ void accum_phase(const char* tc, const char* td, const Geo& G, const bf16x8_t (&f0)[2][2], const bf16x8_t (&f1)[2][2],
-                                            f32x16_t (&o0)[4], f32x16_t (&o1)[4], bf16x8_t (&fr)[2][4]) {
-#pragma unroll
-  for (int st = 0; st < NS; ++st) {
-    if (st + 1 < NS) {
-#pragma unroll
-      for (int db = 0; db < 4; ++db) fr[(st + 1) & 1][db] = col_frag(st + 1 < 4 ? tc : td, G, (st + 1) & 3, db);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const int g = st & 3;
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      if (st < 4) o0[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[st & 1][db], f0[g >> 1][g & 1], o0[db], 0, 0, 0);
-      else o1[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[st & 1][db], f1[g >> 1][g & 1], o1[db], 0, 0, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-__device__ __forceinline__ void pack_frags(const f32x16_t (&a)[2], bf16x8_t (&pf)[2][2]) {
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-      union { bf16x8_t v; uint32_t w[4]; } cv;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) cv.w[j] = pack_bf16x2(a[u][kt * 8 + 2 * j], a[u][kt * 8 + 2 * j + 1]);
-      pf[u][kt] = cv.v;
-    }
-}
 // out[row][d] = alpha * acc^T: lane (row = li, hi) holds d = db*32 + 8*(r>>2) + 4*hi + (r&3); half-wave exchange -> 16-byte stores
 __device__ __forceinline__ void store_rows(bf16_t* orow, const f32x16_t (&acc)[4], float alpha, int hi, bool live) {
 #pragma unroll
@@ -164,109 +87,44 @@ struct Rsrc4 {
   __amdgpu_buffer_rsrc_t a, b, c, d;
 };
 
-// One streamed tile: start the DMA of the next tile into `nxt`, then run this tile's MFMA groups on `cur`.  cur / nxt are __restrict__
-// parameters of one function so that hipcc can tell the fragment reads from the buffer being filled (else every ds_read behind a DMA
-// issue gets a conservative vmcnt(0)).
-template <int MODE>
-__device__ __forceinline__ void bwd_tile(const char* __restrict__ cur, char* __restrict__ nxt, bool issue, int s_next, int s0, const Rsrc4& R,
-                                         const int (&row_src)[4], const int (&col_src)[4], int wave, const Geo& G, const bf16x8_t (&pa)[8],
-                                         const bf16x8_t (&pb)[8], float myL, float myD, const float* __restrict__ L2h,
-                                         const float* __restrict__ Dh, int S, float scale_log2, f32x16_t (&oacc0)[4], f32x16_t (&oacc1)[4],
-                                         float& m_run, float& l_run) {
+// Statistics pass, one streamed K tile: start the DMA of the next tile into `nxt`, then the score product of this tile on `cur` and the
+// online max / sum of scale_log2 * s over the valid keys.  cur / nxt are __restrict__ parameters of one function so that hipcc can tell the
+// fragment reads from the buffer being filled (else every ds_read behind a DMA issue gets a conservative vmcnt(0)).
+__device__ __forceinline__ void stats_tile(const char* __restrict__ cur, char* __restrict__ nxt, bool issue, int s_next, int s0,
+                                           __amdgpu_buffer_rsrc_t rk, const int (&row_src)[4], int wave, const Geo& G, const bf16x8_t (&pq)[8],
+                                           int S, float scale_log2, float& m_run, float& l_run) {
   if (issue) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      char* dst = nxt + (j * 256 + wave * 64) * 16;
-      dma16(R.a, (uint32_t)(s_next * 256 + row_src[j] * 2), dst);
-      if (MODE != 2) {
-        dma16(R.b, (uint32_t)(s_next * 256 + row_src[j] * 2), dst + TILE);
-        dma16(R.c, (uint32_t)(s_next * 2 + col_src[j] * 2), dst + 2 * TILE);
-        if (MODE == 1) dma16(R.d, (uint32_t)(s_next * 2 + col_src[j] * 2), dst + 3 * TILE);
-      }
+    for (int j = 0; j < 4; ++j) dma16(rk, (uint32_t)(s_next * 256 + row_src[j] * 2), nxt + (j * 256 + wave * 64) * 16);
+  }
+  f32x16_t sacc[2];
+  score_mma(cur, G, pq, sacc);
+  // lane (hi), sub-tile u, reg r <-> key s0 + u*32 + 16*(r>>3) + 8*hi + (r&7)
+  float mx = -BIG;
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = s0 + u * 32 + 16 * (r >> 3) + 8 * G.hi + (r & 7);
+      sacc[u][r] = key < S ? sacc[u][r] * scale_log2 : -BIG;
+      mx = fmaxf(mx, sacc[u][r]);
     }
-  }
-  f32x16_t sacc[2], dacc[2];
-  // per streamed row statistics (MODE 1): lane (hi), sub-tile u, reg r <-> row s0 + u*32 + 16*(r>>3) + 8*hi + (r&7)
-  float Lr[2][16], Dr[2][16];
-  if (MODE == 1) {
+  mx = xhalf_max(mx);
+  const float m_new = fmaxf(m_run, mx);
+  float ps = 0.f;
 #pragma unroll
-    for (int u = 0; u < 2; ++u)
+  for (int u = 0; u < 2; ++u)
 #pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        const int o = s0 + u * 32 + 16 * a + 8 * G.hi;
-        const f32x4_t l0 = *(const f32x4_t*)(L2h + o), l1 = *(const f32x4_t*)(L2h + o + 4);
-        const f32x4_t d0 = *(const f32x4_t*)(Dh + o), d1 = *(const f32x4_t*)(Dh + o + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          Lr[u][8 * a + j] = l0[j]; Lr[u][8 * a + 4 + j] = l1[j];
-          Dr[u][8 * a + j] = d0[j]; Dr[u][8 * a + 4 + j] = d1[j];
-        }
-      }
-  }
-  if (MODE == 2) {
-    score_phase<4>(cur, cur, G, pa, pa, sacc, dacc);
-    // online max / sum of scale_log2 * s over the valid keys
-    float mx = -BIG;
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = s0 + u * 32 + 16 * (r >> 3) + 8 * G.hi + (r & 7);
-        sacc[u][r] = key < S ? sacc[u][r] * scale_log2 : -BIG;
-        mx = fmaxf(mx, sacc[u][r]);
-      }
-    mx = xhalf_max(mx);
-    const float m_new = fmaxf(m_run, mx);
-    float ps = 0.f;
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ps += __builtin_amdgcn_exp2f(sacc[u][r] - m_new);
-    l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_new) + ps;
-    m_run = m_new;
-  } else {
-    score_phase<8>(cur, cur + TILE, G, pa, pb, sacc, dacc);
-    // first fragments of the accumulation pipeline: in flight while the element-wise section runs
-    bf16x8_t fr[2][4];
-#pragma unroll
-    for (int db = 0; db < 4; ++db) fr[0][db] = col_frag(cur + 2 * TILE, G, 0, db);
-    f32x16_t pv[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float p;
-        if (MODE == 0) {
-          const int key = s0 + u * 32 + 16 * (r >> 3) + 8 * G.hi + (r & 7);
-          p = key < S ? __builtin_amdgcn_exp2f(sacc[u][r] * scale_log2 - myL) : 0.f;
-          dacc[u][r] = p * (dacc[u][r] - myD);
-        } else {
-          p = __builtin_amdgcn_exp2f(sacc[u][r] * scale_log2 - Lr[u][r]);
-          dacc[u][r] = p * (dacc[u][r] - Dr[u][r]);
-        }
-        pv[u][r] = p;
-      }
-    bf16x8_t dsf[2][2];
-    pack_frags(dacc, dsf);
-    if (MODE == 0) {
-      accum_phase<4>(cur + 2 * TILE, cur + 2 * TILE, G, dsf, dsf, oacc0, oacc1, fr);   // dQ^T += K^T dS^T
-    } else {
-      bf16x8_t pf[2][2];
-      pack_frags(pv, pf);
-      accum_phase<8>(cur + 2 * TILE, cur + 3 * TILE, G, pf, dsf, oacc0, oacc1, fr);   // dV^T += dO^T P;  dK^T += Q^T dS
-    }
-  }
+    for (int r = 0; r < 16; ++r) ps += __builtin_amdgcn_exp2f(sacc[u][r] - m_new);
+  l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_new) + ps;
+  m_run = m_new;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256, 1) void attn_bwd_kernel(const bf16_t* __restrict__ PA, const bf16_t* __restrict__ PB,
-                                                         const bf16_t* __restrict__ TA, const bf16_t* __restrict__ TB,
-                                                         const bf16_t* __restrict__ TC, const bf16_t* __restrict__ TD, float* __restrict__ L2,
-                                                         const float* __restrict__ Dv, bf16_t* __restrict__ OUT0, bf16_t* __restrict__ OUT1,
-                                                         int H, int S, int Spad, float scale, float scale_log2, int nbatch) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NTILE = MODE == 2 ? 1 : MODE == 0 ? 3 : 4;  // tiles per stage
-  constexpr int STAGE = NTILE * TILE;
+// Statistics pass: L2 of a persistent 128-query block (32 query rows per wave, held as MFMA B operands) from the streamed K tiles.  Rows >= S
+// get +big, so that P = 0 on them in the gradient passes.
+__global__ __launch_bounds__(256, 1) void attn_bwd_stats_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, float* __restrict__ L2,
+                                                               int H, int S, int Spad, float scale_log2) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][K tile]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   Geo G;
@@ -284,242 +142,39 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kernel(const bf16_t* __restri
   const int blk = bid % nblk, h = (bid / nblk) % H, b = bid / (nblk * H);
   const long long bh = (long long)b * H + h;
   const long long hoff = bh * Spad * 128;
-  const int r0 = blk * 128 + wave * 32 + G.li;   // this lane's persistent row (query in MODE 0 / 2, key in MODE 1)
+  const int r0 = blk * 128 + wave * 32 + G.li;   // this lane's query row
 
-  bf16x8_t pa[8], pb[8];
+  bf16x8_t pq[8];
 #pragma unroll
-  for (int ds = 0; ds < 8; ++ds) {
-    pa[ds] = *(const bf16x8_t*)(PA + hoff + (long long)r0 * 128 + ds * 16 + G.hi * 8);
-    if (MODE != 2) pb[ds] = *(const bf16x8_t*)(PB + hoff + (long long)r0 * 128 + ds * 16 + G.hi * 8);
-  }
-  float myL = 0.f, myD = 0.f;
-  if (MODE == 0) { myL = L2[bh * Spad + r0]; myD = Dv[bh * Spad + r0]; }
-
+  for (int ds = 0; ds < 8; ++ds) pq[ds] = *(const bf16x8_t*)(Q + hoff + (long long)r0 * 128 + ds * 16 + G.hi * 8);
   // DMA source offsets: 1024 chunks per tile, 4 per thread
-  int row_src[4], col_src[4];
+  int row_src[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int p = j * 256 + tid;
-    { const int row = p >> 4, c = p & 15; row_src[j] = row * 128 + ((c ^ (row & 15)) << 3); }
-    { const int row = p >> 3, c = p & 7; col_src[j] = row * Spad + ((c ^ ((row >> 1) & 7)) << 3); }
+    const int p = j * 256 + tid, row = p >> 4, c = p & 15;
+    row_src[j] = row * 128 + ((c ^ (row & 15)) << 3);
   }
-  Rsrc4 R;
-  {
-    const uint32_t bytes = (uint32_t)Spad * 256u;
-    R.a = __builtin_amdgcn_make_buffer_rsrc((void*)(TA + hoff), 0, bytes, 0x00020000);
-    R.b = __builtin_amdgcn_make_buffer_rsrc((void*)((MODE != 2 ? TB : TA) + hoff), 0, bytes, 0x00020000);
-    R.c = __builtin_amdgcn_make_buffer_rsrc((void*)((MODE != 2 ? TC : TA) + hoff), 0, bytes, 0x00020000);
-    R.d = __builtin_amdgcn_make_buffer_rsrc((void*)((MODE == 1 ? TD : TA) + hoff), 0, bytes, 0x00020000);
-  }
-  f32x16_t oacc0[4], oacc1[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { oacc0[i][r] = 0.f; oacc1[i][r] = 0.f; }
+  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)(K + hoff), 0, (uint32_t)Spad * 256u, 0x00020000);
   float m_run = -BIG, l_run = 0.f;
-  const float* L2h = L2 + bh * Spad;
-  const float* Dh = Dv + bh * Spad;
 
   const int nt = (S + KVB - 1) / KVB;
-  {  // prologue: tile 0 (bwd_tile with nothing to compute would need a third form)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      char* dst = smem + (j * 256 + wave * 64) * 16;
-      dma16(R.a, (uint32_t)(row_src[j] * 2), dst);
-      if (MODE != 2) {
-        dma16(R.b, (uint32_t)(row_src[j] * 2), dst + TILE);
-        dma16(R.c, (uint32_t)(col_src[j] * 2), dst + 2 * TILE);
-        if (MODE == 1) dma16(R.d, (uint32_t)(col_src[j] * 2), dst + 3 * TILE);
-      }
-    }
-  }
+  for (int j = 0; j < 4; ++j) dma16(rk, (uint32_t)(row_src[j] * 2), smem + (j * 256 + wave * 64) * 16);   // tile 0
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   for (int t = 0; t < nt; ++t) {
     const int buf = t & 1;
-    bwd_tile<MODE>(smem + buf * STAGE, smem + (buf ^ 1) * STAGE, t + 1 < nt, (t + 1) * KVB, t * KVB, R, row_src, col_src, wave, G, pa, pb, myL, myD,
-                   L2h, Dh, S, scale_log2, oacc0, oacc1, m_run, l_run);
+    stats_tile(smem + buf * TILE, smem + (buf ^ 1) * TILE, t + 1 < nt, (t + 1) * KVB, t * KVB, rk, row_src, wave, G, pq, S, scale_log2, m_run, l_run);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
-  if (MODE == 2) {
-    l_run = xhalf_sum(l_run);
-    // (both half-waves hold the same row: identical values, either writes)
-    if (G.hi == 0) L2[bh * Spad + r0] = r0 < S ? m_run + __log2f(l_run) : BIG;
-    return;
-  }
-  const bool live = r0 < S;
-  if (MODE == 0) {
-    store_rows(OUT0 + hoff + (long long)r0 * 128, oacc0, scale, G.hi, live);
-  } else {
-    store_rows(OUT0 + hoff + (long long)r0 * 128, oacc0, 1.f, G.hi, live);
-    store_rows(OUT1 + hoff + (long long)r0 * 128, oacc1, scale, G.hi, live);
-  }
+  l_run = xhalf_sum(l_run);
+  // (both half-waves hold the same row: identical values, either writes)
+  if (G.hi == 0) L2[bh * Spad + r0] = r0 < S ? m_run + __log2f(l_run) : BIG;
 }
-
-#ifdef X2I_ABLATION   // (measurement library only since the pipelined passes: the A/B reference of attn_bwd_dq_kernel)
-// dQ with 64 persistent query rows per wave (two 32-row blocks qb): every streamed fragment feeds TWO MFMAs, so the LDS traffic per
-// MFMA is half that of attn_bwd_kernel<0> (whose one-fragment-per-MFMA stream sits at the LDS roof with the matrix pipe half idle).
-// 256 query rows per workgroup; same tiles, fragments, arithmetic and rounding per row as the 32-row form (bit-identical results).
-__device__ __forceinline__ void dq64_tile(const char* __restrict__ cur, char* __restrict__ nxt, bool issue, int s_next, int s0, const Rsrc4& R,
-                                          const int (&row_src)[4], const int (&col_src)[4], int wave, const Geo& G, const bf16x8_t (&pa)[2][8],
-                                          const bf16x8_t (&pb)[2][8], const float (&myL)[2], const float (&myD)[2], int S, float scale_log2,
-                                          f32x16_t (&oacc)[2][4]) {
-  if (issue) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      char* dst = nxt + (j * 256 + wave * 64) * 16;
-      dma16(R.a, (uint32_t)(s_next * 256 + row_src[j] * 2), dst);
-      dma16(R.b, (uint32_t)(s_next * 256 + row_src[j] * 2), dst + TILE);
-      dma16(R.c, (uint32_t)(s_next * 2 + col_src[j] * 2), dst + 2 * TILE);
-    }
-  }
-  f32x16_t sacc[2][2], dacc[2][2];   // [qb][sub-tile u]
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { sacc[qb][u][r] = 0.f; dacc[qb][u][r] = 0.f; }
-  {  // scores S^T = K Q^T and dP^T = V dO^T as one fragment pipeline (steps 0-3: K tile, 4-7: V tile)
-    bf16x8_t fr[2][4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) fr[0][f] = row_frag(cur, G, 0, f);
-#pragma unroll
-    for (int st = 0; st < 8; ++st) {
-      if (st + 1 < 8) {
-#pragma unroll
-        for (int f = 0; f < 4; ++f) fr[(st + 1) & 1][f] = row_frag(st + 1 < 4 ? cur : cur + TILE, G, (st + 1) & 3, f);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      const int g = st & 3;
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb) {
-          if (st < 4) sacc[qb][f & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[st & 1][f], pa[qb][2 * g + (f >> 1)], sacc[qb][f & 1], 0, 0, 0);
-          else dacc[qb][f & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[st & 1][f], pb[qb][2 * g + (f >> 1)], dacc[qb][f & 1], 0, 0, 0);
-        }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  bf16x8_t fr[2][4];   // first fragments of the accumulation pipeline: in flight while the element-wise section runs
-#pragma unroll
-  for (int db = 0; db < 4; ++db) fr[0][db] = col_frag(cur + 2 * TILE, G, 0, db);
-  bf16x8_t dsf[2][2][2];
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = s0 + u * 32 + 16 * (r >> 3) + 8 * G.hi + (r & 7);
-        const float p = key < S ? __builtin_amdgcn_exp2f(sacc[qb][u][r] * scale_log2 - myL[qb]) : 0.f;
-        dacc[qb][u][r] = p * (dacc[qb][u][r] - myD[qb]);
-      }
-    pack_frags(dacc[qb], dsf[qb]);
-  }
-#pragma unroll
-  for (int st = 0; st < 4; ++st) {   // dQ^T += K^T dS^T
-    if (st + 1 < 4) {
-#pragma unroll
-      for (int db = 0; db < 4; ++db) fr[(st + 1) & 1][db] = col_frag(cur + 2 * TILE, G, st + 1, db);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-      for (int qb = 0; qb < 2; ++qb)
-        oacc[qb][db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[st & 1][db], dsf[qb][st >> 1][st & 1], oacc[qb][db], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-__global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ dO, const bf16_t* __restrict__ K,
-                                                              const bf16_t* __restrict__ V, const bf16_t* __restrict__ KT, const float* __restrict__ L2,
-                                                              const float* __restrict__ Dv, bf16_t* __restrict__ dQ, int H, int S, int Spad,
-                                                              float scale, float scale_log2, int nbatch) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int STAGE = 3 * TILE;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  Geo G;
-  G.hi = lane >> 5; G.li = lane & 31;
-  {
-    const int kvm = (G.li & 0x13) | ((G.li & 4) << 1) | ((G.li & 8) >> 1);
-    G.k_row_off = kvm * 256; G.k_swz = kvm & 15; G.v_row_off = G.li * 128; G.v_swz = (G.li >> 1) & 7;
-  }
-  const int nblk = (Spad + 255) / 256;
-  int bid = blockIdx.x;
-  {
-    const int T = gridDim.x, q = T >> 3, r = T & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int blk = bid % nblk, h = (bid / nblk) % H, b = bid / (nblk * H);
-  const long long bh = (long long)b * H + h;
-  const long long hoff = bh * Spad * 128;
-  bf16x8_t pa[2][8], pb[2][8];
-  float myL[2], myD[2];
-  int r0[2];
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    r0[qb] = blk * 256 + wave * 64 + qb * 32 + G.li;   // this lane's persistent query rows
-    const int rr = min(r0[qb], Spad - 1);              // (rows behind Spad -- a last, half block -- read a valid row and are never stored)
-#pragma unroll
-    for (int ds = 0; ds < 8; ++ds) {
-      pa[qb][ds] = *(const bf16x8_t*)(Q + hoff + (long long)rr * 128 + ds * 16 + G.hi * 8);
-      pb[qb][ds] = *(const bf16x8_t*)(dO + hoff + (long long)rr * 128 + ds * 16 + G.hi * 8);
-    }
-    myL[qb] = L2[bh * Spad + rr];
-    myD[qb] = Dv[bh * Spad + rr];
-  }
-  int row_src[4], col_src[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int p = j * 256 + tid;
-    { const int row = p >> 4, c = p & 15; row_src[j] = row * 128 + ((c ^ (row & 15)) << 3); }
-    { const int row = p >> 3, c = p & 7; col_src[j] = row * Spad + ((c ^ ((row >> 1) & 7)) << 3); }
-  }
-  Rsrc4 R;
-  {
-    const uint32_t bytes = (uint32_t)Spad * 256u;
-    R.a = __builtin_amdgcn_make_buffer_rsrc((void*)(K + hoff), 0, bytes, 0x00020000);
-    R.b = __builtin_amdgcn_make_buffer_rsrc((void*)(V + hoff), 0, bytes, 0x00020000);
-    R.c = __builtin_amdgcn_make_buffer_rsrc((void*)(KT + hoff), 0, bytes, 0x00020000);
-    R.d = R.c;
-  }
-  f32x16_t oacc[2][4];
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) oacc[qb][i][r] = 0.f;
-  const int nt = (S + KVB - 1) / KVB;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    char* dst = smem + (j * 256 + wave * 64) * 16;
-    dma16(R.a, (uint32_t)(row_src[j] * 2), dst);
-    dma16(R.b, (uint32_t)(row_src[j] * 2), dst + TILE);
-    dma16(R.c, (uint32_t)(col_src[j] * 2), dst + 2 * TILE);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int t = 0; t < nt; ++t) {
-    const int buf = t & 1;
-    dq64_tile(smem + buf * STAGE, smem + (buf ^ 1) * STAGE, t + 1 < nt, (t + 1) * KVB, t * KVB, R, row_src, col_src, wave, G, pa, pb, myL, myD, S,
-              scale_log2, oacc);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) store_rows(dQ + hoff + (long long)r0[qb] * 128, oacc[qb], scale, G.hi, r0[qb] < S);
-}
-
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
-// dK / dV pass, SOFTWARE-PIPELINED over the two 32-row halves u of a streamed tile (round 6).  attn_bwd_kernel<1> runs a tile as
+// dK / dV pass, SOFTWARE-PIPELINED over the two 32-row halves u of a streamed tile (round 6).  The phase-after-phase form it replaced ran a tile as
 // [S, dP: 32 MFMAs] [element-wise section: ~330 VALU instructions with the matrix pipe idle] [dV, dK: 32 MFMAs]; with one wave per SIMD nothing
 // else fills the middle, the per-row statistics come as 16 global loads per tile that sit BEHIND the next tile's DMA in the vmcnt queue (so
 // their wait is a wait for the whole DMA), and the 16 DMA pieces issue in one burst.  Here a tile is 64 slots, one MFMA each, in four phases
@@ -529,7 +184,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(const bf16_t* __r
 //     D: dV(u1), dK(u1)
 // with every slot closed by a scheduling fence, so the order written here is the order issued: the fragment of slot m + LEAD is requested in
 // slot m (a ring of eight), L2 / D rows of the tile come through LDS with the tile (one 256-byte DMA piece each, read back as broadcasts).
-// Same MFMA order per accumulator and the same element-wise operations as attn_bwd_kernel<1>: bit-identical results (tested).
+// Same MFMA order per accumulator and the same element-wise operations as that form: bit-identical results (tested when it was replaced).
 template <int N, class F>
 __device__ __forceinline__ void sfor(F&& f) {
   if constexpr (N > 0) {
@@ -772,7 +427,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_kernel(const bf16_t* __r
 //     B (32..63): S(u1), dP(u1)                     + the 32 element-wise values of half u0 (slots 34..65)
 //     C (64..95): dQ^T += K^T dS^T, groups (u0,kt0) (u0,kt1) (u1,kt0) (u1,kt1)   + the values of half u1: rows r < 8 of both blocks by slot 79,
 //                                                     rows r >= 8 by slot 87 (two values per slot there: the groups that need them follow)
-// Same MFMA order per accumulator and element-wise operations as attn_bwd_dq64_kernel: bit-identical (tested).  MASKED: the last tile of a
+// Same MFMA order per accumulator and element-wise operations as the phase-after-phase 64-row form it replaced.  MASKED: the last tile of a
 // sequence with S % 64 != 0 (keys at or behind S get p = 0); every other tile runs without the compare / select per value.
 constexpr int DQ_LEAD = 3;   // fragments (= pairs of slots) a read runs ahead of its MFMAs
 struct DqState {
@@ -993,22 +648,13 @@ int x2i_launch_attention_bwd(const void* Q, const void* K, const void* V, const 
   const float scale_log2 = scale * 1.4426950408889634f;
   dim3 grid((Spad / 128) * H * B);
   if (!have_lse) {  // statistics pass; skipped when the forward already wrote them (x2i_attention_lse_bf16)
-    const int shm = 2 * 1 * TILE;
-    hipLaunchKernelGGL((attn_bwd_kernel<2>), grid, dim3(256), shm, stream, (const bf16_t*)Q, (const bf16_t*)nullptr, (const bf16_t*)K,
-                       (const bf16_t*)nullptr, (const bf16_t*)nullptr, (const bf16_t*)nullptr, L2, Dv, (bf16_t*)nullptr, (bf16_t*)nullptr, H, S,
-                       Spad, scale, scale_log2, B);
+    hipLaunchKernelGGL(attn_bwd_stats_kernel, grid, dim3(256), 2 * TILE, stream, (const bf16_t*)Q, (const bf16_t*)K, L2, H, S, Spad, scale_log2);
   }
   // The dQ pass and the dK / dV pass are independent (both read Q, K, V, dO and the statistics; they write different tensors) and each
-  // ends in a partly filled round of one-workgroup-per-CU blocks (B = 1: 1.7 and 3.4 rounds).  Product: the software-pipelined kernels, as ONE launch
-  // (attn_bwd_fused_kernel: dQ blocks in front, dK / dV blocks behind them -- a CU takes the next block as soon as one ends, whichever pass it belongs
-  // to) or, option attn_bwd_overlap = 0, one after the other.  The round-2 kernels (phase after phase; 32-row dQ form) and the two-stream form are
-  // compiled into the measurement library only (options attn_bwd_pipe / attn_bwd_dq64 there; bit-identical, tests behind the `ablation` marker).
-#ifdef X2I_ABLATION
-  const bool pipe = x2i_options().attn_bwd_pipe != 0, dq64 = x2i_options().attn_bwd_dq64 != 0;
-#else
-  const bool pipe = true, dq64 = true;
-#endif
-  if (pipe && dq64 && x2i_options().attn_bwd_overlap) {
+  // ends in a partly filled round of one-workgroup-per-CU blocks (B = 1: 1.7 and 3.4 rounds): ONE launch (attn_bwd_fused_kernel: dQ blocks
+  // in front, dK / dV blocks behind them -- a CU takes the next block as soon as one ends, whichever pass it belongs to) or, option
+  // attn_bwd_overlap = 0, one after the other (bit-identical).
+  if (x2i_options().attn_bwd_overlap) {
     const int shm = 2 * KV_STAGE;
     const int rc = x2i_ensure_dynamic_smem((const void*)attn_bwd_fused_kernel, shm);
     if (rc) return rc;
@@ -1018,54 +664,20 @@ int x2i_launch_attention_bwd(const void* Q, const void* K, const void* V, const 
                        scale_log2, n_dq);
     return x2i_check_launch("attention_bwd (fused passes)");
   }
-  hipStream_t qs = stream;
-#ifdef X2I_ABLATION
-  hipStream_t side = stream;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  const bool overlap = x2i_options().attn_bwd_overlap && x2i_side_stream(stream, &side, &ev_fork, &ev_join) &&
-                       hipEventRecord(ev_fork, stream) == hipSuccess && hipStreamWaitEvent(side, ev_fork, 0) == hipSuccess;
-  qs = overlap ? side : stream;
-#endif
-  if (dq64 && pipe) {   // dQ: 64 query rows per wave, software-pipelined (attn_bwd_dq_kernel)
+  {   // dQ: 64 query rows per wave, software-pipelined (attn_bwd_dq_kernel)
     const int shm = 2 * 3 * TILE;
     const int rc = x2i_ensure_dynamic_smem((const void*)attn_bwd_dq_kernel, shm);
     if (rc) return rc;
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(((Spad + 255) / 256) * H * B), dim3(256), shm, qs, (const bf16_t*)Q, (const bf16_t*)dOh,
+    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(((Spad + 255) / 256) * H * B), dim3(256), shm, stream, (const bf16_t*)Q, (const bf16_t*)dOh,
                        (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)KT, (const float*)L2, Dv, (bf16_t*)dQ, H, S, Spad, scale, scale_log2, B);
   }
-#ifdef X2I_ABLATION
-  else if (dq64) {  // phase after phase (attn_bwd_dq64_kernel); option attn_bwd_dq64 = 0: the 32-row form (A/B, bit-identical)
-    const int shm = 2 * 3 * TILE;
-    const int rc = x2i_ensure_dynamic_smem((const void*)attn_bwd_dq64_kernel, shm);
-    if (rc) return rc;
-    hipLaunchKernelGGL(attn_bwd_dq64_kernel, dim3(((Spad + 255) / 256) * H * B), dim3(256), shm, qs, (const bf16_t*)Q, (const bf16_t*)dOh,
-                       (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)KT, L2, Dv, (bf16_t*)dQ, H, S, Spad, scale, scale_log2, B);
-  } else {
-    const int shm = 2 * 3 * TILE;
-    const int rc = x2i_ensure_dynamic_smem((const void*)attn_bwd_kernel<0>, shm);
-    if (rc) return rc;
-    hipLaunchKernelGGL((attn_bwd_kernel<0>), grid, dim3(256), shm, qs, (const bf16_t*)Q, (const bf16_t*)dOh, (const bf16_t*)K, (const bf16_t*)V,
-                       (const bf16_t*)KT, (const bf16_t*)nullptr, L2, Dv, (bf16_t*)dQ, (bf16_t*)nullptr, H, S, Spad, scale, scale_log2, B);
-  }
-  if (overlap) (void)hipEventRecord(ev_join, side);
-#endif
-  if (pipe) {   // dK / dV: software-pipelined (attn_bwd_dkdv_kernel)
+  {   // dK / dV: software-pipelined (attn_bwd_dkdv_kernel)
     const int shm = 2 * KV_STAGE;
     const int rc = x2i_ensure_dynamic_smem((const void*)attn_bwd_dkdv_kernel, shm);
     if (rc) return rc;
     hipLaunchKernelGGL(attn_bwd_dkdv_kernel, grid, dim3(256), shm, stream, (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)Q, (const bf16_t*)dOh,
                        (const bf16_t*)dOT, (const bf16_t*)QT, (const float*)L2, Dv, (bf16_t*)dV, (bf16_t*)dK, H, S, Spad, scale, scale_log2, B);
   }
-#ifdef X2I_ABLATION
-  else {
-    const int shm = 2 * 4 * TILE;
-    const int rc = x2i_ensure_dynamic_smem((const void*)attn_bwd_kernel<1>, shm);
-    if (rc) return rc;
-    hipLaunchKernelGGL((attn_bwd_kernel<1>), grid, dim3(256), shm, stream, (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)Q, (const bf16_t*)dOh,
-                       (const bf16_t*)dOT, (const bf16_t*)QT, L2, Dv, (bf16_t*)dV, (bf16_t*)dK, H, S, Spad, scale, scale_log2, B);
-  }
-  if (overlap) (void)hipStreamWaitEvent(stream, ev_join, 0);
-#endif
   return x2i_check_launch("attention_bwd");
 }
 

@@ -142,8 +142,9 @@ __device__ __forceinline__ void matrix_phase(const char* __restrict__ kb, const 
 }
 
 // SCH = 0: every wave starts its share of K(t+1) / V(t) at the head of its MATRIX phase M(t) (two K and two V^T buffers).
-// SCH = 1: the DMA issue rides in the VECTOR phase instead -- S(t) starts K(t+2) / V(t+1) into three-deep rings (96 KiB) -- so that
-//          the matrix phase, the longer of the two, carries nothing but fragment reads and MFMAs.
+// SCH = 2: the DMA issue rides at the end of the VECTOR phase instead -- S(t) starts K(t+3) / V(t+2) into four-deep rings (128 KiB) and
+//          reads the first fragments of M(t+1) -- so that the matrix phase, the longer of the two, carries nothing but fragment reads
+//          and MFMAs and starts with its operands in registers (stage_and_prefetch).
 template <int THR, bool OUT8, int SCH>
 __global__ __launch_bounds__(NTH, 2) void attn_pp_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                       const bf16_t* __restrict__ VT, bf16_t* __restrict__ O, int H, int S, int Spad,
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(NTH, 2) void attn_pp_kernel(const bf16_t* __restric
   bf16x8_t pf[2][2] = {};
   float m_run = NEG_BIG, l_run = 0.f;
   const int nt = (S + KVB - 1) / KVB;
-  constexpr int NB = SCH == 2 ? 4 : SCH == 1 ? 3 : 2;
+  constexpr int NB = SCH == 2 ? 4 : 2;
   bf16x8_t fr[3][4];  // fragment ring of the matrix phase (SCH 2: steps 0-1 of the next phase are read at the end of the vector phase)
   char* const kbuf = smem;
   char* const vbuf = smem + NB * KTILE;
@@ -277,36 +278,14 @@ __global__ __launch_bounds__(NTH, 2) void attn_pp_kernel(const bf16_t* __restric
           kbuf + (t & 1) * KTILE, vbuf + ((t + 1) & 1) * VTILE, kbuf + ((t + 1) & 1) * KTILE, vbuf + (t & 1) * VTILE,
           k_rsrc, v_rsrc, (uint32_t)(t + 1) * (KVB * 128 * 2), (uint32_t)t * (KVB * 2), t + 1 < nt, t < nt, k_src, v_src, wave, L, qf, pf,
           sacc, oacc, fr);
-    } else if constexpr (SCH == 1) {
-      matrix_phase<decltype(has_pv)::value, decltype(has_qk)::value>(
-          kbuf + (t % 3) * KTILE, vbuf + ((t + 2) % 3) * VTILE, nullptr, nullptr, k_rsrc, v_rsrc, 0u, 0u, false, false, k_src, v_src, wave, L,
-          qf, pf, sacc, oacc, fr);
     } else {
       matrix_phase<decltype(has_pv)::value, decltype(has_qk)::value, decltype(has_pv)::value>(
           kbuf + (t & 3) * KTILE, vbuf + ((t + 3) & 3) * VTILE, nullptr, nullptr, k_rsrc, v_rsrc, 0u, 0u, false, false, k_src, v_src, wave, L,
           qf, pf, sacc, oacc, fr);
     }
   };
-  // SCH 1: the vector phase S(t) starts this wave's share of K(t+2) and V(t+1); returns how many DMA pieces it issued
-  auto stage_ahead = [&](int t) {
-    int n = 0;
-    if constexpr (SCH == 1) {
-      if (t + 2 < nt) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          dma16(k_rsrc, (uint32_t)(t + 2) * (KVB * 128 * 2) + (uint32_t)k_src[j] * 2, kbuf + ((t + 2) % 3) * KTILE + (j * NTH + wave * 64) * 16);
-        n += 2;
-      }
-      if (t + 1 < nt) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          dma16(v_rsrc, (uint32_t)(t + 1) * (KVB * 2) + (uint32_t)v_src[j] * 2, vbuf + ((t + 1) % 3) * VTILE + (j * NTH + wave * 64) * 16);
-        n += 2;
-      }
-    }
-    return n;
-  };
-  // SCH 2: end of S(t) -- K(t+3) / V(t+2) into the four-deep rings and the first fragments of M(t+1) (V^T(t)) into `fr`
+  // SCH 2: end of S(t) -- K(t+3) / V(t+2) into the four-deep rings and the first fragments of M(t+1) (V^T(t)) into `fr`; returns how
+  // many DMA pieces it issued
   auto stage_tail = [&](int t) {
     int n = 0;
     if constexpr (SCH == 2) {
@@ -333,7 +312,7 @@ __global__ __launch_bounds__(NTH, 2) void attn_pp_kernel(const bf16_t* __restric
   // prologue: K(0) visible to everyone; group B then falls one phase behind group A
 #pragma unroll
   for (int j = 0; j < 2; ++j) dma16(k_rsrc, (uint32_t)k_src[j] * 2, kbuf + (j * NTH + wave * 64) * 16);
-  if constexpr (SCH >= 1) {  // K(1) and V(0) as well (SCH 2: also K(2), V(1)): the rings run ahead of the matrix phases
+  if constexpr (SCH == 2) {  // K(1), K(2), V(0) and V(1) as well: the rings run ahead of the matrix phases
 #pragma unroll
     for (int a = 1; a <= SCH; ++a)
       if (a < nt) {
@@ -360,25 +339,22 @@ __global__ __launch_bounds__(NTH, 2) void attn_pp_kernel(const bf16_t* __restric
   int keep;
   M(0, std::false_type{}, std::true_type{});
   barrier(grp == 1);
-  keep = stage_ahead(0);
   if (nt == 1) softmax(0, std::true_type{});
   else softmax(0, std::false_type{});
-  keep += stage_tail(0);
+  keep = stage_tail(0);
   barrier_keep(grp == 0, keep);
   for (int t = 1; t < nt - 1; ++t) {  // steady state: every key valid, every piece present
     M(t, std::true_type{}, std::true_type{});
     barrier(grp == 1);
-    keep = stage_ahead(t);
     softmax(t, std::false_type{});
-    keep += stage_tail(t);
+    keep = stage_tail(t);
     barrier_keep(grp == 0, keep);
   }
   if (nt > 1) {
     M(nt - 1, std::true_type{}, std::true_type{});
     barrier(grp == 1);
-    keep = stage_ahead(nt - 1);
     softmax(nt - 1, std::true_type{});
-    keep += stage_tail(nt - 1);
+    keep = stage_tail(nt - 1);
     barrier_keep(grp == 0, keep);
   }
   M(nt, std::true_type{}, std::false_type{});  // PV(nt-1); nothing left to stage
@@ -426,50 +402,15 @@ __global__ __launch_bounds__(NTH, 2) void attn_pp_kernel(const bf16_t* __restric
 }  // namespace
 
 // Launcher of the ping-pong form; returns X2I_ERR_STATE when the shape is not served (the caller then uses attn_fwd_kernel).
+// Schedule 2 (four-deep rings, fragment prefetch in the vector phase; +2 % measured) for bf16 outputs, schedule 0 for e4m3 outputs.
 int x2i_launch_attention_pp(const void* Q, const void* K, const void* VT, void* O, int B, int H, int S, int Spad, int ldo,
-                            long long o_bs, float scale_log2, hipStream_t stream, int out8, float oinv, int thr, float* lse) {
+                            long long o_bs, float scale_log2, hipStream_t stream, int out8, float oinv, float* lse) {
   if (!out8 && ((((uintptr_t)O) & 15) || (ldo & 7) || (o_bs & 7))) return X2I_ERR_STATE;  // 16-byte row stores only
-  const int var = x2i_options().attn_variant;
-  // schedule: 2 (four-deep rings, fragment prefetch in the vector phase; +2 % measured) for the bf16 / defer-max launches unless an
-  // A/B variant asks otherwise (5 = schedule 0, 7 = schedule 1); the e4m3-output and THR = 0 instantiations stay on schedule 0
-#ifdef X2I_ABLATION
-  const int sch = var == 7 ? 1 : (var == 8 || (var != 5 && var != 6 && !out8 && thr != 0)) ? 2 : 0;
-#else   // product: schedule 2 for bf16 outputs, schedule 0 for the e4m3-output instantiation (the A/B schedules live in the measurement library)
-  (void)var;
-  const int sch = out8 ? 0 : 2;
-#endif
-  const size_t shm = (sch == 2 ? 4 : sch ? 3 : 2) * (KTILE + VTILE);
-  dim3 grid(((S + 255) / 256) * H * B);
-#ifdef X2I_ABLATION
-  if (sch == 1 && !out8) {
-    const int rc_ = x2i_ensure_dynamic_smem((const void*)attn_pp_kernel<8, false, 1>, (int)shm);
-    if (rc_) return rc_;
-    hipLaunchKernelGGL((attn_pp_kernel<8, false, 1>), grid, dim3(NTH), shm, stream, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)VT,
-                       (bf16_t*)O, H, S, Spad, ldo, o_bs, scale_log2, B, oinv, lse);
-    return x2i_check_launch("attention");
-  }
-#endif
-  if (sch == 2 && !out8) {
-    const int rc_ = x2i_ensure_dynamic_smem((const void*)attn_pp_kernel<8, false, 2>, (int)shm);
-    if (rc_) return rc_;
-    hipLaunchKernelGGL((attn_pp_kernel<8, false, 2>), grid, dim3(NTH), shm, stream, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)VT,
-                       (bf16_t*)O, H, S, Spad, ldo, o_bs, scale_log2, B, oinv, lse);
-    return x2i_check_launch("attention");
-  }
-#define X2I_PP(THR_, O8_)                                                                                                   \
-  {                                                                                                                         \
-    const int rc_ = x2i_ensure_dynamic_smem((const void*)attn_pp_kernel<THR_, O8_, 0>, (int)shm);                           \
-    if (rc_) return rc_;                                                                                                    \
-    hipLaunchKernelGGL((attn_pp_kernel<THR_, O8_, 0>), grid, dim3(NTH), shm, stream, (const bf16_t*)Q, (const bf16_t*)K,    \
-                       (const bf16_t*)VT, (bf16_t*)O, H, S, Spad, ldo, o_bs, scale_log2, B, oinv, lse);                          \
-  }
-  if (out8) X2I_PP(8, true)
-#ifdef X2I_ABLATION
-  else if (thr == 0) X2I_PP(0, false)
-  else X2I_PP(8, false)
-#else
-  else return X2I_ERR_STATE;   // (not reachable: bf16 outputs took schedule 2 above)
-#endif
-#undef X2I_PP
+  const auto kern = out8 ? attn_pp_kernel<8, true, 0> : attn_pp_kernel<8, false, 2>;
+  const size_t shm = (out8 ? 2 : 4) * (KTILE + VTILE);
+  const int rc = x2i_ensure_dynamic_smem((const void*)kern, (int)shm);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3(((S + 255) / 256) * H * B), dim3(NTH), shm, stream, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)VT,
+                     (bf16_t*)O, H, S, Spad, ldo, o_bs, scale_log2, B, oinv, lse);
   return x2i_check_launch("attention");
 }

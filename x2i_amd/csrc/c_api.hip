@@ -46,13 +46,10 @@ X2IOptions make_options() {
   o.gemm_fp8_persist = env_int("X2I_GEMM_FP8_PERSIST", 1);
   o.gemm_fx = env_int("X2I_GEMM_FX", 2);
   o.gemm_fx_nk = env_int("X2I_GEMM_FX_NK", 96);
-  o.gemm_r2 = env_int("X2I_GEMM_R2", 0);
   o.gemm_streamk = env_int("X2I_GEMM_STREAMK", 1);
   o.gemm_pair = env_int("X2I_GEMM_PAIR", 1);
   o.train_rows_wg = env_int("X2I_TRAIN_ROWS_WG", 1);
   o.attn_bwd_overlap = env_int("X2I_ATTN_BWD_OVERLAP", 1);
-  o.attn_bwd_dq64 = env_int("X2I_ATTN_BWD_DQ64", 1);
-  o.attn_bwd_pipe = env_int("X2I_ATTN_BWD_PIPE", 1);
   o.conv256 = env_int("X2I_CONV256", 1);
   o.conv_w4 = env_int("X2I_CONV_W4", 1);
   o.conv_korder = env_int("X2I_CONV_KORDER", 1);
@@ -62,8 +59,6 @@ X2IOptions make_options() {
   o.conv5_variant = env_int("X2I_CONV5_VARIANT", 0);
   o.fp8 = env_int("X2I_FP8", 0);
   o.last_gemm_tile = -1;
-  o.gemm_lform = env_int("X2I_GEMM_LFORM", 1);
-  o.gemm_ablate = env_int("X2I_GEMM_ABLATE", 0);
   o.attn_ablate = env_int("X2I_ATTN_ABLATE", 0);
   return o;
 }
@@ -116,39 +111,6 @@ bool x2i_streamk_workspace(const x2i_gemm_args* a, float** slabs, unsigned** fla
   return true;
 }
 
-// A second stream per device for launches that are independent of each other (the dQ and the dK / dV pass of the attention backward):
-// fork / join by events, which is also the form a stream capture accepts.  Created on first use outside a capture; returns false when
-// it is not available (the caller then issues its launches one after the other on its own stream).
-namespace {
-struct SideStream {
-  hipStream_t s = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-  bool failed = false;
-};
-SideStream g_side[64];
-std::mutex g_side_mu;
-}  // namespace
-
-bool x2i_side_stream(hipStream_t main, hipStream_t* side, hipEvent_t* fork, hipEvent_t* join) {
-  int dev = 0;
-  hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64) return false;
-  std::lock_guard<std::mutex> lk(g_side_mu);
-  SideStream& w = g_side[dev];
-  if (!w.s) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(main, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone || w.failed) { (void)hipGetLastError(); return false; }
-    if (hipStreamCreateWithFlags(&w.s, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&w.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&w.join, hipEventDisableTiming) != hipSuccess) {
-      (void)hipGetLastError();
-      w.s = nullptr; w.failed = true;
-      return false;
-    }
-  }
-  *side = w.s; *fork = w.fork; *join = w.join;
-  return true;
-}
-
 extern "C" {
 
 int x2i_abi_version(void) { return X2I_ABI_VERSION; }
@@ -158,7 +120,7 @@ static long long* opt_slot(X2IOptions& o, const char* name, int** as_int) {
 #define X2I_OPT_INT(N_) if (!strcmp(name, #N_)) { *as_int = &o.N_; return nullptr; }
   X2I_OPT_INT(gemm_tile) X2I_OPT_INT(gemm_gm) X2I_OPT_INT(gemm_split_tail) X2I_OPT_INT(gemm_w4) X2I_OPT_INT(gemm_persist) X2I_OPT_INT(gemm_fp8_persist) X2I_OPT_INT(gemm_fx) X2I_OPT_INT(gemm_fx_nk) X2I_OPT_INT(gemm_streamk) X2I_OPT_INT(gemm_pair) X2I_OPT_INT(train_rows_wg) X2I_OPT_INT(attn_bwd_overlap) X2I_OPT_INT(attn_streamk) X2I_OPT_INT(conv256) X2I_OPT_INT(conv_w4) X2I_OPT_INT(conv_korder) X2I_OPT_INT(attn_variant) X2I_OPT_INT(attn_w16) X2I_OPT_INT(conv5_variant) X2I_OPT_INT(fp8) X2I_OPT_INT(last_gemm_tile)
 #ifdef X2I_ABLATION
-  X2I_OPT_INT(gemm_lform) X2I_OPT_INT(gemm_ablate) X2I_OPT_INT(attn_ablate) X2I_OPT_INT(gemm_r2) X2I_OPT_INT(attn_bwd_dq64) X2I_OPT_INT(attn_bwd_pipe)
+  X2I_OPT_INT(attn_ablate)
 #endif
 #undef X2I_OPT_INT
   if (!strcmp(name, "gemm_min256")) return &o.gemm_min256;

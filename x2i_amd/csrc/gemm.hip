@@ -395,13 +395,6 @@ static int launch_gemm_impl(const x2i_gemm_args* a, const x2i_conv_desc* cd, con
   if (!conv && opt.gemm_w4) {  // plain GEMMs: the 4-wave kernel with the hand-scheduled K-loop (bit-identical results)
     if (kern_t kw = pick_gemm256w(p.act, res, f32, c2)) kern2 = kw, threads2 = 256;
   }
-#ifdef X2I_ABLATION
-  if (!conv && opt.gemm_w4 > 1 && p.act == X2I_ACT_NONE && !res && !f32 && !c2) {  // A/B schedules of the 4-wave K-loop
-    if (kern_t kv = pick_gemm256w_var(opt.gemm_w4 - 1)) kern2 = kv, threads2 = 256;
-  }
-  // measurement-only library: the k-half-unit form (gemm_lform = 0) and its ablation variants replace the product kernel
-  if (!conv && (opt.gemm_ablate || !opt.gemm_lform)) kern2 = pick_gemm256u(p.act, res, f32, c2, opt.gemm_ablate), threads2 = 512;
-#endif
   const int force = opt.gemm_tile;  // 0 = automatic, 128 / 256 = A/B override
   const long long tiles256 = (long long)((a->M + BM2 - 1) / BM2) * ((a->N + BN2 - 1) / BN2) * a->batch;
   // Tile choice (re-measured with the full-line staging kernel, B = 1, 2, 4): the 256^2 kernel wins from about half a round
@@ -490,23 +483,6 @@ static int launch_gemm_impl(const x2i_gemm_args* a, const x2i_conv_desc* cd, con
     }
     if (frc) return frc;
   }
-#ifdef X2I_ABLATION   // (measurement library only since round 6: measured 1.57-1.62x slower than the persistent kernel)
-  // A/B (option gemm_r2): the "two residents" form -- 256 x 128 tiles, two workgroups per CU, epilogues hidden behind the other
-  // workgroup's K-loop; whole K-tiles in groups of four
-  if (opt.gemm_r2 && !conv && !qd && fast && !f32 && a->K % (4 * BK) == 0 && a->M >= 256 && a->N >= 128 && !a->w_batch_stride) {
-    const int var = opt.gemm_ablate;
-    if (kern_t kr = pick_gemm_r2(p.act, res, f32, c2, var)) {
-      const int rc = x2i_ensure_dynamic_smem((const void*)kr, SMEM_R2_BYTES);
-      if (rc) return rc;
-      GemmP pm = p;
-      pm.tilesM = (a->M + 255) / 256; pm.tilesN = (a->N + 127) / 128;
-      pm.gm = opt.gemm_gm > 0 ? opt.gemm_gm : 4;
-      hipLaunchKernelGGL(kr, dim3(pm.tilesM * pm.tilesN, a->batch), dim3(256), SMEM_R2_BYTES, stream, pm);
-      opt.last_gemm_tile = 4256;
-      return x2i_check_launch("gemm (r2)");
-    }
-  }
-#endif
   if (force == 128) use256 = false;
   if (force == 256 && !conv) use256 = true;
   if (conv && !conv256) use256 = false;

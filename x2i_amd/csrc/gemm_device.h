@@ -1,4 +1,4 @@
-// Device-side building blocks shared by the bf16 MFMA GEMM kernels (gemm128.hip, gemm256.hip, gemm_ablate.hip): the kernel
+// Device-side building blocks shared by the bf16 MFMA GEMM kernels (gemm128.hip, gemm256.hip, gemm256w.hip, ...): the kernel
 // parameter block, LDS-DMA staging helpers and the fused epilogues.  See gemm.hip for the launcher and the operator contract.
 #pragma once
 #include "x2i_common.h"
@@ -574,14 +574,8 @@ kern2_t pick_gemm256p_pair(int act, bool res, bool qkv, bool c2 = false);
 kern_t pick_gemm256p_fx();        // gated-residual epilogue, parallel split with fix-up (launches that cannot fill the chip with whole tiles)
 kern2_t pick_gemm256p_pair_fx();  // ... grouped form     // ... over the tiles of two problems (x2i_gemm_pair_bf16 / x2i_gemm_qkv_pair_bf16)
 constexpr int SMEM2P_BYTES = 2 * TILE2_BYTES + 4 * 8192;     // 128 KiB operand ring + 4 x 8 KiB staging = all 160 KiB
-kern_t pick_gemm_r2(int act, bool res, bool f32, bool c2, int var);  // (measurement library only)  // 256 x 128 tiles, two resident workgroups per CU (gemm_r2.hip); var: measurement builds
-constexpr int SMEM_R2_BYTES = 4 * 16384;                     // 4-stage W ring (reused as 4 x 9 KiB epilogue staging)
 kern_t pick_gemm256_fp8(int act, bool res, bool out8);
 kern_t pick_gemm256p_fp8(int act, bool res, bool out8, bool qkv);  // ... in the persistent four-wave form (gemm256p.hip, gen_gemm256f8.py)  // e4m3 operands, MX-scaled K = 128 MFMA (gemm256_fp8.hip)
-#ifdef X2I_ABLATION
-kern_t pick_gemm256w_var(int var);  // A/B schedules of the 4-wave K-loop (option gemm_w4 = 1 + var), plain epilogue only
-kern_t pick_gemm256u(int act, bool res, bool f32, bool c2, int abl);  // k-half-unit form + measurement-only variants
-#endif
 
 // One table of the epilogue combinations that have MFMA instantiations (anything else takes the generic kernel).
 #define X2I_GEMM_PICK_TABLE(PICK)                                                   \

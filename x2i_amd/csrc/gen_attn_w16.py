@@ -13,7 +13,7 @@ shape: the matrix pipe alone sustains 11-14 % more FLOP/s at this part's power c
     ("V", sp, db): O[db][qb] += V^T(db, sp) P[sp][qb], eight d-blocks of 16, two key spans of 32 -- 128 MFMAs of 16 cycles per tile;
   * P^T[sp][qb] = bf16 pairs of S[2 sp][qb][0..3], S[2 sp + 1][qb][0..3]: the lane's OWN registers are the eight k-positions 8g .. 8g+7 of the
     PV MFMA's B operand when k-position kk stands for key 16 ((kk >> 2) & 1) + 4 (kk >> 3) + (kk & 3) of the span -- so V^T must arrive with its
-    keys in that order within every 32-key span (the contract attention16.hip's VPERM form proved; the caller permutes for now);
+    keys in that order within every 32-key span (x2i_vt_pos; the caller permutes);
   * a query's keys sit in four lanes (g = 0 .. 3): the tile maximum is combined with v_permlane16_swap + v_permlane32_swap, the row sums stay
     per lane until the epilogue; the -m copies are 4 registers per query block (every register of a lane's accumulator is the same query).
 

@@ -38,8 +38,7 @@ def acc(i, j):
 #   ("VM", what):            s_waitcnt vmcnt(n) so that the NEXT tile's pieces of operand `what` ("W", "A") have landed
 #   ("BAR",):                s_barrier
 #   ("CNT", n):              loop counter (0: decrement, 1: compare)
-def default_slots(variant=0):
-    """variant 0 = the product schedule; 3 = one barrier for both operands of the next tile (measurement builds only)."""
+def default_slots():
     s = {}
 
     def put(k, *ev):
@@ -58,29 +57,17 @@ def default_slots(variant=0):
     put(45, ("LGK", "A1")); put(46, ("BAR",))
     put(47, ("M0W", 5)); put(48, ("DW", 5)); put(50, ("M0W", 6)); put(51, ("DW", 6)); put(53, ("M0W", 7)); put(54, ("DW", 7))
     put(56, ("M0A", 0)); put(57, ("DA", 0)); put(59, ("M0A", 1)); put(60, ("DA", 1))
-    if variant == 3:
-        put(62, ("VM", "A")); put(63, ("BAR",))      # the next tile's A pieces are younger than its W pieces: one wait covers both
-        for j in range(8):
-            put(64 + 2 * j, ("R0W", j))
-        for i in range(8):
-            put(80 + 2 * i, ("R0A", i))
-        k = 96
-        for jj in range(2, 8):
-            put(k, ("M0A", jj)); put(k + 1, ("DA", jj))
-            k += 3
-        put(115, ("XD",))
-    else:
-        put(62, ("VM", "W")); put(63, ("BAR",))
-        for j in range(8):
-            put(64 + 2 * j, ("R0W", j))
-        k = 80
-        for jj in range(2, 7):
-            put(k, ("M0A", jj)); put(k + 1, ("DA", jj))
-            k += 3
-        put(96, ("VM", "A")); put(97, ("BAR",))
-        for i in range(8):
-            put(98 + 2 * i, ("R0A", i))
-        put(114, ("M0A", 7)); put(115, ("DA", 7)); put(116, ("XD",))
+    put(62, ("VM", "W")); put(63, ("BAR",))
+    for j in range(8):
+        put(64 + 2 * j, ("R0W", j))
+    k = 80
+    for jj in range(2, 7):
+        put(k, ("M0A", jj)); put(k + 1, ("DA", jj))
+        k += 3
+    put(96, ("VM", "A")); put(97, ("BAR",))
+    for i in range(8):
+        put(98 + 2 * i, ("R0A", i))
+    put(114, ("M0A", 7)); put(115, ("DA", 7)); put(116, ("XD",))
     put(121, ("CNT", 0)); put(122, ("CNT", 1))
     put(125, ("LGK", "all"))
     return s
@@ -239,13 +226,13 @@ def emit_event(ev, st):
     if kind == "DW":
         st["vm"].append(("W", st["iter"], ev[1]))
         v, r = ("nw", "rw" if conv else "nrw") if mode in ("B1", "B2") else ("vw", "rw")     # (the next unit may belong to another problem of a grouped launch; a convolution launch has one problem)
-        return [f"buffer_load_dwordx4 %[{v}{ev[1]}], %[{r}], %[koff] offen" + st["aux_w"] + " lds"]
+        return [f"buffer_load_dwordx4 %[{v}{ev[1]}], %[{r}], %[koff] offen lds"]
     if kind == "DA":
         st["vm"].append(("A", st["iter"], ev[1]))
         v, r = ("na", "ra" if conv else "nra") if mode in ("B1", "B2") else ("va", "ra")
         if conv:
-            return [f"buffer_load_dwordx4 %[tv{ev[1] & 3}], %[{r}], %[koffa] offen" + st["aux_a"] + " lds"]
-        return [f"buffer_load_dwordx4 %[{v}{ev[1]}], %[{r}], %[koff] offen" + st["aux_a"] + " lds"]
+            return [f"buffer_load_dwordx4 %[tv{ev[1] & 3}], %[{r}], %[koffa] offen lds"]
+        return [f"buffer_load_dwordx4 %[{v}{ev[1]}], %[{r}], %[koff] offen lds"]
     if kind == "XD":
         return ([f"s_xor_b32 %[dma], %[dma], {hex(geom['a_flip'])}"] + ([f"s_xor_b32 %[dmaw], %[dmaw], {hex(geom['w_flip'])}"] if geom["dmaw"] else []) +
                 (["s_add_u32 %[koff], %[koff], 128"] if mode == "A" and not conv else []))
@@ -337,26 +324,26 @@ def check(slots, geom=None):
     del bars
 
 
-def generate(aux_a="", aux_w="", variant=0):
-    slots = default_slots(variant)
+def generate():
+    slots = default_slots()
     check(slots)
-    st = dict(ds=[], vm=[], iter=0, aux_a=aux_a, aux_w=aux_w, vm_n={})
+    st = dict(ds=[], vm=[], iter=0, vm_n={})
     L = []
     L.append("s_nop 4")  # scalar operands may be fresh from v_readfirstlane
     L.append("s_sub_u32 %[nkm1], %[nk], 1")
     L.append("s_mov_b32 %[koff], 0")
     # ---- prologue: tile 0 -> buffer 0 (any order), tile 1 (clamped to the last tile) -> buffer 1 in the loop's order (W, then A)
     for jj in range(8):
-        L += [f"s_add_u32 m0, %[dma], {jj * 4096}", "s_nop 0", f"buffer_load_dwordx4 %[va{jj}], %[ra], %[koff] offen" + aux_a + " lds"]
+        L += [f"s_add_u32 m0, %[dma], {jj * 4096}", "s_nop 0", f"buffer_load_dwordx4 %[va{jj}], %[ra], %[koff] offen lds"]
     for jj in range(8):
-        L += [f"s_add_u32 m0, %[dma], {32768 + jj * 4096}", "s_nop 0", f"buffer_load_dwordx4 %[vw{jj}], %[rw], %[koff] offen" + aux_w + " lds"]
+        L += [f"s_add_u32 m0, %[dma], {32768 + jj * 4096}", "s_nop 0", f"buffer_load_dwordx4 %[vw{jj}], %[rw], %[koff] offen lds"]
     L += ["s_min_u32 %[tl], %[nkm1], 1", "s_lshl_b32 %[koff], %[tl], 7"]
     st["iter"] = -1
     for jj in range(8):
-        L += [f"s_add_u32 m0, %[dma], {65536 + 32768 + jj * 4096}", "s_nop 0", f"buffer_load_dwordx4 %[vw{jj}], %[rw], %[koff] offen" + aux_w + " lds"]
+        L += [f"s_add_u32 m0, %[dma], {65536 + 32768 + jj * 4096}", "s_nop 0", f"buffer_load_dwordx4 %[vw{jj}], %[rw], %[koff] offen lds"]
         st["vm"].append(("W", -1, jj))
     for jj in range(8):
-        L += [f"s_add_u32 m0, %[dma], {65536 + jj * 4096}", "s_nop 0", f"buffer_load_dwordx4 %[va{jj}], %[ra], %[koff] offen" + aux_a + " lds"]
+        L += [f"s_add_u32 m0, %[dma], {65536 + jj * 4096}", "s_nop 0", f"buffer_load_dwordx4 %[va{jj}], %[ra], %[koff] offen lds"]
         st["vm"].append(("A", -1, jj))
     L += ["s_mov_b32 %[tl], 1", "s_mov_b32 %[it], %[nk]"]
     L += ["s_waitcnt vmcnt(16)", "s_barrier"]
@@ -382,7 +369,7 @@ def generate(aux_a="", aux_w="", variant=0):
     return L, st["vm_n"]
 
 
-def generate_persistent(aux_a="", aux_w="", conv=False, geom_name="256"):
+def generate_persistent(conv=False, geom_name="256"):
     """Seamless form for the persistent kernel: PRO (first output tile of a workgroup: K-tiles 0 and 1, first fragments), MAIN (the nk
     K-tiles of one output tile; the last two iterations fetch K-tiles 0 / 1 of the NEXT output tile through the `na` / `nw` offsets and
     leave its first fragments in wa / aa, so the next MAIN starts multiplying at once), DRAIN (after the last tile)."""
@@ -390,19 +377,19 @@ def generate_persistent(aux_a="", aux_w="", conv=False, geom_name="256"):
     npa, npw = geom["npa"], geom["npw"]
     slots = (conv512_slots() if geom_name == "512" else conv_slots()) if conv else default_slots()
     check(slots, geom)
-    st = dict(ds=[], vm=[], iter=-1, aux_a=aux_a, aux_w=aux_w, vm_n={}, mode="A", conv=conv, geom=geom)
+    st = dict(ds=[], vm=[], iter=-1, vm_n={}, mode="A", conv=conv, geom=geom)
     wbase = "%[dmaw]" if geom["dmaw"] else "%[dma]"
 
     def w_piece(jj, buf):
         off = (geom["w_buf1"] if buf else geom["w_buf0"]) + jj * 4096
         return [f"s_add_u32 m0, {wbase}, {off}" if off else f"s_mov_b32 m0, {wbase}", "s_nop 0",
-                f"buffer_load_dwordx4 %[vw{jj}], %[rw], %[koff] offen" + aux_w + " lds"]
+                f"buffer_load_dwordx4 %[vw{jj}], %[rw], %[koff] offen lds"]
 
     def a_piece(jj, buf):   # prologue A piece: plain offset, or the convolution gather's masked offset + scalar tap offset
         m0 = [f"s_add_u32 m0, %[dma], {buf * 65536 + jj * 4096}"]
         if conv:   # (the two VALU instructions are the wait state between the M0 write and the piece)
-            return m0 + emit_event(("VA", jj), dict(mode="A", geom=geom)) + [f"buffer_load_dwordx4 %[tv{jj & 3}], %[ra], %[koffa] offen" + aux_a + " lds"]
-        return m0 + ["s_nop 0", f"buffer_load_dwordx4 %[va{jj}], %[ra], %[koff] offen" + aux_a + " lds"]
+            return m0 + emit_event(("VA", jj), dict(mode="A", geom=geom)) + [f"buffer_load_dwordx4 %[tv{jj & 3}], %[ra], %[koffa] offen lds"]
+        return m0 + ["s_nop 0", f"buffer_load_dwordx4 %[va{jj}], %[ra], %[koff] offen lds"]
     P = ["s_nop 4"] + (list(CONV_STATE_INIT) if conv else ["s_mov_b32 %[koff], %[k0b]"])
     for jj in range(npa):
         P += a_piece(jj, 0)
@@ -478,18 +465,13 @@ OPERANDS_DOC = """// operands of X2I_GEMM256W_LOOP (all named):
 
 def main():
     out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gemm256w_loop.inc")
-    # _V1.._V3 are A/B variants compiled only into the measurement library (-DX2I_ABLATION): non-temporal A / W pieces, one barrier
-    # for both operands of the next tile
-    variants = {"X2I_GEMM256W_LOOP": ("", "", 0), "X2I_GEMM256W_LOOP_V1": (" nt", "", 0), "X2I_GEMM256W_LOOP_V2": ("", " nt", 0),
-                "X2I_GEMM256W_LOOP_V3": ("", "", 3)}
     txt = ["// GENERATED by gen_gemm256w.py -- do not edit; the schedule table lives in the generator.", OPERANDS_DOC]
-    for name, (aa, aw, var) in variants.items():
-        L, vm = generate(aa, aw, var)
-        txt.append(f"// {name}: {len(L)} lines; vmcnt before the next tile's W / A fragments are read: {vm['W']} / {vm['A']}")
-        txt.append(f"#define {name} \\")
-        txt += [f'  "{l}\\n" \\' for l in L[:-1]]
-        txt.append(f'  "{L[-1]}\\n"')
-        txt.append("")
+    L, vm = generate()
+    txt.append(f"// X2I_GEMM256W_LOOP: {len(L)} lines; vmcnt before the next tile's W / A fragments are read: {vm['W']} / {vm['A']}")
+    txt.append("#define X2I_GEMM256W_LOOP \\")
+    txt += [f'  "{l}\\n" \\' for l in L[:-1]]
+    txt.append(f'  "{L[-1]}\\n"')
+    txt.append("")
     P, MC, MZ, D, vm = generate_persistent()
     txt.append("// persistent (seamless) form -- additional operands: wa0..7 / aa0..7 are \"+v\" (live between the statements), na0..7 / nw0..7 \"v\" = the NEXT")
     txt.append("// output tile's piece offsets (0x80000000 everywhere behind the last tile); nk >= 2;")

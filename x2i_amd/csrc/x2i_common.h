@@ -28,10 +28,8 @@ struct X2IOptions {
   int gemm_gm;            // 0 = per-shape XCD patch height; > 0 forces it                                 X2I_GEMM_GM
   int gemm_split_tail;    // 1 = peel a thin last round into a 128^2 launch (default)                      X2I_GEMM_NOSPLIT=1 -> 0
   int gemm_w4;            // 1 = plain 256^2 launches take the 4-wave hand-scheduled kernel (gemm256w.hip, default); 0 = 8-wave gemm256.hip   X2I_GEMM_W4
-  int attn_bwd_overlap;   // 1 = the dQ and dK / dV passes fill each other's partly filled last rounds: one fused launch (pipelined kernels) or a side stream (the older ones)
-  int attn_bwd_dq64;      // 1 = the dQ pass of the attention backward keeps 64 query rows per wave (0: 32, A/B; bit-identical)
-  int attn_bwd_pipe;      // 1 = the dK / dV pass runs the software-pipelined kernel (attn_bwd_dkdv_kernel: element-wise section under the MFMAs; default);
-                          // 0 = attn_bwd_kernel<1> (A/B; bit-identical)                                          X2I_ATTN_BWD_PIPE
+  int attn_bwd_overlap;   // 1 = the dQ and dK / dV passes of the attention backward fill each other's partly filled last rounds: one fused launch
+                          // (default); 0 = the two passes one after the other (bit-identical)                        X2I_ATTN_BWD_OVERLAP
   int train_rows_wg;      // 1 = ln_mod_bwd / gate_bwd of the training step run a workgroup per row group, a thread per eight columns (default);
                           // 0 = the wave-per-row forms (A/B; same values up to the summation order of the row statistics)    X2I_TRAIN_ROWS_WG
   int gemm_pair;          // 1 = x2i_gemm_pair_bf16 / x2i_gemm_qkv_pair_bf16 issue ONE grouped persistent launch when they can (0: always two launches)
@@ -42,8 +40,6 @@ struct X2IOptions {
                           // with fix-up, gemm256p.hip FX; not bit-identical to whole tiles -- the K sum is associated differently; decided by the
                           // item's shape alone).  2 (DEFAULT) = items with at most half a round of tiles (512^2 samples); 1 = every item below one
                           // round; 0 = never                                                                                 X2I_GEMM_FX
-  int gemm_r2;            // A/B: 1 = plain bf16 launches take the "two residents" kernel (gemm_r2.hip: 256 x 128 tiles, two workgroups per CU) when
-                          // their shape allows (K % 256 == 0); bit-identical results; default 0                              X2I_GEMM_R2
   int gemm_fp8_persist;   // 1 = x2i_gemm_fp8 / x2i_gemm_qkv_fp8 take the persistent four-wave form when they can (default); 0 = the one-tile 8-wave kernel (A/B)
   int gemm_persist;       // 1 = batch-1 launches with whole-line epilogues take the persistent form (gemm256p.hip, default)   X2I_GEMM_PERSIST
   int conv256;            // 1 = >= 256-channel convolutions use the 256^2 kernel (default)                X2I_CONV256
@@ -51,7 +47,8 @@ struct X2IOptions {
                           // eight-wave one-tile form (gemm256.hip); bit-identical results                   X2I_CONV_W4
   int conv_korder;        // persistent conv kernels: 1 = K runs (filter row, channel slice, kx): a filter row's taps back to back, their shifted re-reads hit
                           // L2 (default); 0 = (filter row, kx, channel slice), the other kernels' order: bit-identical to them              X2I_CONV_KORDER
-  int attn_variant;       // 0 = automatic (8-wave ping-pong when the grid fills the chip, else 4-wave); 1..8 = A/B   X2I_ATTN_VARIANT
+  int attn_variant;       // 0 = automatic (8-wave ping-pong when the grid fills the chip, else 4-wave); A/B: 5..8 = ping-pong, 9 = attention_w4.hip,
+                          // 12 = attention_w16.hip, any other = the 4-wave kernel                                    X2I_ATTN_VARIANT
   int attn_w16;           // 1 = x2i_attention_prefers_vt_perm may say yes (sampling path on attention_w16.hip; default); 0 = never; 2 = at any size   X2I_ATTN_W16
   int attn_streamk;       // 1 = x2i_attention_vp_ws_bf16 cuts the items of a partly filled last round along the key axis over all CUs (chained through the
                           // caller's workspace: bit-identical; default); 0 = whole items only                                X2I_ATTN_STREAMK
@@ -60,16 +57,12 @@ struct X2IOptions {
   int last_gemm_tile;     // read-only introspection for the parity tests: tile edge of the kernel the last GEMM / conv launch used
                           // (256, 128, 0 = generic kernel), + 1000 when a peeled 128^2 tail launch followed the 256^2 launch
   // measurement-only library (libx2i_hip_ablate.so, -DX2I_ABLATION); ignored by the product library
-  int gemm_lform;         // 0 = k-half-unit 256^2 kernel                                                   X2I_GEMM_LFORM
-  int gemm_ablate;        // ablation bit mask, wrong results by design                                     X2I_GEMM_ABLATE
-  int attn_ablate;        //                                                                                X2I_ATTN_ABLATE
+  int attn_ablate;        // >= 100: attention_w16.hip cuts its stream-K items at key tile (value - 100) (tools/attn_sk_bench.py --cut)   X2I_ATTN_ABLATE
 };
 X2IOptions& x2i_options();
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device) instead of once per launch
 int x2i_ensure_dynamic_smem(const void* kernel, int bytes);
 int x2i_num_cus();  // compute units of the current device (cached)
-// a second stream + fork / join events per device for x2i_attention_bwd_bf16 (created on first use outside a capture; false: not available)
-bool x2i_side_stream(hipStream_t main, hipStream_t* side, hipEvent_t* fork, hipEvent_t* join);
 struct x2i_gemm_args;
 bool x2i_streamk_workspace(const x2i_gemm_args* a, float** slabs, unsigned** flags, int* rc);  // the caller's workspace, validated
 long long x2i_conv_moments_scratch(int M, int N, int batch);   // gemm.hip: floats of x2i_conv_desc.moments_scratch
