@@ -99,7 +99,10 @@ int x2i_is_ablation_build(void);
  * A: bf16 [M,K] (row stride lda, batch stride a_batch_stride elements); W: bf16 [N,K] (row stride ldw);
  * C: bf16 (or f32 when out_f32) row stride ldc; C2 optional bf16 (same strides as C); gate: f32 [batch][N].
  * res may alias C.  Fast path needs K % 64 == 0 and 16-byte aligned rows; anything else takes a slow
- * generic kernel. */
+ * generic kernel.  Rounding: acc is the f32 sum of the K products; v stays f32 through the whole epilogue (the residual step is one fmaf)
+ * and is rounded ONCE, to nearest even, into C (bf16) -- C2 rounds act2(v) once; an f32 C is v.  Only the M x N elements of C / C2 at
+ * (z, m, n) are written.  Every kernel form (tile sizes, persistent, stream-K, FX, grouped pair) keeps this; tests/gemm_ref.py bounds each
+ * element by it (tests/test_gemm_fp64_gpu.py). */
 typedef struct x2i_gemm_args {
   const void* A; int64_t a_batch_stride; int32_t lda;
   const void* W; int32_t ldw;
@@ -347,6 +350,10 @@ typedef struct x2i_qkv_desc {
                         * 16 ((kk >> 2) & 1) + 4 (kk >> 3) + (kk & 3): the order x2i_attention_vp_bf16 (the 16 x 16 x 32 MFMA attention kernel)
                         * reads.  Every producer of one attention call's V^T must use the same value (x2i_attention_prefers_vt_perm) */
 } x2i_qkv_desc;
+/* Padding: a fused QKV launch writes Q / K rows and V^T positions of the tokens its rows map to, nothing else.  Rows >= S of Q / K and the
+ * V^T positions that hold no token < S (with vt_perm, those inside the last 32-token span that its missing tokens would take) are never
+ * written: the caller zero-fills them once (x2i_amd/flux.py) and the attention kernels rely on that.  Rounding: x = bf16(acc + bias) is
+ * rounded once; q / k leave norm and RoPE in f32 and are rounded once; V^T holds x. */
 int x2i_gemm_qkv_bf16(const x2i_gemm_args* args, const x2i_qkv_desc* qkv, x2i_stream_t stream);
 /* Two GEMMs of the same kind -- the image-stream and the text-stream linear of a double-stream block (lightcontrol_flux.py:173-200:
  * to_q|k|v / add_q|k|v_proj, to_out[0] / to_add_out, ff / ff_context): same layer type, different weights, 8 : 1 in rows -- as ONE
