@@ -318,7 +318,12 @@ int x2i_attention_e4m3out(const void* Q, const void* K, const void* VT, void* O8
  * 1e-6), torch.cat([txt, img], dim=2) and apply_rotary_emb.
  * Joint token s of batch b comes from qkv0 row b*S0+s if s < S0, else qkv1 row b*(S-S0)+(s-S0); a row is
  * [q(H*128) | k(H*128) | v(H*128)] with stride ld.  nq0/nk0 are the RMSNorm weights for source 0
- * (norm_added_q/k), nq1/nk1 for source 1 (norm_q/k).  cos/sin: f32 [S,128]. */
+ * (norm_added_q/k), nq1/nk1 for source 1 (norm_q/k).  cos/sin: f32 [S,128].
+ * Rounding: q / k leave norm and RoPE in f32 and are rounded once; V^T holds v bit for bit.
+ * Writes: Q / K rows s < S of every sample and head; rows >= S are never written.  V^T positions [0, S) hold v, positions
+ * [S, 64 * ceil(S / 64)) are written with +0 (the last 64-token transpose tile), positions from 64 * ceil(S / 64) to Spad are never
+ * written.  The zeros are those the caller's one-time zero fill put there (x2i_amd/flux.py), which the attention kernels rely on, so
+ * both QKV paths leave the same padding behind; a caller that skips the fill gets zeros only up to 64 * ceil(S / 64). */
 int x2i_qkv_split_bf16(const void* qkv0, const void* qkv1, int32_t ld0, int32_t ld1, int32_t B, int32_t S, int32_t S0,
                        int32_t H, const void* nq0, const void* nk0, const void* nq1, const void* nk1,
                        const float* cos, const float* sin, void* Q, void* K, void* VT, int32_t Spad, float eps,
@@ -372,7 +377,10 @@ int x2i_gemm_qkv_fp8(const x2i_gemm_args* args, const x2i_fp8_desc* fp8, const x
 /* LayerNorm(elementwise_affine=False, eps) * (1 + scale[b]) + shift[b]   (AdaLayerNormZero / ZeroSingle /
  * Continuous and `norm2(x) * (1 + scale_mlp[:, None]) + shift_mlp[:, None]`, lightcontrol_flux.py:166-170,
  * 183-184,196-197,89,542).  X,Y: bf16 [B][S][D] with row strides ldx/ldy and batch strides (elements).  Rows
- * s < S0 use (shift0, scale0), the others (shift1, scale1); each is f32 [B][D] with batch stride mod_bs. */
+ * s < S0 use (shift0, scale0), the others (shift1, scale1); each is f32 [B][D] with batch stride mod_bs.
+ * Mean and variance (two passes over the row) in f32, y = fmaf((x - mean) * rstd, 1 + scale, shift), each output rounded to bf16 once
+ * (round to nearest even); a row of equal values gives exactly bf16(shift).  Writes Y[b][s][0, D) for b < B, s < S, nothing else:
+ * columns [D, ldy) and the rows between batch strides keep their contents. */
 int x2i_ln_modulate_bf16(const void* X, int64_t x_bs, int32_t ldx, void* Y, int64_t y_bs, int32_t ldy, int32_t B,
                          int32_t S, int32_t D, int32_t S0, const float* shift0, const float* scale0,
                          const float* shift1, const float* scale1, int64_t mod_bs, float eps, x2i_stream_t stream);
@@ -384,7 +392,10 @@ int x2i_ln_affine_bf16(const void* X, void* Y, int64_t rows, int32_t D, const vo
 /* Y[b][n] (+)= act_out( bias[n] + sum_k W[n][k] * act_in(X[b][k]) ), M = B <= 64 rows: the HBM-bound
  * "skinny" linears -- AdaLayerNorm* modulation (SiLU in), time/text/guidance embedders (diffusers
  * CombinedTimestep*Embeddings; lightcontrol_flux.py:249-254,452-456), ControlNeXt time embedding.
- * X: f32 or bf16 [B,K]; W bf16 [N,K]; bias bf16 or NULL; Y f32 [B,N] (row stride ldy). */
+ * X: f32 or bf16 [B,K]; W bf16 [N,K]; bias bf16 or NULL; Y f32 [B,N] (row stride ldy).
+ * Each output is one f32 value (the sum over k in f32, + bias, act_out; with accumulate one more f32 add to the Y read back), and a
+ * sample's row does not depend on how many samples share the call (B > 8: calls of up to 8 rows).  Writes Y[b][0, N) for b < B,
+ * nothing else: columns [N, ldy) keep their contents. */
 int x2i_skinny_linear(const void* X, int32_t x_is_bf16, const void* W, const void* bias, float* Y, int32_t ldy,
                       int32_t B, int32_t N, int32_t K, int32_t act_in, int32_t act_out, int32_t accumulate,
                       x2i_stream_t stream);
@@ -407,7 +418,8 @@ int x2i_rope_table_f32(const float* ids, int32_t S, int32_t d0, int32_t d1, int3
 /* X[b][s][:] = bf16(X + gate[b][:] * T[b][s][:]): `hidden_states + gate.unsqueeze(1) * attn_output` (lightcontrol_flux.py:180-181,
  * 193-194) as a separate pass.  The sampling path never needs it (the gate / residual ride in the projection's epilogue); it exists
  * for the attention-distillation capture (train/train_qwenvl.py:206-214: forward hooks on every block's `attn`), where the
- * projected attention outputs have to exist as tensors of their own.  Strides in elements; gate f32 [B][D] with batch stride gate_bs. */
+ * projected attention outputs have to exist as tensors of their own.  Strides in elements; gate f32 [B][D] with batch stride gate_bs.
+ * One fmaf and one bf16 rounding (round to nearest even) per element; writes X[b][s][0, D) for b < B, s < S, nothing else. */
 int x2i_gated_residual_bf16(void* X, int64_t x_bs, int32_t ldx, const void* T, int64_t t_bs, int32_t ldt, const float* gate,
                             int64_t gate_bs, int32_t B, int32_t S, int32_t D, x2i_stream_t stream);
 

@@ -52,9 +52,10 @@ ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_SILU = 0, 1, 2, 3
 
 # ---------------------------------------------------------------------------------------------------------------- float64 helpers
 def ulp_bf16(x):
-    """ulp of bf16 at |x| (float64; 2^-133 below the smallest normal)."""
-    _, e = torch.frexp(x.abs().clamp_min(2.0 ** -126))
-    return torch.ldexp(torch.ones_like(x), (e - 8).to(torch.int32))
+    """ulp of bf16 at |x| (float64; 2^-133 below the smallest normal).  Built from the exponent bits: exact on every device (torch.ldexp
+    goes through pow(2, e), which on the GPU need not be exact -- and a bound half an f64 ulp short rejects a correct tie)."""
+    e = (x.double().abs().clamp_min(2.0 ** -126).view(torch.int64) >> 52) & 0x7FF
+    return ((e - 7) << 52).view(torch.float64)
 
 
 def bf16_rne(x):
@@ -141,6 +142,30 @@ def rope_rows(cos, sin, tok):
     return cos[tok].double(), sin[tok].double()
 
 
+def norm_rope_expect(x, dx, nw, scale, epsf, c, s):
+    """RMSNorm * w * scale, then interleaved-pair RoPE, of bf16 values x float64 [m, H, 128] (dx [m, H, 128]: the allowance on x, 0 where x
+    is exact), c / s float64 [m, 128]: (want, f32 part of the bound) float64 [m, H, 128] -- norm_rope8 / rms_rsqrt128 (csrc/x2i_common.h),
+    shared by the fused QKV epilogues and x2i_qkv_split_bf16."""
+    w = nw.double() * scale
+    ss = (x * x).sum(-1, keepdim=True)
+    r = torch.rsqrt(ss / 128.0 + epsf)
+    dss = (dx * (2 * x.abs() + dx)).sum(-1, keepdim=True)
+    rmax = torch.rsqrt((ss - dss).clamp_min(0.0) / 128.0 + epsf)
+    dr = 0.5 * rmax ** 3 * dss / 128.0
+    y = x * r * w
+    dy = w.abs() * (r * dx + (x.abs() + dx) * dr)
+    cc, ss_ = c[:, None, :], s[:, None, :]
+    ye, yo, dye, dyo = y[..., 0::2], y[..., 1::2], dy[..., 0::2], dy[..., 1::2]
+    ce, co, se, so = cc[..., 0::2], cc[..., 1::2], ss_[..., 0::2], ss_[..., 1::2]
+    o = torch.empty_like(y)
+    b = torch.empty_like(y)
+    o[..., 0::2] = ye * ce - yo * se
+    o[..., 1::2] = yo * co + ye * so
+    b[..., 0::2] = dye * ce.abs() + dyo * se.abs() + U_NORM * ((ye * ce).abs() + (yo * se).abs())
+    b[..., 1::2] = dyo * co.abs() + dye * so.abs() + U_NORM * ((yo * co).abs() + (ye * so).abs())
+    return o, b
+
+
 def qkv_expect(A, W, bias, norm_q, norm_k, c, s, *, H, q_scale=1.0, eps=1e-6):
     """Expected Q / K / V rows of x2i_gemm_qkv_bf16 for A [m, K]: (want, bound) float64 [m, 3 H 128] in GEMM-column order (q | k | v sections,
     head-major, 128 dims each) and delta, the part of the bound that is not the output's own rounding.  c, s: float64 [m, 128] RoPE rows of the
@@ -157,28 +182,12 @@ def qkv_expect(A, W, bias, norm_q, norm_k, c, s, *, H, q_scale=1.0, eps=1e-6):
     delta = d.clone()
     qs = float(torch.tensor(q_scale if q_scale not in (0.0, 1.0) else 1.0, dtype=torch.float32))
     epsf = float(torch.tensor(eps, dtype=torch.float32))
-    cc, ss_ = c[:, None, :], s[:, None, :]
     for sec, nw, scale in ((0, norm_q, qs), (1, norm_k, 1.0)):
         sl = slice(sec * HD, (sec + 1) * HD)
         lo, hi = bf16_rne(lin[:, sl] - d[:, sl]), bf16_rne(lin[:, sl] + d[:, sl])
         x = bf16_rne(lin[:, sl]).view(m, H, 128)
         dx = (hi - lo).view(m, H, 128)
-        w = nw.double() * scale
-        ss = (x * x).sum(-1, keepdim=True)
-        r = torch.rsqrt(ss / 128.0 + epsf)
-        dss = (dx * (2 * x.abs() + dx)).sum(-1, keepdim=True)
-        rmax = torch.rsqrt((ss - dss).clamp_min(0.0) / 128.0 + epsf)
-        dr = 0.5 * rmax ** 3 * dss / 128.0
-        y = x * r * w
-        dy = w.abs() * (r * dx + (x.abs() + dx) * dr)
-        ye, yo, dye, dyo = y[..., 0::2], y[..., 1::2], dy[..., 0::2], dy[..., 1::2]
-        ce, co, se, so = cc[..., 0::2], cc[..., 1::2], ss_[..., 0::2], ss_[..., 1::2]
-        o = torch.empty_like(y)
-        b = torch.empty_like(y)
-        o[..., 0::2] = ye * ce - yo * se
-        o[..., 1::2] = yo * co + ye * so
-        b[..., 0::2] = dye * ce.abs() + dyo * se.abs() + U_NORM * ((ye * ce).abs() + (yo * se).abs())
-        b[..., 1::2] = dyo * co.abs() + dye * so.abs() + U_NORM * ((yo * co).abs() + (ye * so).abs())
+        o, b = norm_rope_expect(x, dx, nw, scale, epsf, c, s)
         want[:, sl] = o.view(m, HD)
         bound[:, sl] = _round_bound(o, b, False).view(m, HD)
         # (for the statistic of check_block only: heads with an x at a rounding midpoint may use their whole dx allowance -- left out of it)

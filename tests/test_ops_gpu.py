@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import primitives as P
+from tests import ew_ref as E
 from tests.util import rel_l2, seeded, span_permute
 
 pytestmark = pytest.mark.gpu
@@ -275,6 +276,8 @@ def test_ln_modulate_two_streams(ops):
     ref[:, :S0] = ln[:, :S0] * (1 + mod[:, None, D:2 * D]) + mod[:, None, 0:D]
     ref[:, S0:] = ln[:, S0:] * (1 + mod[:, None, 3 * D:]) + mod[:, None, 2 * D:3 * D]
     assert rel_l2(Y, ref) < 5e-3
+    # every element within its float64-derived bound (tests/ew_ref.py), each row with its own stream's vectors
+    E.check_ln(E.Report("ln_modulate_two_streams"), g(X), Y, S0, m[:, 0:], m[:, D:], m[:, 2 * D:], m[:, 3 * D:], 1e-6).done()
 
 
 @pytest.mark.parametrize("D", [64, 896, 2048, 3584])
@@ -290,10 +293,13 @@ def test_skinny_linear(ops, B, N, K):
     out = ops.skinny_linear(g(X), g(W), g(b), act_in=3, act_out=0)
     ref = F.linear(F.silu(X), W.float(), b.float())
     assert rel_l2(out, ref) < 1e-4
+    E.check_skinny(E.Report("skinny silu in"), g(X), g(W), g(b), out, act_in=3).done()
     out2 = ops.skinny_linear(g(bf(X)), g(W), None, act_in=0, act_out=3)
     assert rel_l2(out2, F.silu(F.linear(bf(X).float(), W.float()))) < 1e-4
+    E.check_skinny(E.Report("skinny silu out"), g(bf(X)), g(W), None, out2, act_out=3).done()
     acc = ops.skinny_linear(g(X), g(W), g(b), out=out.clone(), act_in=3, accumulate=True)
     assert rel_l2(acc, 2 * ref) < 1e-4
+    E.check_skinny(E.Report("skinny accumulate"), g(X), g(W), g(b), acc, act_in=3, y_old=out).done()
 
 
 def test_timestep_sinusoid(ops):
@@ -301,6 +307,12 @@ def test_timestep_sinusoid(ops):
     for dim in (256, 128):
         out = ops.timestep_sinusoid(g(t), dim)
         assert (out.cpu() - P.timesteps_proj(t, dim)).abs().max() < 2e-3  # fp32 cos/sin of arguments up to 1e3
+        # per element against float64 frequencies and cos / sin (tests/ew_ref.py): a bound of at most 2.7e-4 at t = 1000
+        want, bound, delta = E.sinusoid_expect(t, dim, False)
+        rep = E.Report(f"sinusoid dim={dim}")
+        rep.check(out.cpu(), want, bound, delta, sample=torch.arange(4), token=torch.zeros(4, dtype=torch.long), unit=1)
+        rep.done()
+        assert float(bound.max()) < 2e-3 / 4
 
 
 def test_euler_step(ops):
