@@ -13,8 +13,11 @@ re-executes this file under `python -m torch.distributed.run --standalone --nnod
 launcher (torchrun / the driver's torch.distributed.run command) it asserts WORLD_SIZE == --gpus.  The printed n_gpus is
 dist.get_world_size(), never the flag.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (dominant kernel = bf16 MFMA GEMM, measured live with HIP
-events on the launch stream) and "cpu_baseline" (the CPU oracle timed on the host cores on a bounded sample).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps passes, writes --dump-outputs and prints the
+line; everything beside the headline is measured with `--full` only: "roofline" (dominant kernel = bf16 MFMA GEMM, measured live
+with HIP events on the launch stream, with the matrix pipe alone beside it), "roofline_attention", "vae", the "fp8_mlp" / "fp8_all"
+lines and "cpu_baseline" (the CPU oracle timed on the host cores on a bounded sample); `--no-roofline`, `--no-fp8-lines` and
+`--no-cpu-baseline` drop single ones of them from a --full run.
 """
 import argparse
 import json
@@ -560,11 +563,14 @@ def main(argv=None):
     ap.add_argument("--fp8-mode", default="mlp", choices=["mlp", "all"],
                     help="with --dtype fp8: 'mlp' = the MLP GEMMs only; 'all' = also the image-stream / single-block QKV and attention "
                          "output projections (97 %% of the GEMM FLOPs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the line's own steps, also measure what the headline does not need: the live roofline probes, the VAE decode "
+                         "line, the fp8_mlp / fp8_all lines and the CPU baseline (off by default: a plain run times its steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-fp8-lines", action="store_true", help="skip the extra fp8_mlp / fp8_all measurements attached to the bf16 line")
+    ap.add_argument("--no-fp8-lines", action="store_true", help="with --full: skip the extra fp8_mlp / fp8_all measurements attached to the bf16 line")
     ap.add_argument("--no-roofline", action="store_true",
-                    help="skip the live roofline probe (for rocprofv3 --kernel-trace runs whose GEMM total must contain the timed job only)")
+                    help="with --full: skip the live roofline probes (a plain run never starts them)")
     ap.add_argument("--rccl-selftest", action="store_true",
                     help="initialise the RCCL process group and run the all-gather / barrier / max-over-ranks path even at one rank (under a "
                          "launcher with --nproc-per-node 1, or plain): exercises the N > 1 code path on a one-GPU box")
@@ -718,6 +724,7 @@ def main(argv=None):
         line = {
             "metric": "images/sec, FLUX-schnell %dx%d %d-step (projector + denoise loop), whole job" % (args.size, args.size, N),
             "value": images_s, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "setup_passes": setup_passes,
+            "full": args.full,
             "ms_per_step": ms_pass, "ms_per_denoise_step": ms_pass / N, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "bf16", "data": "synthetic (random-init weights, random MLLM hidden states, seeded noise)",
             "rccl_ranks": world if use_dist else 0, "rank_ms_per_step": [round(x, 3) for x in rank_ms],
@@ -754,38 +761,40 @@ def main(argv=None):
                                         "; everything else bf16 as in the headline run; stated drift (~6e-2 on the final latents: outside the 5e-2 proposed for the path) in "
                                         "tests/test_fp8_gpu.py")
                 line["metric"] += " [fp8 MLP GEMMs]" if args.fp8_mode == "mlp" else " [fp8 MLP + attention-projection GEMMs]"
-                line["roofline"] = None if args.no_roofline else gemm_roofline_fp8(B)
-            else:
-                line["roofline"] = None if args.no_roofline else gemm_roofline(B)
-                if not args.no_roofline and args.size == 1024:
-                    line["roofline_attention"] = attention_roofline(B)
-                    if args.config == 2 and world == 1:
-                        line["vae"] = vae_decode_line(B, images_s)
-            if args.dtype == "bf16" and world == 1 and args.config == 2 and not args.no_fp8_lines:
-                # the opt-in e4m3 configurations in the same driver-timed record (the headline above stays bf16 = the reference's arithmetic):
-                # 1 warm-up + 3 timed passes each; stated tolerances in tests/test_fp8_gpu.py / test_fullscale_parity_gpu.py
-                for mode in ("mlp", "all"):
-                    model.enable_fp8(mode)
-                    for _ in range(max(1, setup_passes)):   # (eager pass, then the capture: see setup_passes)
-                        one_pass()
-                    torch.cuda.synchronize()
-                    t1 = time.perf_counter()
-                    for _ in range(3):
-                        one_pass()
-                    torch.cuda.synchronize()
-                    ms8 = (time.perf_counter() - t1) / 3 * 1e3
-                    line["fp8_" + mode] = {"images_s": B * 1e3 / ms8, "ms_per_denoise_step": ms8 / N, "passes": 3,
-                                           "model_tflops_per_gpu": fl * N / (ms8 * 1e-3) / 1e12,
-                                           "gemm_flops_on_e4m3": 0.72 if mode == "mlp" else 0.97}
-                r8 = gemm_roofline_fp8(B)
-                line["fp8_mlp"]["roofline"] = line["fp8_all"]["roofline"] = {k: r8[k] for k in ("bound", "achieved", "peak", "unit", "frac", "frac_best", "frac_of_pipe_alone", "kernel", "shapes")}
-                model.enable_fp8(None)
-                ops.streamk_check(sync=True)
-            if not args.no_cpu_baseline and world == 1 and args.config == 2:
-                line["cpu_baseline"] = cpu_baseline()
+            if args.full:   # everything beside the headline; a plain run prints the line as it stands
+                if args.dtype == "fp8":
+                    line["roofline"] = None if args.no_roofline else gemm_roofline_fp8(B)
+                else:
+                    line["roofline"] = None if args.no_roofline else gemm_roofline(B)
+                    if not args.no_roofline and args.size == 1024:
+                        line["roofline_attention"] = attention_roofline(B)
+                        if args.config == 2 and world == 1:
+                            line["vae"] = vae_decode_line(B, images_s)
+                if args.dtype == "bf16" and world == 1 and args.config == 2 and not args.no_fp8_lines:
+                    # the opt-in e4m3 configurations in the same driver-timed record (the headline above stays bf16 = the reference's arithmetic):
+                    # 1 warm-up + 3 timed passes each; stated tolerances in tests/test_fp8_gpu.py / test_fullscale_parity_gpu.py
+                    for mode in ("mlp", "all"):
+                        model.enable_fp8(mode)
+                        for _ in range(max(1, setup_passes)):   # (eager pass, then the capture: see setup_passes)
+                            one_pass()
+                        torch.cuda.synchronize()
+                        t1 = time.perf_counter()
+                        for _ in range(3):
+                            one_pass()
+                        torch.cuda.synchronize()
+                        ms8 = (time.perf_counter() - t1) / 3 * 1e3
+                        line["fp8_" + mode] = {"images_s": B * 1e3 / ms8, "ms_per_denoise_step": ms8 / N, "passes": 3,
+                                               "model_tflops_per_gpu": fl * N / (ms8 * 1e-3) / 1e12,
+                                               "gemm_flops_on_e4m3": 0.72 if mode == "mlp" else 0.97}
+                    r8 = gemm_roofline_fp8(B)
+                    line["fp8_mlp"]["roofline"] = line["fp8_all"]["roofline"] = {k: r8[k] for k in ("bound", "achieved", "peak", "unit", "frac", "frac_best", "frac_of_pipe_alone", "kernel", "shapes")}
+                    model.enable_fp8(None)
+                    ops.streamk_check(sync=True)
+                if not args.no_cpu_baseline and world == 1 and args.config == 2:
+                    line["cpu_baseline"] = cpu_baseline()
             print(json.dumps(line), flush=True)
     if use_dist:
-        dist.barrier()  # rank 0 is still timing the roofline kernels: leave the job together
+        dist.barrier()  # with --full, rank 0 may still be timing the roofline kernels: leave the job together
         dist.destroy_process_group()
 
 

@@ -62,3 +62,10 @@ def test_dump_outputs_samples_beyond_the_limit(tmp_path):
 def test_steps_below_one_is_refused():
     r, lines = _bench(["--selftest-launcher", "--steps", "0", "--warmup", "0", "--batch", "1", "--size", "128"])
     assert r.returncode != 0 and not lines and "--steps" in r.stderr
+
+
+def test_full_is_off_by_default_and_the_line_says_which_run_it_was():
+    common = ["--selftest-launcher", "--steps", "1", "--warmup", "0", "--batch", "1", "--size", "128"]
+    for extra, want in (([], False), (["--full"], True)):
+        r, lines = _bench(common + extra)
+        assert r.returncode == 0 and len(lines) == 1 and lines[0]["full"] is want, r.stderr[-2000:]
