@@ -527,6 +527,41 @@ int x2i_clip_coef_f32(const float* sumsq, float max_norm, float* out, x2i_stream
 int x2i_adamw_bf16(void* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                    float bias_correction1, float bias_correction2, const float* grad_coef, x2i_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * ControlNeXt backward: the trainable side of the LightControl step (lightcontrol/train_lightcontrol.py:572-588, :769-775: the control nets'
+ * `loss.backward()`, then clip_grad_norm_ and AdamW, which x2i_sum_partials / x2i_clip_coef_f32 / x2i_adamw_bf16 serve).  Data gradients are
+ * x2i_conv2d_nhwc_bf16 launches on host-repacked weights; the entry points below are the weight gradients and the GroupNorm backward
+ * (csrc/conv_bwd.hip).  Added under ABI version 5: new entry points only.  Every workspace is caller-owned f32 scratch sized by its query
+ * (which returns X2I_ERR_SHAPE for a shape the entry point refuses); results are deterministic (per-split partials, then x2i_reduce_rows_f32's
+ * fixed-order sum; no atomics), and `accumulate` = 1 adds into dw / db (gradient accumulation).
+ *
+ * Weight gradient of nn.Conv2d(Cin -> Cout, (KH, KW), stride, pad) on NHWC bf16: dw f32 [Cout][Cin][KH][KW] (the parameter's own layout, written by
+ * the epilogue) (+)= sum over b, oy, ox of dy[b][oy][ox][co] x[b][stride oy + ky - pad][stride ox + kx - pad][ci] (zero outside the image); db f32
+ * [Cout] (+)= sum of dy, or NULL.  x: [B][H][W][Cin] dense; dy: output pixel rows [B][OH * OW] of row stride ldy (>= Cout, % 8) and batch stride
+ * dy_batch_stride (% 8), so that the image rows of a token buffer can be passed as they are.  Cin, Cout multiples of 64; 16-byte aligned x, dy. */
+int x2i_conv_wgrad_workspace_floats(int32_t B, int32_t OH, int32_t OW, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW, int64_t* floats);
+int x2i_conv_wgrad_bf16(const void* x, const void* dy, int64_t dy_batch_stride, int32_t ldy, float* dw, float* db, int32_t B, int32_t H, int32_t W,
+                        int32_t Cin, int32_t OH, int32_t OW, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t accumulate,
+                        float* workspace, int64_t workspace_floats, x2i_stream_t stream);
+/* Weight gradient of x2i_conv_stem_bf16's Conv2d(3 -> Cout, k3, s2, p1) (ControlNeXt embedding.0, lightcontrol_flux.py:594): x NHWC bf16 [B][H][W][3],
+ * dy NHWC bf16 [B][ceil(H/2)][ceil(W/2)][Cout] (Cout <= 64); dw f32 [Cout][3][3][3], db f32 [Cout] or NULL.  The hint takes no gradient. */
+int x2i_conv_stem_wgrad_workspace_floats(int32_t B, int32_t H, int32_t W, int32_t Cout, int64_t* floats);
+int x2i_conv_stem_wgrad_bf16(const void* x, const void* dy, float* dw, float* db, int32_t B, int32_t H, int32_t W, int32_t Cout, int32_t accumulate,
+                             float* workspace, int64_t workspace_floats, x2i_stream_t stream);
+/* Backward of x2i_groupnorm_nhwc_bf16, y = act(weight GN(x + pre_add) + bias) + post_add, on NHWC bf16 [B][HW][C] (the post_add term's gradient is dy
+ * itself and stays with the caller).  Statistics are recomputed from x; act' is taken at the recomputed affine output (none, ReLU, SiLU).  Writes
+ * dx bf16 = d loss / d x (+ dx_in when non-NULL: a residual branch's gradient; dx may be dx_in), dweight / dbias f32 [C] (both or neither),
+ * dpre_add f32 [B][C] = d loss / d pre_add (needs pre_add; may be NULL).  in_relu = 1: x is the output of a ReLU and dx is the gradient at that
+ * ReLU's input (zero where x <= 0; no pre_add).  C % 8 == 0, 256 % (C / 8) == 0, C <= 1024. */
+int x2i_groupnorm_bwd_workspace_floats(int32_t B, int64_t HW, int32_t C, int32_t G, int64_t* floats);
+int x2i_groupnorm_nhwc_bwd_bf16(const void* x, const void* dy, const void* weight, const void* bias, const float* pre_add, void* dx, const void* dx_in,
+                                float* dweight, float* dbias, float* dpre_add, int32_t B, int64_t HW, int32_t C, int32_t G, float eps, int32_t act,
+                                int32_t in_relu, int32_t accumulate, float* workspace, int64_t workspace_floats, x2i_stream_t stream);
+/* Weight gradient of the time-embedding linears (TimestepEmbedding, ResnetBlock2D.time_emb_proj; B rows): dw f32 [N][K] (+)= sum_b dy[b][n]
+ * act_in(x[b][k]) (act_in: none or SiLU), db f32 [N] (+)= sum_b dy[b][n] or NULL; dy f32 [B][N], x f32 [B][K] contiguous. */
+int x2i_linear_wgrad_f32(const float* dy, const float* x, float* dw, float* db, int32_t B, int32_t N, int32_t K, int32_t act_in, int32_t accumulate,
+                         x2i_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

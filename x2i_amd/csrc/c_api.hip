@@ -458,4 +458,41 @@ int x2i_attention_bwd_prep_bf16(const void* dO, int64_t do_bs, int32_t lddo, con
   return x2i_launch_attention_bwd_prep(dO, do_bs, lddo, O, o_bs, ldo, D, B, H, S, Spad, (hipStream_t)stream);
 }
 
+// ControlNeXt backward (conv_bwd.hip)
+static int ws_query(long long n, int64_t* floats, const char* what) {
+  if (!floats) return x2i_set_error(X2I_ERR_ARG, "%s: null result pointer", what);
+  if (n < 0) return x2i_set_error(X2I_ERR_SHAPE, "%s: unsupported shape", what);
+  *floats = n;
+  return X2I_OK;
+}
+int x2i_conv_wgrad_workspace_floats(int32_t B, int32_t OH, int32_t OW, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW, int64_t* floats) {
+  return ws_query(x2i_conv_wgrad_workspace(B, OH, OW, Cin, Cout, KH, KW), floats, "conv_wgrad_workspace_floats");
+}
+int x2i_conv_wgrad_bf16(const void* x, const void* dy, int64_t dy_batch_stride, int32_t ldy, float* dw, float* db, int32_t B, int32_t H, int32_t W,
+                        int32_t Cin, int32_t OH, int32_t OW, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t accumulate,
+                        float* workspace, int64_t workspace_floats, x2i_stream_t stream) {
+  return x2i_launch_conv_wgrad(x, dy, dy_batch_stride, ldy, dw, db, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, accumulate, workspace,
+                               workspace_floats, (hipStream_t)stream);
+}
+int x2i_conv_stem_wgrad_workspace_floats(int32_t B, int32_t H, int32_t W, int32_t Cout, int64_t* floats) {
+  return ws_query(x2i_conv_stem_wgrad_workspace(B, H, W, Cout), floats, "conv_stem_wgrad_workspace_floats");
+}
+int x2i_conv_stem_wgrad_bf16(const void* x, const void* dy, float* dw, float* db, int32_t B, int32_t H, int32_t W, int32_t Cout, int32_t accumulate,
+                             float* workspace, int64_t workspace_floats, x2i_stream_t stream) {
+  return x2i_launch_conv_stem_wgrad(x, dy, dw, db, B, H, W, Cout, accumulate, workspace, workspace_floats, (hipStream_t)stream);
+}
+int x2i_groupnorm_bwd_workspace_floats(int32_t B, int64_t HW, int32_t C, int32_t G, int64_t* floats) {
+  return ws_query(x2i_groupnorm_bwd_workspace(B, HW, C, G), floats, "groupnorm_bwd_workspace_floats");
+}
+int x2i_groupnorm_nhwc_bwd_bf16(const void* x, const void* dy, const void* weight, const void* bias, const float* pre_add, void* dx, const void* dx_in,
+                                float* dweight, float* dbias, float* dpre_add, int32_t B, int64_t HW, int32_t C, int32_t G, float eps, int32_t act,
+                                int32_t in_relu, int32_t accumulate, float* workspace, int64_t workspace_floats, x2i_stream_t stream) {
+  return x2i_launch_groupnorm_bwd(x, dy, weight, bias, pre_add, dx, dx_in, dweight, dbias, dpre_add, B, HW, C, G, eps, act, in_relu, accumulate, workspace,
+                                  workspace_floats, (hipStream_t)stream);
+}
+int x2i_linear_wgrad_f32(const float* dy, const float* x, float* dw, float* db, int32_t B, int32_t N, int32_t K, int32_t act_in, int32_t accumulate,
+                         x2i_stream_t stream) {
+  return x2i_launch_linear_wgrad(dy, x, dw, db, B, N, K, act_in, accumulate, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -101,3 +101,16 @@ int x2i_launch_attention_bwd(const void* Q, const void* K, const void* V, const 
                              int have_lse, hipStream_t stream);
 int x2i_launch_attention_bwd_prep(const void* dO, long long do_bs, int lddo, const void* O, long long o_bs, int ldo, float* Dv, int B, int H,
                                   int S, int Spad, hipStream_t stream);
+
+/* ---- backward kernels of the ControlNeXt control nets (conv_bwd.hip); the workspace queries return -1 for a shape the launcher refuses */
+long long x2i_conv_wgrad_workspace(int B, int OH, int OW, int Cin, int Cout, int KH, int KW);
+int x2i_launch_conv_wgrad(const void* x, const void* dy, long long dy_bs, int ldy, float* dw, float* db, int B, int H, int W, int Cin, int OH, int OW,
+                          int Cout, int KH, int KW, int stride, int pad, int accumulate, float* ws, long long ws_floats, hipStream_t stream);
+long long x2i_conv_stem_wgrad_workspace(int B, int H, int W, int Cout);
+int x2i_launch_conv_stem_wgrad(const void* x, const void* dy, float* dw, float* db, int B, int H, int W, int Cout, int accumulate, float* ws,
+                               long long ws_floats, hipStream_t stream);
+long long x2i_groupnorm_bwd_workspace(int B, long long HW, int C, int G);
+int x2i_launch_groupnorm_bwd(const void* x, const void* dy, const void* w, const void* b, const float* pre_add, void* dx, const void* dx_in, float* dw,
+                             float* db, float* dpre, int B, long long HW, int C, int G, float eps, int act, int in_relu, int accumulate, float* ws,
+                             long long ws_floats, hipStream_t stream);
+int x2i_launch_linear_wgrad(const float* dy, const float* x, float* dw, float* db, int B, int N, int K, int act_in, int accumulate, hipStream_t stream);

@@ -944,3 +944,95 @@ def attention_lse(Q, K, VT, out, lse2, B, H, S, Spad, ldo, o_batch_stride, scale
 def attention_bwd_prep(dO, O, Dv, B, H, S, Spad, *, do_bs, lddo, o_bs, ldo, do_offset=0, o_offset=0):
     check(_lib.load().x2i_attention_bwd_prep_bf16(_off(dO, do_offset), do_bs, lddo, _off(O, o_offset), o_bs, ldo, _p(Dv), B, H, S, Spad, _stream()),
           "attention_bwd_prep")
+
+
+# ---------------------------------------------------------------------------------------------------- ControlNeXt backward
+_bwd_ws = {}
+
+
+def _bwd_workspace(device, floats, kind):
+    """Caller-owned f32 scratch of the backward entry points, one growing buffer per (device, kind); launches on one stream reuse it in order."""
+    key = (device, kind)
+    if key not in _bwd_ws or _bwd_ws[key].numel() < floats:
+        _bwd_ws[key] = torch.empty(max(int(floats), 1), device=device, dtype=torch.float32)
+    return _bwd_ws[key]
+
+
+def _query(fn, *args):
+    n = C.c_int64(0)
+    check(fn(*args, C.byref(n)), fn.__name__)
+    return n.value
+
+
+def conv_wgrad_workspace_floats(B, OH, OW, Cin, Cout, KH, KW):
+    return _query(_lib.load().x2i_conv_wgrad_workspace_floats, B, OH, OW, Cin, Cout, KH, KW)
+
+
+def conv_wgrad(x, dy, dw, db, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, *, B=None, dy_offset=0, dy_batch_stride=None, ldy=None, accumulate=False):
+    """Weight gradient of Conv2d(Cin -> Cout, (KH, KW), stride, pad) on NHWC bf16 x [B, H, W, Cin] (include/x2i.h: x2i_conv_wgrad_bf16): dw f32
+    [Cout, Cin, KH, KW] (+)= sum over the output pixels of dy x, db f32 [Cout] (+)= sum dy (or None).  dy: bf16 output pixel rows [B, OH * OW] of
+    row stride ldy (default Cout) and batch stride dy_batch_stride (default OH * OW * ldy), starting at element dy_offset."""
+    lib = _lib.load()
+    _req(x, torch.bfloat16, "x")
+    _req(dy, torch.bfloat16, "dy")
+    _req(dw, torch.float32, "dw")
+    B = x.shape[0] if B is None else B
+    ldy = Cout if ldy is None else ldy
+    dbs = OH * OW * ldy if dy_batch_stride is None else dy_batch_stride
+    if x.numel() < B * H * W * Cin or dy.numel() < dy_offset + (B - 1) * dbs + OH * OW * ldy - (ldy - Cout) or dw.numel() != Cout * Cin * KH * KW or \
+            (db is not None and db.numel() != Cout):
+        raise _lib.X2IError("conv_wgrad: x, dy, dw or db is smaller than the shape arguments say")
+    ws = _bwd_workspace(x.device, conv_wgrad_workspace_floats(B, OH, OW, Cin, Cout, KH, KW), "conv_wgrad")
+    check(lib.x2i_conv_wgrad_bf16(_p(x), _off(dy, dy_offset), dbs, ldy, _p(dw), _p(db), B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad,
+                                  1 if accumulate else 0, _p(ws), ws.numel(), _stream()), "conv_wgrad")
+    return dw
+
+
+def conv_stem_wgrad(x, dy, dw, db, accumulate=False):
+    """Weight gradient of conv_stem's Conv2d(3 -> Cout, k3, s2, p1): x bf16 NHWC [B, H, W, 3], dy bf16 NHWC [B, H/2, W/2, Cout]; dw f32
+    [Cout, 3, 3, 3] and db f32 [Cout] (or None), (+)= (x2i_conv_stem_wgrad_bf16)."""
+    lib = _lib.load()
+    _req(x, torch.bfloat16, "x")
+    _req(dy, torch.bfloat16, "dy")
+    _req(dw, torch.float32, "dw")
+    B, H, W, _ = x.shape
+    Cout = dy.shape[-1]
+    if x.shape[-1] != 3 or tuple(dy.shape) != (B, (H + 1) // 2, (W + 1) // 2, Cout) or dw.numel() != Cout * 27 or (db is not None and db.numel() != Cout):
+        raise _lib.X2IError("conv_stem_wgrad: x [B, H, W, 3], dy [B, H/2, W/2, Cout], dw [Cout, 3, 3, 3], db [Cout]")
+    ws = _bwd_workspace(x.device, _query(lib.x2i_conv_stem_wgrad_workspace_floats, B, H, W, Cout), "conv_stem_wgrad")
+    check(lib.x2i_conv_stem_wgrad_bf16(_p(x), _p(dy), _p(dw), _p(db), B, H, W, Cout, 1 if accumulate else 0, _p(ws), ws.numel(), _stream()),
+          "conv_stem_wgrad")
+    return dw
+
+
+def groupnorm_bwd(x, dy, weight, bias, G, eps, act=ACT_NONE, pre_add=None, dpre=None, dx_in=None, dx=None, dw=None, db=None, in_relu=False,
+                  accumulate=False):
+    """Backward of groupnorm_nhwc(x, weight, bias, G, eps, act, pre_add) on NHWC bf16 x [B, ..., C] (include/x2i.h: x2i_groupnorm_nhwc_bwd_bf16).
+    Returns dx bf16 (+ dx_in); dw / db f32 [C] (+)= d weight / d bias when given; dpre f32 [B, C] <- d pre_add when given.  in_relu: x came out
+    of a ReLU, dx is taken through it."""
+    lib = _lib.load()
+    _req(x, torch.bfloat16, "x")
+    _req(dy, torch.bfloat16, "dy")
+    B, Cc = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * Cc)
+    if dy.shape != x.shape or (dx is not None and dx.shape != x.shape) or (dx_in is not None and dx_in.shape != x.shape) or \
+            any(t is not None and t.numel() != n for t, n in ((pre_add, B * Cc), (dpre, B * Cc), (dw, Cc), (db, Cc))):
+        raise _lib.X2IError("groupnorm_bwd: dy / dx / dx_in shaped like x, pre_add / dpre [B, C], dw / db [C]")
+    dx = torch.empty_like(x) if dx is None else dx
+    ws = _bwd_workspace(x.device, _query(lib.x2i_groupnorm_bwd_workspace_floats, B, HW, Cc, G), "groupnorm_bwd")
+    check(lib.x2i_groupnorm_nhwc_bwd_bf16(_p(x), _p(dy), _p(weight), _p(bias), _p(pre_add), _p(dx), _p(dx_in), _p(dw), _p(db), _p(dpre), B, HW, Cc, G,
+                                          float(eps), act, 1 if in_relu else 0, 1 if accumulate else 0, _p(ws), ws.numel(), _stream()),
+          "groupnorm_bwd")
+    return dx
+
+
+def linear_wgrad(dy, x, dw, db, act_in=ACT_NONE, accumulate=False):
+    """dw f32 [N, K] (+)= dy^T act_in(x), db f32 [N] (+)= column sums of dy (or None); dy f32 [B, N], x f32 [B, K] (x2i_linear_wgrad_f32)."""
+    _req(dy, torch.float32, "dy")
+    _req(x, torch.float32, "x")
+    B, N = dy.shape
+    if x.shape[0] != B or dw.numel() != N * x.shape[1] or (db is not None and db.numel() != N):
+        raise _lib.X2IError("linear_wgrad: dy [B, N], x [B, K], dw [N, K], db [N] (got %s, %s, %s)" % (tuple(dy.shape), tuple(x.shape), tuple(dw.shape)))
+    check(_lib.load().x2i_linear_wgrad_f32(_p(dy.contiguous()), _p(x.contiguous()), _p(dw), _p(db), B, N, x.shape[1], act_in, 1 if accumulate else 0,
+                                           _stream()), "linear_wgrad")
+    return dw
