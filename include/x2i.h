@@ -211,6 +211,13 @@ typedef struct x2i_conv_desc {
                            * ldc, c_batch_stride multiples of 8, 16-byte aligned C) */
   float* moments_scratch; /* caller-owned, x2i_conv_moments_scratch_floats(M, N, batch) floats, 16-byte aligned (required with `moments`) */
 } x2i_conv_desc;
+/* Rounding: the K sum, bias + bias2, the activation and the residual add (ONE f32 add: res + v, no gate) stay in f32; every output is rounded once,
+ * to nearest even, into C.  Write set: element n < N of output pixel (oy, ox) of item z, at C + z * c_batch_stride + oy * pitch + ox * ldc + n with
+ * pitch = out_row_pitch, or OW * ldc -- nothing else: the channels [N, ldc) of a pixel, the pixels of another phase between two rows of a
+ * pitched output, the rows between batch strides keep their contents.  moments: all N entries of every item are written -- entry c % 4 == 0 with the
+ * f32 sums of the ROUNDED outputs of channels c .. c + 3 (a fixed summation tree: deterministic), the other three with +0; with
+ * moments_accumulate the launch's sums are added to the c % 4 == 0 entries and the other three are left alone.  tests/conv_ref.py bounds every
+ * output and every moments entry by this. */
 int x2i_conv2d_nhwc_bf16(const x2i_gemm_args* args, const x2i_conv_desc* conv, x2i_stream_t stream);
 int64_t x2i_conv_moments_scratch_floats(int32_t M, int32_t N, int32_t batch);
 
@@ -218,7 +225,8 @@ int64_t x2i_conv_moments_scratch_floats(int32_t M, int32_t N, int32_t batch);
  * image resolution; infer/inference_qwenvl.py:213-214).  x [B][H][W][Cin], Cin in {32, 64, 96, 128}; w bf16 [Cout][3][3][Cin] (ky,kx,ci);
  * bias bf16 [Cout] or NULL; y [B][H][W][ldy] with ldy % 4 == 0: channels 0 .. 3 of every pixel are written (those behind Cout as zeros),
  * the rest of a pixel is left alone.  The output channels ride in the ROWS of the 16 x 16 x 32 MFMA, 16 neighbouring pixels in its columns
- * (csrc/conv_narrow.hip) -- as an implicit GEMM three channels would pay for a 128-column tile. */
+ * (csrc/conv_narrow.hip) -- as an implicit GEMM three channels would pay for a 128-column tile.  Rounding: f32 sum of the 9 Cin products + bias,
+ * rounded once.  Write set: channels 0 .. 3 of every pixel -- 0 .. Cout - 1 with the results, Cout .. 3 with +0; channels [4, ldy) are never written. */
 int x2i_conv3x3_narrow_bf16(const void* x, const void* w, const void* bias, void* y, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                             int32_t ldy, x2i_stream_t stream);
 
@@ -227,7 +235,8 @@ int x2i_conv3x3_narrow_bf16(const void* x, const void* w, const void* bias, void
  * x [B][Cin][H][W] directly (1 <= Cin <= 4) and writing NHWC bf16 y [B][H][W][Cout] (Cout % 16 == 0, 16 .. 128; 16-byte aligned).  w bf16
  * [Cout][Cin][3][3] = the nn.Conv2d weight as it is; bias bf16 [Cout] or NULL.  f32 accumulation, one rounding.  moments: NULL, or f32 [B][Cout][2]
  * in exactly the layout and fixed-order reduction of x2i_conv_desc.moments (channel-quad sums of the bf16 outputs), with moments_scratch of
- * x2i_conv_moments_scratch_floats(H * W, Cout, B) floats (16-byte aligned).  Deterministic (csrc/vae_encode.hip). */
+ * x2i_conv_moments_scratch_floats(H * W, Cout, B) floats (16-byte aligned).  Deterministic (csrc/vae_encode.hip).  Write set: all of y and all
+ * B * Cout * 2 moments entries (c % 4 == 0: the quad's sums of the rounded outputs; the others +0). */
 int x2i_conv3x3_image_bf16(const void* x, const void* w, const void* bias, void* y, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout,
                            float* moments, float* moments_scratch, x2i_stream_t stream);
 
@@ -242,14 +251,20 @@ int x2i_vae_posterior_bf16(const void* params, int32_t ldp, const void* eps, voi
                            int32_t w, int32_t scale_shift, float shift, float scale, x2i_stream_t stream);
 
 /* Conv2d(3 -> Cout, k=3, stride=2, pad=1) on an NHWC bf16 image (lightcontrol_flux.py:594); w f32 [Cout][3][3][3]
- * (ky,kx,ci), bias f32 [Cout]; y NHWC bf16 [B][H/2][W/2][Cout], Cout % 16 == 0 and <= 64. */
+ * (ky,kx,ci), bias f32 [Cout]; y NHWC bf16 [B][H/2][W/2][Cout], Cout % 16 == 0 and <= 64.  Rounding: the f32 chain bias + 27 products in (ky, kx,
+ * ci) order, rounded once; all of y is written, nothing else. */
 int x2i_conv_stem_bf16(const void* x, const float* w, const float* bias, void* y, int32_t B, int32_t H, int32_t W,
                        int32_t Cout, x2i_stream_t stream);
 
 /* nn.GroupNorm(G, C, eps) on NHWC bf16 [B][HW][C] with fused epilogue: y = act(GN(x + pre_add[b][c]) * w + b) + post_add
  * (ControlNeXt embedding GN+ReLU :595-602; ResnetBlock2D norm1/norm2 + SiLU with the time-embedding term added before
  * norm2; mid block conv->ReLU->GN ... + x :632-653,744).  pre_add: f32 [B][C] or NULL; post_add: bf16 like x or NULL.
- * `partial` is caller-owned scratch of x2i_groupnorm_scratch_floats(B, G) floats. */
+ * `partial` is caller-owned scratch of x2i_groupnorm_scratch_floats(B, G) floats.
+ * Statistics: ONE pass in f32 -- S1 = sum (x + pre_add), S2 = sum (x + pre_add)^2 per (item, group) over 256 slabs of pixels, added in a fixed order;
+ * mean = S1 / n, var = max(S2 / n - mean^2, 0), rstd = rsqrtf(var + eps).  The variance therefore carries a relative error proportional to
+ * kappa = (mean^2 + var) / var (tests/conv_ref.py derives the bound; DESIGN.md has the models' kappa).  A constant group gives rstd = 1 / sqrt(eps).
+ * Apply: sc = rstd * w, sh = fma(pre_add - mean, sc, b), v = act(fma(x, sc, sh)), + post_add (one f32 add), rounded ONCE to bf16.
+ * Write set: the B * HW * C elements of y (and `partial`), nothing else. */
 int64_t x2i_groupnorm_scratch_floats(int32_t B, int32_t G);
 int x2i_groupnorm_nhwc_bf16(const void* x, void* y, int32_t B, int64_t HW, int32_t C, int32_t G, const void* weight,
                             const void* bias, float eps, int32_t act, const float* pre_add, const void* post_add,
@@ -260,7 +275,11 @@ int x2i_groupnorm_nhwc_bf16(const void* x, void* y, int32_t B, int64_t HW, int32
  * x2i_groupnorm_nhwc_from_moments_bf16 normalises x + pre_add with the group statistics derived from them (sum (x + v) = S1 + HW v,
  * sum (x + v)^2 = S2 + 2 v S1 + HW v^2) -- no statistics pass over x.  For ResnetBlock2D's norm2 in the ControlNeXt branch: its input is
  * conv1(...) + time_emb_proj(silu(temb)) (diffusers ResnetBlock2D; lightcontrol_flux.py:620-640, forward :741), and conv1's output depends
- * on the hint only, so its moments are taken once per hint and the per-step statistics cost nothing.  `partial` as above. */
+ * on the hint only, so its moments are taken once per hint and the per-step statistics cost nothing.  `partial` as above.
+ * x2i_groupnorm_moments_f32 writes the B * C * 2 f32 sums (per slab, then the 256 slabs one after the other: deterministic) and nothing else.  The
+ * from-moments entry points treat `moments` as an operand: per-channel moments with any pre_add, or the channel-QUAD moments of a conv epilogue
+ * (x2i_conv_desc.moments) without pre_add; the sums of a group are formed in f32 (one more cancelling step when |pre_add| >> |x|), then mean, var,
+ * rstd, apply, rounding and write set exactly as x2i_groupnorm_nhwc_bf16. */
 int64_t x2i_groupnorm_moments_scratch_floats(int32_t B, int32_t C);
 int x2i_groupnorm_moments_f32(const void* x, int32_t B, int64_t HW, int32_t C, float* moments, float* scratch, x2i_stream_t stream);
 int x2i_groupnorm_nhwc_from_moments_bf16(const void* x, void* y, int32_t B, int64_t HW, int32_t C, int32_t G, const void* weight,

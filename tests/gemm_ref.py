@@ -47,7 +47,7 @@ SENTINEL32 = 0x7F7F7F7F         # f32 bits of 3.39e38
 # the old style of check, kept here only to show what it misses (tests/test_gemm_ref_cpu.py): rel-L2 on a few sampled rows
 OLD_SAMPLED_BOUND = 1e-2
 
-ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_SILU = 0, 1, 2, 3
+ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_SILU, ACT_RELU = 0, 1, 2, 3, 4
 
 
 # ---------------------------------------------------------------------------------------------------------------- float64 helpers
@@ -71,6 +71,8 @@ def act_f64(x, act):
         return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
     if act == ACT_SILU:
         return x * torch.sigmoid(x)
+    if act == ACT_RELU:
+        return x.clamp_min(0.0)
     assert act == ACT_NONE, act
     return x
 
@@ -85,12 +87,14 @@ def dact_f64(x, act):
     if act == ACT_SILU:
         s = torch.sigmoid(x)
         return s * (1.0 + x * (1.0 - s))
+    if act == ACT_RELU:
+        return (x > 0).to(x.dtype)
     return torch.ones_like(x)
 
 
 def _act_bound(x, y, d, act):
     """bound on |act_f32(x~) - act(x)| for |x~ - x| <= d, y = act(x)"""
-    if act == ACT_NONE:
+    if act in (ACT_NONE, ACT_RELU):           # (ReLU is fmaxf(v, 0): exact, |max(a, 0) - max(b, 0)| <= |a - b|, no U_ACT term)
         return d
     return (dact_f64(x, act).abs() + d) * d + U_ACT * y.abs() + ACT_TAIL * x.abs()
 
@@ -110,11 +114,15 @@ def linear_f64(A, W, bias):
     return lin, mag
 
 
-def gemm_expect(A, W, bias=None, *, act=ACT_NONE, gate=None, res=None, act2=None, out_f32=False):
+def gemm_expect(A, W, bias=None, *, act=ACT_NONE, gate=None, res=None, act2=None, out_f32=False, bias2=None):
     """Expected outputs of x2i_gemm_bf16 for the rows A [m, K] of one batch item: W [N, K], bias [N] (bf16 or None), gate [N] f32 or None,
-    res [m, N] bf16 or None.  Returns (want, bound, delta) float64 [m, N] for C (delta: the f32 part of the bound), and (want2, bound2, delta2) for
+    res [m, N] bf16 or None, bias2 [N] f32 or None (x2i_gemm_args.bias2 of this item: added in front of the activation; its magnitude joins
+    the U_ACC term like the bias's).  Returns (want, bound, delta) float64 [m, N] for C (delta: the f32 part of the bound), and (want2, bound2, delta2) for
     C2 = act2(v) when act2 is not None."""
     lin, mag = linear_f64(A, W, bias)
+    if bias2 is not None:
+        lin += bias2.double()
+        mag += bias2.double().abs()
     d = U_ACC * mag
     del mag
     v = act_f64(lin, act)
