@@ -40,8 +40,12 @@ activations; bf16 / f32 -> float64 is exact).  u = U_F32 = 2^-24 below.
     E_m = (cpg + 3) u sum_c A_c / n, A_c = |S1_c| + HW |v_c|;  E_v = (cpg + 5) u sum_c Q_c / n + 2 |m| E_m + E_m^2 + u m^2 + u (|q / n| + m^2),
     Q_c = |S2_c| + 2 |v_c S1_c| + HW v_c^2 -- which carries the cancellation of the pre_add-dominant case.  rstd and apply as above.
 
-Constants: every allowance below is an operation count read off the code.  No GPU module drives this checker yet, so none of them carries a
-share measured on MI355X; the f32 stand-ins of tests/test_conv_ref_cpu.py stay inside every one of them (asserted there)."""
+Constants: every allowance below is an operation count read off the code; the f32 stand-ins of tests/test_conv_ref_cpu.py stay inside every
+one of them (asserted there).  Largest share used on MI355X (tests/test_conv_fp64_gpu.py, profiles/conv_fp64_gputest.log; |err| beyond the
+output's own rounding over the f32 allowance, or |err| / bound per moments entry), over every kernel form and the models' replayed launches:
+U_ACC: conv outputs 0.14 (gemm256c in either K order, eight-wave 256^2), 0.17 (gemm512c in either K order, 128^2), narrow 0.02, image 0.07;
+STEM_DEPTH 0.03; MOM_* per entry 0.11 (gemm256c, eight-wave), 0.09 (gemm512c), 0.12 (128^2), 0.03 (image conv); gn_moments_chain 0.20;
+GN_* direct 0.03 - 0.07 per operand kind, from per-channel moments 0.08 - 0.18, from channel-quad moments 0.13 - 0.23.  None was changed."""
 import math
 
 import torch

@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import conv_ref as R
 from tests.util import rel_l2, seeded
 
 pytestmark = pytest.mark.gpu
@@ -22,10 +23,11 @@ def _flat(o):
     return [t.float().flatten() for t in (o if isinstance(o, tuple) else (o,))]
 
 
-def _both(fn, tile_new=5256):
+def _both(fn, tile_new=5256, check=None):
     """fn() under conv_w4 = 1 and 0 -> (new, old, tile read-backs).  The new kernels run in the OTHER kernels' K order here (conv_korder = 0: the
     bit-identity claim); their product order (conv_korder = 1: a filter row's taps back to back, so their shifted re-reads hit L2) sums the same
-    products in another order and is checked against it with a tolerance: every output tensor of fn() within 2e-3 (rel-L2)."""
+    products in another order and is checked against it with a tolerance: every output tensor of fn() within 2e-3 (rel-L2) -- and, through
+    check(product-order result), against the float64 reference per element (tests/conv_ref.py): the other order shares none of its mistakes."""
     from x2i_amd import _lib
     out = []
     tiles = []
@@ -48,7 +50,24 @@ def _both(fn, tile_new=5256):
         _lib.set_option("gemm_min256", 128)
     for a, b in zip(_flat(prod), _flat(out[0])):
         assert float((a - b).norm() / b.norm().clamp_min(1e-30)) < 2e-3
+    if check is not None:
+        check(prod)
     return out[0], out[1], tiles
+
+
+def _fp64(name, x, w, b, g, N, B, **kw):
+    """check(...) of _both: every element of the conv output y (or of (y, moments): every moments entry too, 128-row blocks) against float64"""
+    def check(o):
+        y, mom = o if isinstance(o, tuple) else (o, None)
+        R.check_conv(R.Report(name), x, w, b, y, g, N, B, **kw).done()
+        if mom is not None:
+            want, bound = R.moments_expect(y.reshape(B, g.M, N), R.moments_depth(g.M, N, 128, blocks=kw_blocks(g.M, name)))
+            R.assert_entries(name + " moments", mom, want, bound)
+    return check
+
+
+def kw_blocks(M, name):
+    return (M + 511) // 512 * 4 if name.startswith("conv512") else None
 
 
 CASES = [
@@ -72,19 +91,22 @@ def test_conv_w4_bit_identical_to_eight_wave_form(Cin, Cout, KH, KW, s, p, H, W,
     b = bf(seeded((Cout,), 3))
     xn = x.permute(0, 2, 3, 1).contiguous().to(DEV)
     wp = w.permute(0, 2, 3, 1).reshape(Cout, -1).contiguous().to(DEV)
-    new, old, tiles = _both(lambda: ops.conv2d_nhwc(xn, wp, b.to(DEV), H, W, Cin, Cout, KH, KW, s, p))
+    g, bd = R.Geom(H, W, Cin, KH, KW, s, p), b.to(DEV)
+    new, old, tiles = _both(lambda: ops.conv2d_nhwc(xn, wp, b.to(DEV), H, W, Cin, Cout, KH, KW, s, p), check=_fp64("conv_w4", xn, wp, bd, g, Cout, B))
     assert tiles == [5256, 256], tiles           # the persistent four-wave kernel / the eight-wave kernel were really taken
     assert torch.equal(new, old)
     ref = F.conv2d(x.float(), w.float(), b.float(), stride=s, padding=p)
     assert rel_l2(new.permute(0, 3, 1, 2), ref) < 1e-2
     # ReLU + a per-batch f32 bias (ControlNeXt mid block; the time-embedding term)
     b2 = seeded((B, Cout), 4)
-    new, old, tiles = _both(lambda: ops.conv2d_nhwc(xn, wp, b.to(DEV), H, W, Cin, Cout, KH, KW, s, p, act=ops.ACT_RELU, bias2=b2.to(DEV)))
+    new, old, tiles = _both(lambda: ops.conv2d_nhwc(xn, wp, b.to(DEV), H, W, Cin, Cout, KH, KW, s, p, act=ops.ACT_RELU, bias2=b2.to(DEV)),
+                            check=_fp64("conv_w4 relu + bias2", xn, wp, bd, g, Cout, B, act=R.ACT_RELU, bias2=b2.to(DEV)))
     assert tiles == [5256, 256] and torch.equal(new, old)
     assert rel_l2(new.permute(0, 3, 1, 2), torch.relu(ref + b2[:, :, None, None])) < 1e-2
     # residual add (ResnetBlock2D's conv2 + shortcut), also in place
     res = bf(seeded(tuple(ref.shape), 5)).permute(0, 2, 3, 1).contiguous().to(DEV)
-    new, old, tiles = _both(lambda: ops.conv2d_nhwc(xn, wp, b.to(DEV), H, W, Cin, Cout, KH, KW, s, p, res=res))
+    new, old, tiles = _both(lambda: ops.conv2d_nhwc(xn, wp, b.to(DEV), H, W, Cin, Cout, KH, KW, s, p, res=res),
+                            check=_fp64("conv_w4 res", xn, wp, bd, g, Cout, B, res_store=res))
     assert tiles == [5256, 256] and torch.equal(new, old)
     assert rel_l2(new.permute(0, 3, 1, 2), ref + res.float().permute(0, 3, 1, 2).cpu()) < 1e-2
 
@@ -102,7 +124,8 @@ def test_conv_w4_epilogue_moments_bit_identical(Cin, Cout, H, W, B):
             mom = torch.full((B, Cout, 2), 7.0, device=DEV)
             y = ops.conv2d_nhwc(x, wp, b, H, W, Cin, Cout, 3, 3, 1, 1, moments=mom, **kw)
             return y, mom
-        (yn, mn), (yo, mo), tiles = _both(run)
+        (yn, mn), (yo, mo), tiles = _both(run, check=_fp64("conv_w4 moments", x, wp, b, R.Geom(H, W, Cin, 3, 3, 1, 1), Cout, B,
+                                                           res_store=kw.get("res")))
         assert tiles == [5256, 256]
         assert torch.equal(yn, yo) and torch.equal(mn, mo)
         q = yn.float().reshape(B, H * W, Cout // 4, 4)
@@ -113,9 +136,17 @@ def test_conv_w4_epilogue_moments_bit_identical(Cin, Cout, H, W, B):
     def run2():
         mom = torch.zeros((B, Cout, 2), device=DEV)
         ops.conv2d_nhwc(x, wp, b, H, W, Cin, Cout, 3, 3, 1, 1, moments=mom)
-        ops.conv2d_nhwc(x, wp, b, H, W, Cin, Cout, 3, 3, 1, 1, moments=mom, moments_accumulate=True)
-        return mom
-    mn, mo, _ = _both(run2)
+        y = ops.conv2d_nhwc(x, wp, b, H, W, Cin, Cout, 3, 3, 1, 1, moments=mom, moments_accumulate=True)
+        return y, mom
+
+    def check2(o):
+        y, mom = o
+        g = R.Geom(H, W, Cin, 3, 3, 1, 1)
+        R.check_conv(R.Report("conv_w4 accumulate"), x, wp, b, y, g, Cout, B).done()
+        want, bound = R.moments_expect(y.reshape(B, g.M, Cout), R.moments_depth(g.M, Cout, 128, accumulate=True))
+        # two launches, each within `bound` of the sums; the second adds onto what the first left: one rounding of at most |want| + bound
+        R.assert_entries("conv_w4 moments accumulated twice", mom, 2 * want, 2 * bound + R.U_F32 * (want.abs() + bound))
+    (_, mn), (_, mo), _ = _both(run2, check=check2)
     assert torch.equal(mn, mo)
 
 
@@ -144,7 +175,18 @@ def test_conv_w4_four_phase_upsample_form(C, Co, H, W):
                                 c_offset=(py * 2 * W + px) * Co, c_batch_stride=4 * H * W * Co, out_row_pitch=4 * W * Co, moments=mom,
                                 moments_accumulate=(py, px) != (0, 0))
         return y, mom
-    (yn, mn), (yo, mo), tiles = _both(run)
+    def check(o):
+        y, mom = o
+        for py in (0, 1):
+            for px in (0, 1):
+                g = R.Geom(H, W, C, 2, 2, 1, 1 - py, pad_w=1 - px, out_w=W, out_h=H)
+                R.check_conv(R.Report(f"phase ({py}, {px})"), xn, wp[py][px], pb, y, g, Co, B, ldc=2 * Co, c_offset=(py * 2 * W + px) * Co,
+                             c_batch_stride=4 * H * W * Co, out_row_pitch=4 * W * Co).done()
+        # four accumulating launches from zero: each adds its own sums (depth with accumulate) and rounds onto what is there, which is at most
+        # the whole sum of magnitudes -- three more roundings relative to it
+        want, bound = R.moments_expect(y.reshape(B, 4 * H * W, Co), R.moments_depth(H * W, Co, 128, accumulate=True) + 3)
+        R.assert_entries("four-phase moments", mom, want, bound)
+    (yn, mn), (yo, mo), tiles = _both(run, check=check)
     assert tiles == [5256, 256]
     assert torch.equal(yn, yo) and torch.equal(mn, mo)
     ref = F.conv2d(F.interpolate(x.float(), scale_factor=2.0, mode="nearest"), conv.weight.float().cpu(), conv.bias.float().cpu(), padding=1)
@@ -203,7 +245,9 @@ def test_conv512_bit_identical_to_the_128_tile_kernel(Cin, Cout, KH, KW, s, p, H
             mom = torch.zeros((B, Cout, 2), device=DEV)
             y = ops.conv2d_nhwc(xn, wp, b.to(DEV), H, W, Cin, Cout, KH, KW, s, p, moments=mom, **kw)
             return y, mom
-        (yn, mn), (yo, mo), tiles = _both128(run)
+        ck = dict(kw, res_store=kw["res"]) if "res" in kw else dict(kw)
+        ck.pop("res", None)
+        (yn, mn), (yo, mo), tiles = _both(run, tile_new=5512, check=_fp64("conv512", xn, wp, b.to(DEV), R.Geom(H, W, Cin, KH, KW, s, p), Cout, B, **ck))
         assert tiles == [5512, 128], tiles
         assert torch.equal(yn, yo)                               # same MFMA, same k order, same epilogue arithmetic
         assert rel_l2(yn.permute(0, 3, 1, 2), want) < 1e-2

@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import vae as OV
+from tests import conv_ref as R
 from tests.util import rel_l2, seeded
 
 pytestmark = pytest.mark.gpu
@@ -90,7 +91,7 @@ def test_conv_epilogue_channel_moments(C, Co, H, W, res):
     """x2i_conv_desc.moments: the conv epilogue's (sum, sum of squares) of the bf16 outputs per channel quad -- both tile kernels (Cout = 128: 128^2,
     Cout >= 256 with >= 1024 pixels: 256^2), ragged last tiles, with and without the residual epilogue, accumulation over two launches -- against the
     sums of the stored tensor, bit-reproducible, and feeding groupnorm_nhwc_from_moments = groupnorm_nhwc of the same tensor."""
-    from x2i_amd import ops
+    from x2i_amd import _lib, ops
     B = 2
     x = bf(seeded((B, H, W, C), 21)).to(DEV)
     w = bf(seeded((Co, 3, 3, C), 22) / 24).reshape(Co, -1).contiguous().to(DEV)
@@ -98,6 +99,13 @@ def test_conv_epilogue_channel_moments(C, Co, H, W, res):
     r = bf(seeded((B, H, W, Co), 24)).to(DEV) if res else None
     mom = torch.full((B, Co, 2), 7.0, device=DEV)
     y = ops.conv2d_nhwc(x, w, b, H, W, C, Co, 3, 3, 1, 1, res=r, moments=mom)
+    tile = _lib.get_option("last_gemm_tile")
+    # every output element and every moments entry against float64 (tests/conv_ref.py)
+    g = R.Geom(H, W, C, 3, 3, 1, 1)
+    R.check_conv(R.Report("conv with moments"), x, w, b, y, g, Co, B, res_store=r).done()
+    rb_ = 64 if tile == 128 else 128
+    m_want, m_bound = R.moments_expect(y.reshape(B, H * W, Co), R.moments_depth(H * W, Co, rb_))
+    R.assert_entries("conv epilogue moments", mom, m_want, m_bound)
     y0 = ops.conv2d_nhwc(x, w, b, H, W, C, Co, 3, 3, 1, 1, res=r)
     assert torch.equal(y, y0)                                             # the outputs do not change
     yf = y.float().reshape(B, H * W, Co)
@@ -111,10 +119,19 @@ def test_conv_epilogue_channel_moments(C, Co, H, W, res):
     assert torch.equal(mom, mom2)                                         # fixed summation order
     ops.conv2d_nhwc(x, w, b, H, W, C, Co, 3, 3, 1, 1, res=r, moments=mom2, moments_accumulate=True)
     assert float((mom2 - 2 * want).abs().max() / want.abs().max()) < 4e-5
+    m_want, m_bound = R.moments_expect(y.reshape(B, H * W, Co), R.moments_depth(H * W, Co, rb_, accumulate=True), prev=mom)
+    R.assert_entries("conv epilogue moments, accumulated", mom2, m_want, m_bound)
     gw, gb = bf(1 + 0.1 * seeded((Co,), 25)).to(DEV), bf(0.1 * seeded((Co,), 26)).to(DEV)
     a1 = ops.groupnorm_nhwc_from_moments(y, mom, gw, gb, 32, 1e-6, act=3)
     a0 = ops.groupnorm_nhwc(y, gw, gb, 32, 1e-6, act=3)
     assert rel_l2(a1, a0) < 2e-3
+    y3 = y.reshape(B, H * W, Co)
+    rep = R.Report("groupnorm from the epilogue moments")
+    R.check_groupnorm(rep, y3, a1.reshape(B, H * W, Co), gw, gb, 32, 1e-6, act=R.ACT_SILU, moments=mom, W=W)
+    rep.done()
+    rep = R.Report("groupnorm of the conv output")
+    R.check_groupnorm(rep, y3, a0.reshape(B, H * W, Co), gw, gb, 32, 1e-6, act=R.ACT_SILU, W=W)
+    rep.done()
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout", [(2, 9, 21, 128, 3), (1, 64, 80, 128, 3), (1, 37, 16, 64, 4), (3, 5, 130, 32, 1), (1, 130, 70, 96, 2)])
@@ -133,6 +150,11 @@ def test_conv3x3_narrow_output(B, H, W, Cin, Cout):
     ref = F.conv2d(x.float(), w.float(), b.float(), padding=1)
     assert rel_l2(y[..., :Cout].permute(0, 3, 1, 2), ref) < 6e-3
     assert float(y[..., Cout:4].float().abs().max() if Cout < 4 else 0.0) == 0.0 and bool((y[..., 4:] == 5.0).all())   # zeros behind Cout, the rest untouched
+    # every element against float64, the channels behind the kernel's four still the sentinel (tests/conv_ref.py)
+    yp = R.poison_(torch.empty((B, H, W, 8), device=DEV, dtype=torch.bfloat16))
+    ops.conv3x3_narrow(xn, wp, b.to(DEV), Cout, out=yp, ldy=8)
+    assert torch.equal(yp[..., :4], y[..., :4])
+    R.check_narrow(R.Report("narrow conv"), xn, wp, b.to(DEV), yp, Cout).done()
     w8 = torch.zeros((8, 9 * Cin), dtype=torch.bfloat16, device=DEV)
     w8[:Cout] = wp
     b8 = torch.zeros((8,), dtype=torch.bfloat16, device=DEV)
@@ -142,13 +164,18 @@ def test_conv3x3_narrow_output(B, H, W, Cin, Cout):
         assert rel_l2(y[..., :Cout], g[..., :Cout]) < 6e-3
     y2 = ops.conv3x3_narrow(xn, wp, None, Cout)
     assert y2.shape == (B, H, W, 4) and rel_l2(y2[..., :Cout].permute(0, 3, 1, 2), ref - b.float().view(1, -1, 1, 1)) < 6e-3
+    R.check_narrow(R.Report("narrow conv, no bias"), xn, wp, None, y2, Cout).done()
 
 
 def test_groupnorm_four_channels_per_group():
     from x2i_amd import ops
     x, w, b = bf(seeded((2, 128, 9, 11), 4, 2.0) + 0.2), bf(1 + 0.1 * seeded((128,), 5)), bf(0.1 * seeded((128,), 6))
-    out = ops.groupnorm_nhwc(x.permute(0, 2, 3, 1).contiguous().to(DEV), w.to(DEV), b.to(DEV), 32, 1e-6, act=3)
+    xn = x.permute(0, 2, 3, 1).contiguous().to(DEV)
+    out = ops.groupnorm_nhwc(xn, w.to(DEV), b.to(DEV), 32, 1e-6, act=3)
     assert rel_l2(out.permute(0, 3, 1, 2), F.silu(F.group_norm(x.float(), 32, w.float(), b.float(), 1e-6))) < 5e-3
+    rep = R.Report("groupnorm, four channels per group")
+    R.check_groupnorm(rep, xn.reshape(2, 99, 128), out.reshape(2, 99, 128), w.to(DEV), b.to(DEV), 32, 1e-6, act=R.ACT_SILU, W=11)
+    rep.done()
 
 
 def test_softmax_rows_and_batched_weight_gemm():
