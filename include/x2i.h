@@ -19,7 +19,8 @@
  *     x2i_groupnorm_scratch_floats, x2i_streamk_workspace_bytes (x2i_gemm_args.workspace, x2i_attention_vp_ws_bf16).  Process-wide state, all of it
  *     mutex-protected: the option table below and a per-kernel "dynamic LDS size already raised" cache.
  *   - ABI version 5 (x2i_abi_version; 5 adds x2i_attention_vp_ws_bf16 -- no struct changed; x2i_conv3x3_image_bf16 and x2i_vae_posterior_bf16
- *     (the VAE encoder) were added under the same version: new entry points only, no struct or existing signature changed; 4 appended `w_group` to x2i_gemm_args, 0 = what version 3 did, and added the *_grouped entry points).  Since version 1: x2i_gemm_args grew `workspace` / `workspace_bytes`, x2i_qkv_desc `q_scale`
+ *     (the VAE encoder), the ControlNeXt backward and x2i_flow_match_noise_bf16 / x2i_mse_loss_grad_bf16 / x2i_mse_loss_workspace_floats (the head of
+ *     the LightControl training step) were added under the same version: new entry points only, no struct or existing signature changed; 4 appended `w_group` to x2i_gemm_args, 0 = what version 3 did, and added the *_grouped entry points).  Since version 1: x2i_gemm_args grew `workspace` / `workspace_bytes`, x2i_qkv_desc `q_scale`
  *     and x2i_conv_desc a ninth field (version 2); version 3 re-defines that field as `pad_w_p1` (0 = same padding as `pad`, so that a
  *     zero-initialised descriptor means what it meant in version 1), appends `out_w`, `out_h`, `out_row_pitch` (0 = computed / dense) and the `moments` fields (NULL = off) to it, gives `up` the value 2, and appends `vt_perm` to x2i_qkv_desc (0 = the old layout).  A caller built against another version must not load this
  *     library (x2i_amd/_lib.py checks).
@@ -580,6 +581,24 @@ int x2i_groupnorm_nhwc_bwd_bf16(const void* x, const void* dy, const void* weigh
  * act_in(x[b][k]) (act_in: none or SiLU), db f32 [N] (+)= sum_b dy[b][n] or NULL; dy f32 [B][N], x f32 [B][K] contiguous. */
 int x2i_linear_wgrad_f32(const float* dy, const float* x, float* dw, float* db, int32_t B, int32_t N, int32_t K, int32_t act_in, int32_t accumulate,
                          x2i_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Head of the LightControl training step (lightcontrol/train_lightcontrol.py:706-714, :756-762; csrc/train.hip; driven by
+ * x2i_amd/lightcontrol_step.py).  Added under ABI version 5: new entry points only.
+ *
+ * Flow-matching noising, written in FLUX's packed token layout: x, noise bf16 NCHW [B][C][h][w] (C, h, w even), sigma f32 [B];
+ * noisy, target bf16 [B][(h/2)(w/2)][4 C] with packed[b][i (w/2) + j][4 c + 2 dy + dx] = t[b][c][2 i + dy][2 j + dx] (_pack_latents, :708-714).
+ * The arithmetic is the reference's, which runs on bf16 tensors: s = bf16(sigma[b]), a = bf16(1 - s), noisy = bf16(bf16(a x) + bf16(s noise)),
+ * target = bf16(noise - x); every operation is evaluated in f32 and rounded to nearest even -- bit-identical to the torch expression. */
+int x2i_flow_match_noise_bf16(const void* x, const void* noise, const float* sigma, void* noisy, void* target, int32_t B, int32_t C, int32_t h, int32_t w,
+                              x2i_stream_t stream);
+/* Mean-squared-error loss with its gradient (:758-762, weighting "none") on n contiguous bf16 elements (n % 8 == 0): workspace f32
+ * [x2i_mse_loss_workspace_floats(n)] receives one partial sum of (pred - target)^2 per workgroup (fixed order, no atomics: two launches are
+ * bit-identical); x2i_reduce_rows_f32 with np = that count, len = 1 and alpha = 1 / n turns them into the mean.  d_pred = bf16(2 (pred - target) / n
+ * * grad_scale) (grad_scale: gradient accumulation; a power of two scales the gradient exactly).  d_pred may alias neither input. */
+int x2i_mse_loss_workspace_floats(int64_t n, int64_t* floats);
+int x2i_mse_loss_grad_bf16(const void* pred, const void* target, void* d_pred, int64_t n, float grad_scale, float* workspace, int64_t workspace_floats,
+                           x2i_stream_t stream);
 
 #ifdef __cplusplus
 }

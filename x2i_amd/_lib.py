@@ -124,6 +124,9 @@ SIGNATURES = {
     "x2i_groupnorm_bwd_workspace_floats": [_i32, _i64, _i32, _i32, C.POINTER(C.c_int64)],
     "x2i_groupnorm_nhwc_bwd_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _i32, _i32, _vp, _i64, _vp],
     "x2i_linear_wgrad_f32": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "x2i_flow_match_noise_bf16": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "x2i_mse_loss_workspace_floats": [_i64, C.POINTER(C.c_int64)],
+    "x2i_mse_loss_grad_bf16": [_vp, _vp, _vp, _i64, _f32, _vp, _i64, _vp],
     "x2i_proj_conv5x5_packed_bf16": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "x2i_proj_layer_mean_bf16": [_vp, _vp, _vp, _i32, _i32, _i64, _vp],
     "x2i_seq_mean_f32": [_vp, _vp, _i32, _i32, _i32, _vp],

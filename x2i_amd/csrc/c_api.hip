@@ -495,4 +495,15 @@ int x2i_linear_wgrad_f32(const float* dy, const float* x, float* dw, float* db, 
   return x2i_launch_linear_wgrad(dy, x, dw, db, B, N, K, act_in, accumulate, (hipStream_t)stream);
 }
 
+// head of the LightControl training step (train.hip)
+int x2i_flow_match_noise_bf16(const void* x, const void* noise, const float* sigma, void* noisy, void* target, int32_t B, int32_t C, int32_t h, int32_t w,
+                              x2i_stream_t stream) {
+  return x2i_launch_flow_match_noise(x, noise, sigma, noisy, target, B, C, h, w, (hipStream_t)stream);
+}
+int x2i_mse_loss_workspace_floats(int64_t n, int64_t* floats) { return ws_query(x2i_mse_loss_workspace(n), floats, "mse_loss_workspace_floats"); }
+int x2i_mse_loss_grad_bf16(const void* pred, const void* target, void* d_pred, int64_t n, float grad_scale, float* workspace, int64_t workspace_floats,
+                           x2i_stream_t stream) {
+  return x2i_launch_mse_loss_grad(pred, target, d_pred, n, grad_scale, workspace, workspace_floats, (hipStream_t)stream);
+}
+
 }  // extern "C"

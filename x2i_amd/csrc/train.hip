@@ -917,9 +917,146 @@ __global__ __launch_bounds__(256) void adamw_kernel(bf16_t* __restrict__ p, cons
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Head of the LightControl training step (lightcontrol/train_lightcontrol.py:706-714, :756-762).
+//
+// Flow-matching noising on NCHW latents, written straight into FLUX's packed token layout
+//   packed[b][i * (w / 2) + j][4 c + 2 dy + dx] = t[b][c][2 i + dy][2 j + dx]:
+// noisy = bf16(bf16(a x) + bf16(s n)), target = bf16(n - x) with s = bf16(sigma[b]), a = bf16(1 - s) -- the reference does this arithmetic on
+// bf16 tensors, so every operation is an f32 evaluation rounded to nearest even, and the explicit roundings between them keep the compiler
+// from contracting a product into the sum.  A work item is a channel PAIR of TJ neighbouring tokens of one packed row: it reads 2 * TJ
+// consecutive latents of four image rows (channel c and c + 1, row 2 i and 2 i + 1; 16 bytes each when W8) and writes 16 bytes per token; the
+// channel pair is the fastest index, so the C / 2 lanes of a token write its 8 C bytes contiguously.
+__device__ __forceinline__ float rbf(float v) { return bf16_to_f32(f32_to_bf16(v)); }
+template <bool W8>
+__global__ __launch_bounds__(256) void flow_match_noise_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ nz, const float* __restrict__ sigma,
+                                                               bf16_t* __restrict__ noisy, bf16_t* __restrict__ target, int C, int h, int w,
+                                                               long long total) {
+  constexpr int TJ = W8 ? 4 : 1, NE = 2 * TJ;
+  const int c2 = C >> 1, h2 = h >> 1, w2 = w >> 1, njg = w2 / TJ;
+  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+    const int cp = (int)(idx % c2);
+    long long r = idx / c2;
+    const int jg = (int)(r % njg);
+    r /= njg;
+    const int i = (int)(r % h2), b = (int)(r / h2);
+    const float s = rbf(sigma[b]), a = rbf(1.f - s);
+    float yv[2][2][NE], tv[2][2][NE];   // [channel of the pair][dy][column]
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc) {
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy) {
+        const long long off = (((long long)b * C + 2 * cp + cc) * h + 2 * i + dy) * w + (long long)jg * NE;
+        float xv[NE], nv[NE];
+        if constexpr (W8) {
+          unpack8(*(const bf16x8_t*)(x + off), xv);
+          unpack8(*(const bf16x8_t*)(nz + off), nv);
+        } else {
+          const uint32_t xu = *(const uint32_t*)(x + off), nu = *(const uint32_t*)(nz + off);
+          xv[0] = __uint_as_float(xu << 16); xv[1] = __uint_as_float(xu & 0xffff0000u);
+          nv[0] = __uint_as_float(nu << 16); nv[1] = __uint_as_float(nu & 0xffff0000u);
+        }
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+          yv[cc][dy][e] = rbf(a * xv[e]) + rbf(s * nv[e]);
+          tv[cc][dy][e] = nv[e] - xv[e];
+        }
+      }
+    }
+    const long long tok = ((long long)b * h2 + i) * w2 + (long long)jg * TJ;
+#pragma unroll
+    for (int tj = 0; tj < TJ; ++tj) {
+      float yo[8], to[8];
+#pragma unroll
+      for (int cc = 0; cc < 2; ++cc) {
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+#pragma unroll
+          for (int dx = 0; dx < 2; ++dx) {
+            yo[4 * cc + 2 * dy + dx] = yv[cc][dy][2 * tj + dx];
+            to[4 * cc + 2 * dy + dx] = tv[cc][dy][2 * tj + dx];
+          }
+        }
+      }
+      const long long o = (tok + tj) * 4 * C + 8 * cp;
+      *(bf16x8_t*)(noisy + o) = pack8(yo);    // (the one rounding of the sum / the difference)
+      *(bf16x8_t*)(target + o) = pack8(to);
+    }
+  }
+}
+
+// MSE loss of the flow-matching step and its gradient (:758-762, weighting "none"): workgroup `blk` owns the 8-element vectors
+// [blk * per_block, (blk + 1) * per_block) of the flat tensors, a thread every 256th of them; partial[blk] = sum (pred - target)^2 in a fixed order
+// (per thread one fmaf chain over its elements, DPP wave sum, the four waves' sums added in order through LDS; x2i_reduce_rows_f32 finishes: no
+// atomics), d_pred = bf16((pred - target) * scale), scale = 2 / n * grad_scale.
+constexpr int MSE_VEC_PER_BLOCK = 512;   // vectors a workgroup owns until the grid reaches MSE_MAX_BLOCKS
+constexpr int MSE_MAX_BLOCKS = 1024;
+__global__ __launch_bounds__(256) void mse_loss_grad_kernel(const bf16_t* __restrict__ pred, const bf16_t* __restrict__ target, bf16_t* __restrict__ d_pred,
+                                                            long long n8, long long per_block, float scale, float* __restrict__ partial) {
+  __shared__ float red[4];
+  const long long lo = (long long)blockIdx.x * per_block, hi = min(n8, lo + per_block);
+  float acc = 0.f;
+  for (long long v = lo + threadIdx.x; v < hi; v += 256) {
+    float p[8], t[8];
+    unpack8(*(const bf16x8_t*)(pred + v * 8), p);
+    unpack8(*(const bf16x8_t*)(target + v * 8), t);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d = p[j] - t[j];
+      acc = fmaf(d, d, acc);
+      p[j] = d * scale;
+    }
+    *(bf16x8_t*)(d_pred + v * 8) = pack8(p);
+  }
+  acc = wave_sum_lane63(acc);
+  if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 bool al16p(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 }  // namespace
+
+int x2i_launch_flow_match_noise(const void* x, const void* noise, const float* sigma, void* noisy, void* target, int B, int C, int h, int w,
+                                hipStream_t stream) {
+  if (!x || !noise || !sigma || !noisy || !target || B <= 0 || C <= 0 || h <= 0 || w <= 0)
+    return x2i_set_error(X2I_ERR_ARG, "flow_match_noise: bad argument");
+  if (C % 2 || h % 2 || w % 2) return x2i_set_error(X2I_ERR_SHAPE, "flow_match_noise: C, h and w must be even (2 x 2 patches, channel pairs)");
+  if (!al16p(x) || !al16p(noise) || !al16p(noisy) || !al16p(target)) return x2i_set_error(X2I_ERR_ALIGN, "flow_match_noise: 16-byte aligned tensors");
+  const bool w8 = w % 8 == 0;
+  const long long total = (long long)B * (h / 2) * (w8 ? w / 8 : w / 2) * (C / 2);
+  const long long blocks = (total + 255) / 256;
+  const dim3 grid((unsigned)(blocks < 8192 ? blocks : 8192));
+  if (w8)
+    hipLaunchKernelGGL(flow_match_noise_kernel<true>, grid, dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)noise, sigma, (bf16_t*)noisy,
+                       (bf16_t*)target, C, h, w, total);
+  else
+    hipLaunchKernelGGL(flow_match_noise_kernel<false>, grid, dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)noise, sigma, (bf16_t*)noisy,
+                       (bf16_t*)target, C, h, w, total);
+  return x2i_check_launch("flow_match_noise");
+}
+
+// number of workgroups (= partial sums) of x2i_launch_mse_loss_grad for n elements; -1: a size the launcher refuses
+long long x2i_mse_loss_workspace(long long n) {
+  if (n <= 0 || n % 8) return -1;
+  const long long n8 = n / 8, blocks = (n8 + MSE_VEC_PER_BLOCK - 1) / MSE_VEC_PER_BLOCK;
+  return blocks < MSE_MAX_BLOCKS ? blocks : MSE_MAX_BLOCKS;
+}
+
+int x2i_launch_mse_loss_grad(const void* pred, const void* target, void* d_pred, long long n, float grad_scale, float* ws, long long ws_floats,
+                             hipStream_t stream) {
+  if (!pred || !target || !d_pred || !ws) return x2i_set_error(X2I_ERR_ARG, "mse_loss_grad: null pointer");
+  const long long blocks = x2i_mse_loss_workspace(n);
+  if (blocks < 0) return x2i_set_error(X2I_ERR_SHAPE, "mse_loss_grad: n must be a positive multiple of 8");
+  if (ws_floats < blocks) return x2i_set_error(X2I_ERR_ARG, "mse_loss_grad: workspace smaller than x2i_mse_loss_workspace_floats says");
+  if (!al16p(pred) || !al16p(target) || !al16p(d_pred)) return x2i_set_error(X2I_ERR_ALIGN, "mse_loss_grad: 16-byte aligned tensors");
+  const long long n8 = n / 8, per_block = (n8 + blocks - 1) / blocks;
+  const float scale = (float)(2.0 / (double)n) * grad_scale;
+  hipLaunchKernelGGL(mse_loss_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t*)pred, (const bf16_t*)target, (bf16_t*)d_pred, n8,
+                     per_block, scale, ws);
+  return x2i_check_launch("mse_loss_grad");
+}
 
 int x2i_launch_conv5x5_wgrad(const void* x, const void* dy, float* partial, int B, int C, int S, int H, hipStream_t stream) {
   if (!x || !dy || !partial || B <= 0 || C <= 0 || S <= 0 || H <= 0 || H % 8) return x2i_set_error(X2I_ERR_ARG, "conv5x5_wgrad: bad argument (H %% 8 == 0)");

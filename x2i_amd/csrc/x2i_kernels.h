@@ -101,6 +101,12 @@ int x2i_launch_attention_bwd(const void* Q, const void* K, const void* V, const 
                              int have_lse, hipStream_t stream);
 int x2i_launch_attention_bwd_prep(const void* dO, long long do_bs, int lddo, const void* O, long long o_bs, int ldo, float* Dv, int B, int H,
                                   int S, int Spad, hipStream_t stream);
+/* ---- head of the LightControl training step (train.hip); the workspace query returns -1 for a size the launcher refuses */
+int x2i_launch_flow_match_noise(const void* x, const void* noise, const float* sigma, void* noisy, void* target, int B, int C, int h, int w,
+                                hipStream_t stream);
+long long x2i_mse_loss_workspace(long long n);
+int x2i_launch_mse_loss_grad(const void* pred, const void* target, void* d_pred, long long n, float grad_scale, float* ws, long long ws_floats,
+                             hipStream_t stream);
 
 /* ---- backward kernels of the ControlNeXt control nets (conv_bwd.hip); the workspace queries return -1 for a shape the launcher refuses */
 long long x2i_conv_wgrad_workspace(int B, int OH, int OW, int Cin, int Cout, int KH, int KW);

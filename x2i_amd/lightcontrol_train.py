@@ -2,8 +2,9 @@
 
 The reference trains only its 19 `ControlNeXtModel`s (a ModuleList; 6.49 M parameters each) behind a frozen FLUX.1-dev transformer, with
 `clip_grad_norm_` over `controlnet.parameters()` and AdamW.  This is the counterpart of `ProjectorTrainer` (x2i_amd/train.py) for that step:
-forward with saved activations, the backward of every net from d loss / d control output, and the optimizer.  Wiring it to the transformer's
-activation-gradient chain is the caller's business: `backward` takes the gradient in the form `forward_nhwc(add_into=...)` writes the output.
+forward with saved activations, the backward of every net from d loss / d control output, and the optimizer.  `backward` / `backward_net` take
+the gradient in the form `forward_nhwc(add_into=...)` writes the output; x2i_amd/lightcontrol_step.py wires `backward_net` to the injection
+points of the transformer's activation-gradient chain (the whole step, loss to AdamW).
 
 Launches of the backward ("ControlNeXt backward"):
   * weight gradients: x2i_conv_wgrad_bf16 for every conv with Cin >= 64 (the 3x3, the 1x1 shortcut and the 2x2 stride-2 projection),
@@ -204,8 +205,17 @@ class ControlNeXtTrainer:
         like forward_nhwc's add_into (element offset, batch stride, row stride ld)."""
         if self.saved is None:
             raise RuntimeError("ControlNeXtTrainer.backward: call forward first")
-        for i, (net, sv, d_out) in enumerate(zip(self.nets, self.saved, d_outs)):
-            self._backward_net(i, net, sv, d_out, offset, batch_stride, ld)
+        for i, d_out in zip(range(len(self.nets)), d_outs):
+            self.backward_net(i, d_out, offset, batch_stride, ld)
+
+    @torch.no_grad()
+    def backward_net(self, i, d_out, offset=0, batch_stride=None, ld=None):
+        """backward() for net i alone, from d loss / d (its control output) addressed the same way.  The transformer's gradient chain calls this
+        at injection i with its residual-stream gradient in place (DistillBackward.backward(on_injection=...): offset = St D, batch stride
+        S D, row stride D); d_out is read by the launches enqueued here and may be overwritten by whatever the caller enqueues next."""
+        if self.saved is None:
+            raise RuntimeError("ControlNeXtTrainer.backward_net: call forward first")
+        self._backward_net(i, self.nets[i], self.saved[i], d_out, offset, batch_stride, ld)
 
     def _backward_net(self, i, net, sv, d_out, offset, batch_stride, ld):
         def g(name):

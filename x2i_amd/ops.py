@@ -1036,3 +1036,49 @@ def linear_wgrad(dy, x, dw, db, act_in=ACT_NONE, accumulate=False):
     check(_lib.load().x2i_linear_wgrad_f32(_p(dy.contiguous()), _p(x.contiguous()), _p(dw), _p(db), B, N, x.shape[1], act_in, 1 if accumulate else 0,
                                            _stream()), "linear_wgrad")
     return dw
+
+
+# ---------------------------------------------------------------------------------------------------- head of the LightControl training step
+def flow_match_noise(x, noise, sigma, noisy=None, target=None):
+    """Flow-matching noising of NCHW bf16 latents x [B, C, h, w] with noise (same shape) at sigma f32 [B], in FLUX's packed token layout
+    (include/x2i.h: x2i_flow_match_noise_bf16): returns (noisy, target), both bf16 [B, (h/2)(w/2), 4C]; noisy = (1 - sigma) x + sigma noise
+    and target = noise - x with the reference's bf16 roundings."""
+    _req(x, torch.bfloat16, "x")
+    _req(noise, torch.bfloat16, "noise")
+    _req(sigma, torch.float32, "sigma")
+    B, Cc, h, w = x.shape
+    if noise.shape != x.shape or sigma.numel() != B or not x.is_contiguous() or not noise.is_contiguous() or not sigma.is_contiguous():
+        raise _lib.X2IError("flow_match_noise: contiguous x, noise [B, C, h, w] and sigma [B]")
+    shape = (B, (h // 2) * (w // 2), 4 * Cc)
+    noisy = torch.empty(shape, device=x.device, dtype=torch.bfloat16) if noisy is None else noisy
+    target = torch.empty(shape, device=x.device, dtype=torch.bfloat16) if target is None else target
+    if tuple(noisy.shape) != shape or tuple(target.shape) != shape or not noisy.is_contiguous() or not target.is_contiguous():
+        raise _lib.X2IError("flow_match_noise: noisy / target must be contiguous [B, (h/2)(w/2), 4C]")
+    _req(noisy, torch.bfloat16, "noisy")
+    _req(target, torch.bfloat16, "target")
+    check(_lib.load().x2i_flow_match_noise_bf16(_p(x), _p(noise), _p(sigma), _p(noisy), _p(target), B, Cc, h, w, _stream()), "flow_match_noise")
+    return noisy, target
+
+
+def mse_loss_workspace_floats(n):
+    return _query(_lib.load().x2i_mse_loss_workspace_floats, n)
+
+
+def mse_loss_grad(pred, target, grad_scale=1.0, d_pred=None, loss=None):
+    """loss f32 [1] = mean((pred - target)^2) and d_pred = bf16(2 (pred - target) / n * grad_scale) for contiguous bf16 tensors of n elements
+    (include/x2i.h: x2i_mse_loss_grad_bf16; the per-workgroup partial sums are finished by reduce_rows: deterministic).  Returns (loss, d_pred)."""
+    lib = _lib.load()
+    _req(pred, torch.bfloat16, "pred")
+    _req(target, torch.bfloat16, "target")
+    n = pred.numel()
+    if target.shape != pred.shape or not pred.is_contiguous() or not target.is_contiguous():
+        raise _lib.X2IError("mse_loss_grad: pred and target must be contiguous and of one shape")
+    d_pred = torch.empty_like(pred) if d_pred is None else d_pred
+    if d_pred.shape != pred.shape or d_pred.dtype != torch.bfloat16 or not d_pred.is_contiguous():
+        raise _lib.X2IError("mse_loss_grad: d_pred must be a contiguous bf16 tensor shaped like pred")
+    nb = mse_loss_workspace_floats(n)
+    ws = _bwd_workspace(pred.device, nb, "mse_loss")
+    check(lib.x2i_mse_loss_grad_bf16(_p(pred), _p(target), _p(d_pred), n, float(grad_scale), _p(ws), ws.numel(), _stream()), "mse_loss_grad")
+    loss = torch.empty((1,), device=pred.device, dtype=torch.float32) if loss is None else loss
+    reduce_rows(ws, loss, np_=nb, len_=1, in_ps=1, alpha=1.0 / n)
+    return loss, d_pred

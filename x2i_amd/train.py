@@ -77,13 +77,18 @@ class DistillBackward:
 
     # ------------------------------------------------------------------ forward with saves
     @torch.no_grad()
-    def forward_train(self, state, hidden_states, timestep, teacher=None, tap_grads=None, temperature=3.0):
+    def forward_train(self, state, hidden_states, timestep, teacher=None, tap_grads=None, temperature=3.0, *, control=None, keep_head=False):
         """One transformer evaluation (prepared conditioning `state` as in FluxTransformer2DModel.denoise) that keeps what backward()
-        needs.  Exactly one of
+        needs.  At most one of
           teacher   = three stacked tensors / lists [(B, 19, Si, D), (B, 19, St, D), (B, 38, S, D)] as the reference's batch holds them
                       (KD_teacher_tensor0/1/2, train/train_qwenvl.py:570-572): the loss is evaluated tap by tap, or
           tap_grads = three lists of explicit gradients with the taps' shapes (tests, other losses)
-        may be given.  Returns (noise_pred, loss) with loss a device f32 scalar (0 when tap_grads is used)."""
+        may be given; with neither, no gradient is injected at the taps (a loss on noise_pred: backward(seed=...)).
+          control   = callable (i, timestep_x1000, X, St, S, D) invoked after double block i, where denoise() calls its control function: it
+                      adds control net i's output into the image rows of X (lightcontrol_flux.py:504-507) and returns False when there is no
+                      net i; backward(on_injection=...) hands the gradient at these points back
+          keep_head = True keeps the final residual stream (the input of norm_out) for backward(seed=...)
+        Returns (noise_pred, loss) with loss a device f32 scalar (0 when no teacher is given)."""
         m = self.m
         cfg, f, ws = m.config, m._fused, state["ws"]
         B, St, Si = state["B"], state["St"], state["Si"]
@@ -135,7 +140,7 @@ class DistillBackward:
             loss_terms.append(term)
             return g
 
-        saved = dict(state=state, B=B, St=St, Si=Si, S=S, Spad=Spad, temb=temb, MOD=self._keep("MOD", MOD), double=[], single=[])
+        saved = dict(state=state, B=B, St=St, Si=Si, S=S, Spad=Spad, temb=temb, MOD=self._keep("MOD", MOD), double=[], single=[], injections=0)
         qkv_img_off = B * St * 3 * D
         for i in range(cfg.num_layers):
             p = f"d{i}"
@@ -181,6 +186,8 @@ class DistillBackward:
             ops.gated_residual_(X, FF, mod(oc + 5 * D), B, St, D, S * D, D, S * D, D, Ntot)
             sv.update(PRE=PRE, FF=FF)
             saved["double"].append(sv)
+            if control is not None and control(i, t1000, X, St, S, D) is not False:
+                saved["injections"] = i + 1   # hidden_states += control_nets[i](...)['out'] * 1.0: the next block's saved input holds it
         base = cfg.num_layers * 12 * D
         for i in range(cfg.num_single_layers):
             p = f"s{i}"
@@ -206,6 +213,8 @@ class DistillBackward:
             saved["single"].append(sv)
         o = base + cfg.num_single_layers * 3 * D
         NRMF = ws["NRMF"]
+        if keep_head:
+            saved["Xout"] = self._keep("Xout", X)
         ops.ln_modulate(X, NRMF, B, Si, D, 0, None, None, mod(o + D), mod(o), Ntot, x_bs=S * D, ldx=D, y_bs=Si * D, ldy=D, x_offset=St * D)
         out = torch.empty((B, Si, m.out_channels * cfg.patch_size ** 2), **bf)
         ops.gemm(NRMF, f["proj_out.w"], f["proj_out.b"], out=out, M=B * Si)
@@ -285,9 +294,16 @@ class DistillBackward:
         ops.qkv_split_bwd(qkv0, qkv1, ld, ld, dQKV0, dQKV1, ld, ld, B, S, S0, H, nq0, nk0, nq1, nk1, cos, sin, dQ, dK, dV, Spad)
 
     @torch.no_grad()
-    def backward(self):
+    def backward(self, *, seed=None, on_injection=None, stop_after_injections=False):
         """Runs the chain on the activations kept by forward_train(); returns (d_encoder_hidden_states [B, St, joint_dim] bf16,
-        d_pooled_projections [B, pooled_dim] f32)."""
+        d_pooled_projections [B, pooled_dim] f32).
+          seed           = d loss / d noise_pred, bf16 [B, Si, out_channels] (forward_train(keep_head=True)): the chain then starts with the
+                           data gradient of proj_out and the backward of norm_out (AdaLayerNormContinuous) into the image rows of dX
+          on_injection   = callable (i, dX, St, S, D) invoked for every control injection i of forward_train(control=...), highest first, when
+                           the chain has gone back through everything behind it: the image rows of dX [B, S, D] are then d loss / d control
+                           output i (hidden += out * 1.0); dX is overwritten as the chain goes on, so the callee consumes it in place
+          stop_after_injections = True ends the chain behind the lowest injection (everything below is frozen and no control output
+                           depends on it); returns (None, None)"""
         sv = self.saved
         if sv is None:
             raise RuntimeError("backward: call forward_train() first")
@@ -329,6 +345,22 @@ class DistillBackward:
             colsum(np_, 1, 2, shift_off)
 
         base = cfg.num_layers * 12 * D
+        if seed is not None:
+            # ---- output head: noise_pred = proj_out(norm_out(X[:, St:])), norm_out = LayerNorm * (1 + scale) + shift with scale FIRST in the table
+            if "Xout" not in sv:
+                raise RuntimeError("backward(seed=...): call forward_train(keep_head=True)")
+            o = base + cfg.num_single_layers * 3 * D
+            No = f["proj_out.w"].shape[0]
+            if tuple(seed.shape) != (B, Si, No):
+                raise ValueError("backward: seed must be d noise_pred [%d, %d, %d]" % (B, Si, No))
+            dNF = self._buf("dNF", (B, Si, D))
+            ops.gemm(seed.to(**bf).contiguous(), self._wt("proj_out.w"), out=dNF, M=B * Si)
+            ops.ln_mod_bwd(sv["Xout"], dNF, mod(o), None, dX, part, B=B, S=Si, D=D, R=R, mult_bs=Ntot, x_bs=S * D, dy_bs=Si * D, dx_bs=S * D,
+                           x_offset=St * D, dx_offset=St * D)
+            np_ = (Si + R - 1) // R
+            colsum(np_, 0, 2, o)
+            colsum(np_, 1, 2, o + D)
+        n_inj = sv["injections"] if on_injection is not None else 0
         # ---- single-stream blocks, last to first
         for i in reversed(range(cfg.num_single_layers)):
             p = f"s{i}"
@@ -353,6 +385,10 @@ class DistillBackward:
             oi = i * 12 * D
             oc = oi + 6 * D
             d_ = sv["double"][i]
+            if i < n_inj:   # everything behind injection i is done: the image rows of dX are d loss / d control output i
+                on_injection(i, dX, St, S, D)
+                if stop_after_injections and i == 0:
+                    return None, None
             # feed-forward: x = x_mid + gate_mlp * FF
             gate_bwd(d_["FF"], None, oi + 5 * D, St, Si)
             gate_bwd(d_["FF"], None, oc + 5 * D, 0, St)
