@@ -140,3 +140,20 @@ def test_trainer_names_follow_the_module_list_and_step_needs_a_forward():
     assert all(tr.named_grads()[k].shape == p.shape for k, p in zip(want, tr.params))
     with pytest.raises(RuntimeError):
         tr.backward([None, None])
+
+
+def test_projector_trainer_exposes_the_same_flat_buffer_bookkeeping():
+    """ProjectorTrainer and ControlNeXtTrainer share FlatAdamW; built on the CPU device, no launch."""
+    from x2i_amd.proj import Proj7Exp
+    from x2i_amd.train import ProjectorTrainer
+    pr = Proj7Exp(in_channels=3, input_dim=16, output_dim0=8, output_dim1=24, use_t5=False, use_scale=False, use_cnn=True, device="cpu")
+    tr = ProjectorTrainer(pr)
+    named = list(pr.named_parameters())
+    assert tr.names == [n for n, _ in named] and "conv.weight" in tr.names
+    assert all(a is b for a, (_, b) in zip(tr.params, named))
+    o = 0
+    for n, p in named:
+        assert tr.off[n] == (o, p.numel()) and tr.g(n).numel() == p.numel() and tr.g(n).data_ptr() == tr.grad.data_ptr() + 4 * o
+        o += p.numel()
+    assert o == tr.grad.numel() == tr.m.numel() == tr.v.numel() and tr.grad.dtype == torch.float32
+    assert list(tr.named_grads()) == tr.names and tr.step_count == 0 and tr.last_norm is None

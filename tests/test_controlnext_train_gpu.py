@@ -233,6 +233,10 @@ def test_trainer_backward_against_float64_autograd(B, H):
     out = tr.forward(hint.to(DEV), torch.tensor([t], device=DEV))[0]
     ref = nets[0](hint.to(DEV), torch.tensor([t], device=DEV))["out"].permute(0, 2, 3, 1)
     assert torch.equal(out, ref)                             # the same launches as ControlNeXtModel.forward on the chained form
+    if (B, H) == (2, 128):                                   # the trainer ignores net.compose: it always trains the chained form
+        nets[0].compose = True
+        assert torch.equal(tr.forward(hint.to(DEV), torch.tensor([t], device=DEV))[0], ref)
+        nets[0].compose = False
     g = bf(seeded(tuple(out.shape), 5))
     tr.backward([g.to(DEV)])
     hip = {k: v.double().cpu() for k, v in tr.named_grads().items()}

@@ -697,7 +697,7 @@ def vae_encode_expected(boc):
 CNX_PREPARE = [STEM, GN, CONV, GN, CONV, GN, GN, CONV, GNM]                              # embedding, down_res.0 norm1 + conv1, its moments
 CNX_CHAINED = CNX_PREPARE + [GNF, CONV, CONV, GN, CONV, GN, CONV, CONV, CONV, CONV, GN, CONV, GN, CONV]
 CNX_COMPOSED_TRUNK = [GNF, CONV, CONV, CONV, GN, CONV, GN, CONV, CONV, CONV, CONV, CONV, GN, CONV, GN]
-CNX_TRAIN_FORWARD = [STEM, GN, CONV, GN, CONV, GN, GN, CONV, GNM, GNF, CONV, CONV, GN, CONV, GN, CONV, CONV, CONV, CONV, GN, CONV, GN, CONV]
+CNX_TRAIN_FORWARD = CNX_CHAINED
 CNX_TRAIN_BACKWARD = [CONV, CONV] + [CONV] * 4 + [CONV, CONV, CONV] + [CONV] * 4 + [CONV, CONV, CONV, CONV]
 
 BOC = (128, 128, 256, 256)

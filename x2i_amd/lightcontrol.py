@@ -34,6 +34,13 @@ def _param(*shape, device, dtype=torch.bfloat16):
     return nn.Parameter(torch.empty(shape, device=device, dtype=dtype), requires_grad=False)
 
 
+def _kept(keep, name, t):
+    """t itself; with a dict `keep` (the training forward, ControlNeXtTrainer) it is also recorded there under `name` for the backward."""
+    if keep is not None:
+        keep[name] = t
+    return t
+
+
 class _Conv(nn.Module):
     def __init__(self, cin, cout, k, device):
         super().__init__()
@@ -191,18 +198,22 @@ class ControlNeXtModel(nn.Module):
         mid0 = _Sparse({0: _Conv(256, 256, 3, device), 2: _Affine(256, device), 3: _Conv(256, 256, 3, device),
                         4: _Affine(256, device)})
         self.mid_convs = _Sparse({0: mid0, 1: _Conv(256, control_out_channels, 2, device)})
-        self._hint_cache = None
         self.compose = True        # conv2 -> Downsample2D chains as one convolution each (module docstring); False: the chained form (A/B)
         self._composed_cache = None
 
     def _apply(self, fn, recurse=True):
         r = super()._apply(fn, recurse)
+        self.invalidate_weight_caches()
+        return r
+
+    def invalidate_weight_caches(self):
+        """Drop everything derived from the weights (the packed conv weights, the composed chains).  The caches are keyed on weight._version, which
+        moves with load_state_dict and torch's in-place operations -- but ops.adamw_ writes through the raw pointer: weight._version does not
+        move, so after an optimizer step (ControlNeXtTrainer.step) the version-keyed caches would go stale silently."""
         for m in self.modules():
             if isinstance(m, _Conv):
                 m._packed = None
-        self._hint_cache = None
         self._composed_cache = None
-        return r
 
     def _composed(self, h, w):
         """The two composed chains for a (h, w) = (H/2, W/2) grid; rebuilt when a weight changes (load_state_dict, .to())."""
@@ -213,46 +224,87 @@ class ControlNeXtModel(nn.Module):
                                     _Composed(self.down_res[1], self.down_sample[1], h // 4, w // 4))
         return self._composed_cache[1], self._composed_cache[2]
 
-    # ---- timestep-independent prefix (cached per hint tensor)
-    @torch.no_grad()
-    def prepare_hint(self, sample):
-        """embedding (3 convs + GN + ReLU, :593-603,740) and ResnetBlock 0's norm1+SiLU+conv1 (before the time term)."""
+    # ---- the chained form (compose = False, and what ControlNeXtTrainer differentiates): ONE implementation, split where the timestep comes in.
+    # `keep`: None, or the dict that receives every intermediate under the name ControlNeXtTrainer._backward_net reads it by.
+    def _prefix(self, sample, keep=None):
+        """Timestep-independent prefix: embedding (3 convs + GN + ReLU, :593-603,740) and ResnetBlock 0's norm1+SiLU+conv1 (before the time
+        term).  Returns prepare_hint's dict without the composed form's extras."""
         B, _, H, W = sample.shape
         e = self.embedding
-        x = sample.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()  # NHWC
+        x = _kept(keep, "img", sample.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous())  # NHWC
         w0 = e[0].weight.float().permute(0, 2, 3, 1).contiguous()  # [64, ky, kx, 3]
-        x = ops.conv_stem(x, w0, e[0].bias.float(), 64)
-        x = ops.groupnorm_nhwc(x, e[1].weight, e[1].bias, 2, 1e-5, act=ACT_RELU)
+        x = _kept(keep, "s0", ops.conv_stem(x, w0, e[0].bias.float(), 64))
+        x = _kept(keep, "a0", ops.groupnorm_nhwc(x, e[1].weight, e[1].bias, 2, 1e-5, act=ACT_RELU))
         h, w = H // 2, W // 2
-        x = ops.conv2d_nhwc(x, e[3].packed(), e[3].bias, h, w, 64, 64, 3, 3, 1, 1)
-        x = ops.groupnorm_nhwc(x, e[4].weight, e[4].bias, 2, 1e-5, act=ACT_RELU)
-        x = ops.conv2d_nhwc(x, e[6].packed(), e[6].bias, h, w, 64, 128, 3, 3, 1, 1)
-        x0 = ops.groupnorm_nhwc(x, e[7].weight, e[7].bias, 2, 1e-5, act=ACT_RELU)
+        x = _kept(keep, "s3", ops.conv2d_nhwc(x, e[3].packed(), e[3].bias, h, w, 64, 64, 3, 3, 1, 1))
+        x = _kept(keep, "a3", ops.groupnorm_nhwc(x, e[4].weight, e[4].bias, 2, 1e-5, act=ACT_RELU))
+        x = _kept(keep, "s6", ops.conv2d_nhwc(x, e[6].packed(), e[6].bias, h, w, 64, 128, 3, 3, 1, 1))
+        x0 = _kept(keep, "x0", ops.groupnorm_nhwc(x, e[7].weight, e[7].bias, 2, 1e-5, act=ACT_RELU))
         r = self.down_res[0]
-        n = ops.groupnorm_nhwc(x0, r.norm1.weight, r.norm1.bias, self.groups[0], 1e-6, act=ACT_SILU)
-        h1 = ops.conv2d_nhwc(n, r.conv1.packed(), r.conv1.bias, h, w, 128, 128, 3, 3, 1, 1)
+        n = _kept(keep, "n1", ops.groupnorm_nhwc(x0, r.norm1.weight, r.norm1.bias, self.groups[0], 1e-6, act=ACT_SILU))
+        h1 = _kept(keep, "h1", ops.conv2d_nhwc(n, r.conv1.packed(), r.conv1.bias, h, w, 128, 128, 3, 3, 1, 1))
         # norm2 of this block normalises h1 + time_emb_proj(...): h1 does not depend on the timestep, so its per-channel moments are taken
         # here, once per hint, and the denoising loop never runs a statistics pass over the [B, H/2, W/2, 128] tensor again
-        prep = dict(x0=x0, h1=h1, h1_moments=ops.groupnorm_moments(h1), h=h, w=w, B=B, round_bf16=sample.dtype == torch.bfloat16)
-        if self.compose:
-            # down_sample[0] of (the block's identity shortcut + the bias fields): the timestep-independent part of what it will see
-            ca, _ = self._composed(h, w)
-            d = self.down_sample[0].conv
-            prep["d0"] = ops.conv2d_nhwc(x0, d.packed(), None, h, w, 128, 128, 3, 3, 2, 1, res=ca.bias_map, res_batch_stride=0)
-        return prep
+        _kept(keep, "B", B), _kept(keep, "h", h), _kept(keep, "w", w)
+        return dict(x0=x0, h1=h1, h1_moments=ops.groupnorm_moments(h1), h=h, w=w, B=B, round_bf16=sample.dtype == torch.bfloat16)
 
-    def _resblock_tail(self, r, x_in, h1, temb_act, G, h, w, cin, cout, h1_moments=None):
-        """ResnetBlock2D after conv1: h = h1 + time_emb_proj(silu(temb)); h = conv2(silu(GN(h))); out = shortcut(x) + h."""
-        tproj = ops.skinny_linear(temb_act, r.time_emb_proj.weight, r.time_emb_proj.bias, act_in=ACT_SILU)  # [B, cout] f32
+    def _resblock_tail(self, r, x_in, h1, emb, G, h, w, cin, cout, keep, names, h1_moments=None):
+        """ResnetBlock2D after conv1: h = h1 + time_emb_proj(silu(emb)); h = conv2(silu(GN(h))); out = shortcut(x) + h.  names: what `keep` calls
+        the time term, the normalised tensor and the block's output."""
+        tproj = _kept(keep, names[0], ops.skinny_linear(emb, r.time_emb_proj.weight, r.time_emb_proj.bias, act_in=ACT_SILU))  # [B, cout] f32
         if h1_moments is not None:
             n = ops.groupnorm_nhwc_from_moments(h1, h1_moments, r.norm2.weight, r.norm2.bias, G, 1e-6, act=ACT_SILU, pre_add=tproj)
         else:
             n = ops.groupnorm_nhwc(h1, r.norm2.weight, r.norm2.bias, G, 1e-6, act=ACT_SILU, pre_add=tproj)
+        _kept(keep, names[1], n)
         if hasattr(r, "conv_shortcut"):
             sc = ops.conv2d_nhwc(x_in, r.conv_shortcut.packed(), r.conv_shortcut.bias, h, w, cin, cout, 1, 1, 1, 0)
         else:
             sc = x_in
-        return ops.conv2d_nhwc(n, r.conv2.packed(), r.conv2.bias, h, w, cout, cout, 3, 3, 1, 1, res=sc)
+        return _kept(keep, names[2], ops.conv2d_nhwc(n, r.conv2.packed(), r.conv2.bias, h, w, cout, cout, 3, 3, 1, 1, res=sc))
+
+    def _chained_trunk(self, prep, tp, keep=None):
+        """Timestep-dependent trunk up to (not including) mid_convs[1] on _prefix's dict; tp: timestep_features.  Returns (x [B, h, w, 256], h, w)."""
+        h, w = prep["h"], prep["w"]
+        te = self.time_embedding
+        _kept(keep, "tp", tp)
+        if keep is not None:   # the one launch training has over inference: linear_1 BEFORE its SiLU (for the SiLU's derivative only)
+            keep["pre1"] = ops.skinny_linear(tp, te.linear_1.weight, te.linear_1.bias)
+        e1 = _kept(keep, "e1", ops.skinny_linear(tp, te.linear_1.weight, te.linear_1.bias, act_out=ACT_SILU))
+        emb = _kept(keep, "emb", ops.skinny_linear(e1, te.linear_2.weight, te.linear_2.bias))  # [B,256] f32
+        x = self._resblock_tail(self.down_res[0], prep["x0"], prep["h1"], emb, self.groups[0], h, w, 128, 128, keep, ("tp0", "n2", "xr0"),
+                                h1_moments=prep["h1_moments"])
+        d = self.down_sample[0].conv
+        x = _kept(keep, "xd0", ops.conv2d_nhwc(x, d.packed(), d.bias, h, w, 128, 128, 3, 3, 2, 1))
+        h, w = h // 2, w // 2
+        r = self.down_res[1]
+        n = _kept(keep, "n1b", ops.groupnorm_nhwc(x, r.norm1.weight, r.norm1.bias, self.groups[1], 1e-6, act=ACT_SILU))
+        h1 = _kept(keep, "h1b", ops.conv2d_nhwc(n, r.conv1.packed(), r.conv1.bias, h, w, 128, 256, 3, 3, 1, 1))
+        x = self._resblock_tail(r, x, h1, emb, self.groups[1], h, w, 128, 256, keep, ("tp1", "n2b", "xr1"))
+        d = self.down_sample[1].conv
+        x = _kept(keep, "xd1", ops.conv2d_nhwc(x, d.packed(), d.bias, h, w, 256, 256, 3, 3, 2, 1))
+        h, w = h // 2, w // 2
+        return _mid_tail(_mid_tensors(self), x, h, w, keep=keep), h, w
+
+    @torch.no_grad()
+    def forward_chained(self, sample, timestep, keep=None):
+        """forward on the chained form whatever `compose` says, as NHWC [B, H/16, W/16, out_ch] (timestep as forward_nhwc takes it).  With a dict
+        `keep` the intermediates stay in it (ControlNeXtTrainer.forward); nothing else differs, so the output is the same bits either way."""
+        prep = self._prefix(sample, keep)
+        x, h, w = self._chained_trunk(prep, self.timestep_features(prep, timestep), keep)
+        return self._final(x, h, w)
+
+    @torch.no_grad()
+    def prepare_hint(self, sample):
+        """Everything that does not depend on the timestep, computed once per hint tensor: _prefix, plus the composed form's share of it."""
+        prep = self._prefix(sample)
+        if self.compose:
+            # down_sample[0] of (the block's identity shortcut + the bias fields): the timestep-independent part of what it will see
+            h, w = prep["h"], prep["w"]
+            ca, _ = self._composed(h, w)
+            d = self.down_sample[0].conv
+            prep["d0"] = ops.conv2d_nhwc(prep["x0"], d.packed(), None, h, w, 128, 128, 3, 3, 2, 1, res=ca.bias_map, res_batch_stride=0)
+        return prep
 
     @staticmethod
     @torch.no_grad()
@@ -271,31 +323,13 @@ class ControlNeXtModel(nn.Module):
         residual buffer) the final conv's epilogue adds its result straight into the image-token rows instead
         (hidden_states + control['out'] * 1.0, lightcontrol_flux.py:506-507).  `tp`: timestep_features(prep, timestep) when the caller
         has them already."""
-        B, h, w = prep["B"], prep["h"], prep["w"]
         if tp is None:
             tp = self.timestep_features(prep, timestep)
         if self.compose and "d0" in prep:
+            h, w = prep["h"], prep["w"]
             x, h, w = _trunk(_trunk_tensors([self], h, w), prep, tp, self.groups, 0)
             return self._final(x, h, w, add_into, add_offset, add_batch_stride, add_ld)
-        te = self.time_embedding
-        e1 = ops.skinny_linear(tp, te.linear_1.weight, te.linear_1.bias, act_out=ACT_SILU)
-        emb = ops.skinny_linear(e1, te.linear_2.weight, te.linear_2.bias)  # [B,256] f32
-        x = self._resblock_tail(self.down_res[0], prep["x0"], prep["h1"], emb, self.groups[0], h, w, 128, 128, h1_moments=prep.get("h1_moments"))
-        d = self.down_sample[0].conv
-        x = ops.conv2d_nhwc(x, d.packed(), d.bias, h, w, 128, 128, 3, 3, 2, 1)
-        h, w = h // 2, w // 2
-        r = self.down_res[1]
-        n = ops.groupnorm_nhwc(x, r.norm1.weight, r.norm1.bias, self.groups[1], 1e-6, act=ACT_SILU)
-        h1 = ops.conv2d_nhwc(n, r.conv1.packed(), r.conv1.bias, h, w, 128, 256, 3, 3, 1, 1)
-        x = self._resblock_tail(r, x, h1, emb, self.groups[1], h, w, 128, 256)
-        d = self.down_sample[1].conv
-        x = ops.conv2d_nhwc(x, d.packed(), d.bias, h, w, 256, 256, 3, 3, 2, 1)
-        h, w = h // 2, w // 2
-        m = self.mid_convs[0]
-        y = ops.conv2d_nhwc(x, m[0].packed(), m[0].bias, h, w, 256, 256, 3, 3, 1, 1, act=ACT_RELU)
-        y = ops.groupnorm_nhwc(y, m[2].weight, m[2].bias, 8, 1e-5)
-        y = ops.conv2d_nhwc(y, m[3].packed(), m[3].bias, h, w, 256, 256, 3, 3, 1, 1)
-        x = ops.groupnorm_nhwc(y, m[4].weight, m[4].bias, 8, 1e-5, post_add=x)  # mid_convs[0](x) + x (:744)
+        x, h, w = self._chained_trunk(prep, tp)
         return self._final(x, h, w, add_into, add_offset, add_batch_stride, add_ld)
 
     def _final(self, x, h, w, add_into=None, add_offset=0, add_batch_stride=None, add_ld=None):
@@ -316,13 +350,28 @@ class ControlNeXtModel(nn.Module):
         return {"out": out.permute(0, 3, 1, 2), "scale": self.scale}  # NCHW view like the reference
 
 
+def _mid_tensors(net):
+    """The parameters of mid_convs[0] under the names _mid_tail reads them by."""
+    m = net.mid_convs[0]
+    return dict(m0w=m[0].packed(), m0b=m[0].bias, g2w=m[2].weight, g2b=m[2].bias, m3w=m[3].packed(), m3b=m[3].bias, g4w=m[4].weight, g4b=m[4].bias)
+
+
+def _mid_tail(T, x, h, w, wg=0, keep=None):
+    """mid_convs[0](x) + x (:744), the end of both trunks.  T: _mid_tensors of one net (wg = 0), or _trunk_tensors of a bank's nets (wg as _trunk's)."""
+    g = dict(w_group=wg)
+    y = _kept(keep, "y0", ops.conv2d_nhwc(x, T["m0w"], T["m0b"], h, w, 256, 256, 3, 3, 1, 1, act=ACT_RELU, **g))
+    y = _kept(keep, "y2", ops.groupnorm_nhwc(y, T["g2w"], T["g2b"], 8, 1e-5, **g))
+    y = _kept(keep, "y3", ops.conv2d_nhwc(y, T["m3w"], T["m3b"], h, w, 256, 256, 3, 3, 1, 1, **g))
+    return _kept(keep, "xm", ops.groupnorm_nhwc(y, T["g4w"], T["g4b"], 8, 1e-5, post_add=x, **g))
+
+
 def _trunk_tensors(nets, h, w):
     """The parameters the timestep-dependent trunk reads (composed form), as a dict: of ONE net as they are, of several nets stacked along a new
     leading dimension ([nets, ...], contiguous) for the grouped launches of a bank."""
     per = []
     for net in nets:
         ca, cb = net._composed(h, w)
-        te, r0, r1, m = net.time_embedding, net.down_res[0], net.down_res[1], net.mid_convs[0]
+        te, r0, r1 = net.time_embedding, net.down_res[0], net.down_res[1]
         per.append(dict(
             l1w=te.linear_1.weight, l1b=te.linear_1.bias, l2w=te.linear_2.weight, l2b=te.linear_2.bias,
             t0w=r0.time_emb_proj.weight, t0b=r0.time_emb_proj.bias, n02w=r0.norm2.weight, n02b=r0.norm2.bias,
@@ -330,7 +379,7 @@ def _trunk_tensors(nets, h, w):
             n11w=r1.norm1.weight, n11b=r1.norm1.bias, c1w=r1.conv1.packed(), c1b=r1.conv1.bias,
             t1w=r1.time_emb_proj.weight, t1b=r1.time_emb_proj.bias, n12w=r1.norm2.weight, n12b=r1.norm2.bias,
             bsc=cb.wsc, bmap=cb.bias_map, b5=cb.w5, btop=cb.w_top, bleft=cb.w_left, bcorner=cb.w_corner,
-            m0w=m[0].packed(), m0b=m[0].bias, g2w=m[2].weight, g2b=m[2].bias, m3w=m[3].packed(), m3b=m[3].bias, g4w=m[4].weight, g4b=m[4].bias))
+            **_mid_tensors(net)))
     if len(nets) == 1:
         return per[0]
     return {k: torch.stack([d[k] for d in per]).contiguous() for k in per[0]}
@@ -360,11 +409,7 @@ def _trunk(T, prep, tp, groups, wg):
     t1 = ops.conv2d_nhwc(x, T["bsc"], None, h, w, 128, 256, 3, 3, 2, 1, res=bmap, res_batch_stride=(h // 2) * (w // 2) * 256 if wg else 0, **g)
     x = _composed_apply(T["b5"], T["btop"], T["bleft"], T["bcorner"], 256, 256, n, h, w, t1, w_group=wg)       # = down_sample[1](conv2(n) + conv_shortcut(x))
     h, w = h // 2, w // 2
-    y = ops.conv2d_nhwc(x, T["m0w"], T["m0b"], h, w, 256, 256, 3, 3, 1, 1, act=ACT_RELU, **g)
-    y = ops.groupnorm_nhwc(y, T["g2w"], T["g2b"], 8, 1e-5, **g)
-    y = ops.conv2d_nhwc(y, T["m3w"], T["m3b"], h, w, 256, 256, 3, 3, 1, 1, **g)
-    x = ops.groupnorm_nhwc(y, T["g4w"], T["g4b"], 8, 1e-5, post_add=x, **g)   # mid_convs[0](x) + x (:744)
-    return x, h, w
+    return _mid_tail(T, x, h, w, wg), h, w
 
 
 class ControlNeXtBank:

@@ -6,7 +6,8 @@ The reference trains its 19 ControlNeXt nets behind a frozen FLUX.1-dev transfor
   sample_timesteps / sigmas_for   the logit-normal timestep density (:693-701) and get_sigmas (:412-420) on the scheduler's training tables
   x2i_flow_match_noise_bf16       noisy = (1 - sigma) x + sigma noise and target = noise - x with the reference's bf16 roundings, written as
                                   packed tokens (:706-714, :756); `flow_match_noise_reference` below is its torch restatement
-  ControlNeXtTrainer.forward      every net's control output with the activations its backward needs (x2i_amd/lightcontrol_train.py)
+  ControlNeXtTrainer.forward      every net's control output with the activations its backward needs (ControlNeXtModel.forward_chained
+                                  with a dict to keep them in; x2i_amd/lightcontrol_train.py)
   DistillBackward.forward_train   the transformer forward with saves; net i's output is added into the image rows behind double block i
   x2i_mse_loss_grad_bf16          loss = mean((noise_pred - target)^2) (:758-762, weighting "none") and d noise_pred.  The mean over samples
                                   of per-sample means is the overall mean (equal sizes), and unpacking is a permutation, so the loss on
@@ -15,7 +16,7 @@ The reference trains its 19 ControlNeXt nets behind a frozen FLUX.1-dev transfor
                                   every injection the image rows of the residual-stream gradient ARE d loss / d control output i
                                   (hidden += out * 1.0) and go to ControlNeXtTrainer.backward_net in place -- no snapshots; the chain stops
                                   behind injection 0 (what lies below is frozen, and no control output depends on it)
-  ControlNeXtTrainer.step         global-norm clip over all nets, AdamW (:769-775)
+  ControlNeXtTrainer.step         global-norm clip over all nets, AdamW (:769-775): FlatAdamW.step (x2i_amd/optim.py)
 
 The transformer stays frozen: no weight gradient of it is computed.  VAE encoding of the target image is the caller's business
 (x2i_amd.vae.AutoencoderKL(with_encoder=True)); the training program around the step (arguments, data, lr schedule, checkpoint loop), the 8-bit

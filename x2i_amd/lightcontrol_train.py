@@ -2,7 +2,9 @@
 
 The reference trains only its 19 `ControlNeXtModel`s (a ModuleList; 6.49 M parameters each) behind a frozen FLUX.1-dev transformer, with
 `clip_grad_norm_` over `controlnet.parameters()` and AdamW.  This is the counterpart of `ProjectorTrainer` (x2i_amd/train.py) for that step:
-forward with saved activations, the backward of every net from d loss / d control output, and the optimizer.  `backward` / `backward_net` take
+forward with saved activations (`ControlNeXtModel.forward_chained(keep=...)`: the inference code of the chained form itself, handed a dict to
+fill -- there is no second statement of the forward), the backward of every net from d loss / d control output, and the optimizer
+(`FlatAdamW.step`, x2i_amd/optim.py, shared with `ProjectorTrainer`).  `backward` / `backward_net` take
 the gradient in the form `forward_nhwc(add_into=...)` writes the output; x2i_amd/lightcontrol_step.py wires `backward_net` to the injection
 points of the transformer's activation-gradient chain (the whole step, loss to AdamW).
 
@@ -18,13 +20,13 @@ Launches of the backward ("ControlNeXt backward"):
       1x1         a 1x1 conv of dY with W^T;
       2x2 s2      one GEMM per input-row parity ky: N = 2 Cin covers that row's kx and ci, the rows 2y + ky are written through ldc / batch stride.
     The repacks depend on the weights, which change every step: they are made inside backward() and never cached.
-Gradients accumulate in ONE flat f32 buffer (one all-reduce per step) until step(); the moments are f32 like ProjectorTrainer's.
+Gradients accumulate in FlatAdamW's ONE flat f32 buffer (one all-reduce per step) until step(); the moments are f32 like ProjectorTrainer's.
 """
 import torch
 
 from . import ops
-from .lightcontrol import ControlNeXtModel, _Conv
 from .ops import ACT_RELU, ACT_SILU
+from .optim import FlatAdamW
 
 # ---------------------------------------------------------------------------------------------------- host-side data-gradient repacks
 # (device-agnostic torch index plumbing: they run wherever the weight lives)
@@ -96,108 +98,32 @@ def _skinny_bwd(dy, W):
     return torch.cat([ops.skinny_linear_bwd(dy[i:i + 8].contiguous(), W) for i in range(0, dy.shape[0], 8)])
 
 
-# ---------------------------------------------------------------------------------------------------- forward with saves
-@torch.no_grad()
-def forward_saving(net, sample, timestep):
-    """ControlNeXtModel.forward on the chained form (compose = False) -- the same launches in the same order as prepare_hint + forward_nhwc, so the
-    output is bit-identical -- keeping what the backward needs.  Returns (out NHWC bf16 [B, H/16, W/16, Cout], saved dict)."""
-    B, _, H, W = sample.shape
-    e = net.embedding
-    img = sample.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
-    w0 = e[0].weight.float().permute(0, 2, 3, 1).contiguous()
-    s0 = ops.conv_stem(img, w0, e[0].bias.float(), 64)
-    a0 = ops.groupnorm_nhwc(s0, e[1].weight, e[1].bias, 2, 1e-5, act=ACT_RELU)
-    h, w = H // 2, W // 2
-    s3 = ops.conv2d_nhwc(a0, e[3].packed(), e[3].bias, h, w, 64, 64, 3, 3, 1, 1)
-    a3 = ops.groupnorm_nhwc(s3, e[4].weight, e[4].bias, 2, 1e-5, act=ACT_RELU)
-    s6 = ops.conv2d_nhwc(a3, e[6].packed(), e[6].bias, h, w, 64, 128, 3, 3, 1, 1)
-    x0 = ops.groupnorm_nhwc(s6, e[7].weight, e[7].bias, 2, 1e-5, act=ACT_RELU)
-    r = net.down_res[0]
-    n1 = ops.groupnorm_nhwc(x0, r.norm1.weight, r.norm1.bias, net.groups[0], 1e-6, act=ACT_SILU)
-    h1 = ops.conv2d_nhwc(n1, r.conv1.packed(), r.conv1.bias, h, w, 128, 128, 3, 3, 1, 1)
-    h1m = ops.groupnorm_moments(h1)
-    tp = ControlNeXtModel.timestep_features(dict(x0=x0, B=B, round_bf16=sample.dtype == torch.bfloat16), timestep)
-    te = net.time_embedding
-    pre1 = ops.skinny_linear(tp, te.linear_1.weight, te.linear_1.bias)       # (for the SiLU's derivative only)
-    e1 = ops.skinny_linear(tp, te.linear_1.weight, te.linear_1.bias, act_out=ACT_SILU)
-    emb = ops.skinny_linear(e1, te.linear_2.weight, te.linear_2.bias)
-    tp0 = ops.skinny_linear(emb, r.time_emb_proj.weight, r.time_emb_proj.bias, act_in=ACT_SILU)
-    n2 = ops.groupnorm_nhwc_from_moments(h1, h1m, r.norm2.weight, r.norm2.bias, net.groups[0], 1e-6, act=ACT_SILU, pre_add=tp0)
-    xr0 = ops.conv2d_nhwc(n2, r.conv2.packed(), r.conv2.bias, h, w, 128, 128, 3, 3, 1, 1, res=x0)
-    d = net.down_sample[0].conv
-    xd0 = ops.conv2d_nhwc(xr0, d.packed(), d.bias, h, w, 128, 128, 3, 3, 2, 1)
-    h2, w2 = h // 2, w // 2
-    r = net.down_res[1]
-    n1b = ops.groupnorm_nhwc(xd0, r.norm1.weight, r.norm1.bias, net.groups[1], 1e-6, act=ACT_SILU)
-    h1b = ops.conv2d_nhwc(n1b, r.conv1.packed(), r.conv1.bias, h2, w2, 128, 256, 3, 3, 1, 1)
-    tp1 = ops.skinny_linear(emb, r.time_emb_proj.weight, r.time_emb_proj.bias, act_in=ACT_SILU)
-    n2b = ops.groupnorm_nhwc(h1b, r.norm2.weight, r.norm2.bias, net.groups[1], 1e-6, act=ACT_SILU, pre_add=tp1)
-    sc = ops.conv2d_nhwc(xd0, r.conv_shortcut.packed(), r.conv_shortcut.bias, h2, w2, 128, 256, 1, 1, 1, 0)
-    xr1 = ops.conv2d_nhwc(n2b, r.conv2.packed(), r.conv2.bias, h2, w2, 256, 256, 3, 3, 1, 1, res=sc)
-    d = net.down_sample[1].conv
-    xd1 = ops.conv2d_nhwc(xr1, d.packed(), d.bias, h2, w2, 256, 256, 3, 3, 2, 1)
-    h3, w3 = h2 // 2, w2 // 2
-    m = net.mid_convs[0]
-    y0 = ops.conv2d_nhwc(xd1, m[0].packed(), m[0].bias, h3, w3, 256, 256, 3, 3, 1, 1, act=ACT_RELU)
-    y2 = ops.groupnorm_nhwc(y0, m[2].weight, m[2].bias, 8, 1e-5)
-    y3 = ops.conv2d_nhwc(y2, m[3].packed(), m[3].bias, h3, w3, 256, 256, 3, 3, 1, 1)
-    xm = ops.groupnorm_nhwc(y3, m[4].weight, m[4].bias, 8, 1e-5, post_add=xd1)
-    out = net._final(xm, h3, w3)
-    sv = dict(B=B, h=h, w=w, img=img, s0=s0, a0=a0, s3=s3, a3=a3, s6=s6, x0=x0, n1=n1, h1=h1, tp=tp, pre1=pre1, e1=e1, emb=emb, tp0=tp0, n2=n2,
-              xr0=xr0, xd0=xd0, n1b=n1b, h1b=h1b, tp1=tp1, n2b=n2b, xr1=xr1, xd1=xd1, y0=y0, y2=y2, y3=y3, xm=xm)
-    return out, sv
-
-
-class ControlNeXtTrainer:
+class ControlNeXtTrainer(FlatAdamW):
     """The control nets of a LightControl step as the trainable side: forward with saves, backward from d loss / d control output, then
     (all-reduce,) global-norm clip over all nets' parameters together (the reference clips controlnet.parameters(), train_lightcontrol.py:769-772)
     and AdamW (:582-588, :773-775).  Parameters stay the nets' bf16 tensors, updated in place; gradients and the two moments are f32 in one flat
-    buffer each, in the order of the reference ModuleList's named_parameters() ("{i}.<name>")."""
+    buffer each (FlatAdamW), in the order of the reference ModuleList's named_parameters() ("{i}.<name>"): named_grads() has the key set of
+    controlnet.named_parameters() on the ModuleList, which is also what checkpoints.save_control_nets writes.  After the update step() drops
+    every net's weight-derived caches (ControlNeXtModel.invalidate_weight_caches) and the saved activations."""
 
     def __init__(self, nets, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=1.0, process_group=None):
         self.nets = list(nets)
-        self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_grad_norm
-        self.pg = process_group
-        self.names, self.params = [], []
-        for i, net in enumerate(self.nets):
-            for n, p in net.named_parameters():
-                self.names.append("%d.%s" % (i, n))
-                self.params.append(p)
-        dev = self.params[0].device
-        self.off = {}
-        o = 0
-        for n, p in zip(self.names, self.params):
-            self.off[n] = (o, p.numel())
-            o += p.numel()
-        self.grad = torch.zeros((o,), device=dev, dtype=torch.float32)
-        self.m = torch.zeros_like(self.grad)
-        self.v = torch.zeros_like(self.grad)
-        self.step_count = 0
+        super().__init__((("%d.%s" % (i, n), p) for i, net in enumerate(self.nets) for n, p in net.named_parameters()),
+                         lr, betas, eps, weight_decay, max_grad_norm, process_group)
         self.saved = None
-        self.last_norm = None
 
-    def g(self, name):
-        o, s = self.off[name]
-        return self.grad[o:o + s]
-
-    def named_grads(self):
-        """{"{i}.<parameter name>": f32 gradient shaped like the parameter} -- the key set of controlnet.named_parameters() on the ModuleList,
-        which is also what checkpoints.save_control_nets writes."""
-        return {n: self.g(n).view(p.shape) for n, p in zip(self.names, self.params)}
-
-    def zero_grad(self):
-        self.grad.zero_()
+    def _weights_changed(self):
+        for net in self.nets:
+            net.invalidate_weight_caches()
+        self.saved = None
 
     @torch.no_grad()
     def forward(self, guided_hint, timestep):
         """Every net's control output (NHWC bf16 [B, H/16, W/16, Cout]; timestep already x 1000, as forward_nhwc takes it), keeping the
-        activations the backward needs.  Bit-identical to ControlNeXtModel.forward with compose = False.  Nothing is cached across steps."""
-        outs, self.saved = [], []
-        for net in self.nets:
-            out, sv = forward_saving(net, guided_hint, timestep)
-            outs.append(out)
-            self.saved.append(sv)
-        return outs
+        activations the backward needs.  Always the chained form, whatever net.compose says: ControlNeXtModel.forward_chained, i.e. the very
+        code ControlNeXtModel.forward runs with compose = False, so bit-identical to it.  Nothing is cached across steps."""
+        self.saved = [{} for _ in self.nets]
+        return [net.forward_chained(guided_hint, timestep, keep=sv) for net, sv in zip(self.nets, self.saved)]
 
     @torch.no_grad()
     def backward(self, d_outs, offset=0, batch_stride=None, ld=None):
@@ -298,32 +224,6 @@ class ControlNeXtTrainer:
         de1 = _skinny_bwd(demb, te.linear_2.weight)
         ops.act_bwd_(de1, sv["pre1"], ACT_SILU)
         ops.linear_wgrad(de1, sv["tp"], g("time_embedding.linear_1.weight"), g("time_embedding.linear_1.bias"), accumulate=True)
-
-    @torch.no_grad()
-    def step(self):
-        """all-reduce (mean) over the data-parallel group, clip by the global norm of all nets' gradients, AdamW; clears the gradients and every
-        cache derived from the weights.  Returns the device tensor [clip coefficient, gradient norm]."""
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.pg) > 1:
-            dist.all_reduce(self.grad, group=self.pg)
-            ops.reduce_rows(self.grad, self.grad, np_=1, len_=self.grad.numel(), alpha=1.0 / dist.get_world_size(self.pg))
-        coef = ops.clip_coef(ops.sum_all(self.grad, squares=True), self.max_norm)
-        self.step_count += 1
-        for n, p in zip(self.names, self.params):
-            o, s = self.off[n]
-            ops.adamw_(p, self.grad[o:o + s], self.m[o:o + s], self.v[o:o + s], lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
-                       weight_decay=self.wd, step=self.step_count, coef=coef)
-        # AdamW writes through the raw pointer: weight._version does not move, so the version-keyed caches would go stale silently
-        for net in self.nets:
-            for mod in net.modules():
-                if isinstance(mod, _Conv):
-                    mod._packed = None
-            net._hint_cache = None
-            net._composed_cache = None
-        self.saved = None
-        self.grad.zero_()
-        self.last_norm = coef
-        return coef
 
 
 def _resolve(net, dotted):

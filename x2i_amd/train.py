@@ -14,8 +14,9 @@ chain -- no weight gradients -- and that is what `DistillBackward` implements:
                     deterministic, HBM-bound rather than flash-style (the fused form is the next optimisation, DESIGN.md);
                     returns d loss / d encoder_hidden_states and d loss / d pooled_projections.
 
-`ProjectorTrainer` (below) is the other half: the projector's forward with saves, its backward (weight gradients), gradient
-clipping and AdamW, and `distill_step` strings the reference's step together.  Everything numeric runs in the C-ABI library; torch
+`ProjectorTrainer` (below) is the other half: the projector's forward with saves and its backward (weight gradients); gradient all-reduce,
+clipping and AdamW are `FlatAdamW.step` (x2i_amd/optim.py), which it shares with `ControlNeXtTrainer`; `distill_step` strings the
+reference's step together.  Everything numeric runs in the C-ABI library; torch
 is storage and launch order.
 """
 import math
@@ -24,6 +25,7 @@ import torch
 
 from . import ops
 from .ops import ACT_GELU_ERF, ACT_GELU_TANH, ACT_NONE, ACT_SILU
+from .optim import FlatAdamW
 
 
 def _gcd_rows(*ns):
@@ -449,37 +451,20 @@ class DistillBackward:
         return st
 
 
-class ProjectorTrainer:
+class ProjectorTrainer(FlatAdamW):
     """The trainable half of the reference's step: Proj7Exp forward with saved activations, its backward (weight gradients), gradient
     all-reduce over the data-parallel group (what DistributedDataParallel does for the reference, train/train_qwenvl.py:483),
     `clip_grad_norm_` (:628) and `torch.optim.AdamW` (:447-459, :630).  Parameters stay the module's bf16 tensors; gradients and the two
-    moments are f32 in ONE flat buffer each (a single RCCL all-reduce per step; the reference's moments are bf16 -- stated difference,
+    moments are f32 in ONE flat buffer each (FlatAdamW; a single RCCL all-reduce per step; the reference's moments are bf16 -- stated difference,
     results agree with torch.optim.AdamW on bf16 parameters to bf16 rounding, tests/test_train_gpu.py)."""
 
     def __init__(self, proj, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=1.0, process_group=None):
+        super().__init__(proj.named_parameters(), lr, betas, eps, weight_decay, max_grad_norm, process_group)
         self.proj = proj
-        self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_grad_norm
-        self.pg = process_group
-        self.names = [n for n, _ in proj.named_parameters()]
-        self.params = [p for _, p in proj.named_parameters()]
-        sizes = [p.numel() for p in self.params]
-        dev = self.params[0].device
-        total = sum(sizes)
-        self.grad = torch.zeros((total,), device=dev, dtype=torch.float32)
-        self.m = torch.zeros_like(self.grad)
-        self.v = torch.zeros_like(self.grad)
-        self.off = {}
-        o = 0
-        for n, s in zip(self.names, sizes):
-            self.off[n] = (o, s)
-            o += s
-        self.step_count = 0
         self.saved = None
-        self.last_norm = None
 
-    def g(self, name):
-        o, s = self.off[name]
-        return self.grad[o:o + s]
+    def _weights_changed(self):
+        self.proj.__dict__.pop("_conv5x5_cache", None)  # the packed conv table is keyed on the weight's version counter; drop it
 
     @torch.no_grad()
     def forward(self, x):
@@ -574,25 +559,6 @@ class ProjectorTrainer:
             ops.sum_all(dx0, out=self.g("conv.bias"), accumulate=True)
         if keep:  # intermediates for the parity tests
             self.kept = dict(dtok=dtok, dx2=dg2, dpre0=dh, dxn=dxn, dx0=dx0)
-
-    @torch.no_grad()
-    def step(self):
-        """all-reduce (mean) over the data-parallel group, clip by global norm, AdamW; clears the gradients.  Returns the device tensor
-        [clip coefficient, gradient norm]."""
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.pg) > 1:
-            dist.all_reduce(self.grad, group=self.pg)  # one flat buffer: a single RCCL ring all-reduce per step
-            ops.reduce_rows(self.grad, self.grad, np_=1, len_=self.grad.numel(), alpha=1.0 / dist.get_world_size(self.pg))  # in place: mean
-        coef = ops.clip_coef(ops.sum_all(self.grad, squares=True), self.max_norm)
-        self.step_count += 1
-        for n, p in zip(self.names, self.params):
-            o, s = self.off[n]
-            ops.adamw_(p, self.grad[o:o + s], self.m[o:o + s], self.v[o:o + s], lr=self.lr, beta1=self.betas[0], beta2=self.betas[1],
-                       eps=self.eps, weight_decay=self.wd, step=self.step_count, coef=coef)
-        self.proj.__dict__.pop("_conv5x5_cache", None)  # the packed conv table is keyed on the weight's version counter; drop it
-        self.grad.zero_()
-        self.last_norm = coef
-        return coef
 
 
 @torch.no_grad()
