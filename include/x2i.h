@@ -20,7 +20,7 @@
  *     mutex-protected: the option table below and a per-kernel "dynamic LDS size already raised" cache.
  *   - ABI version 5 (x2i_abi_version; 5 adds x2i_attention_vp_ws_bf16 -- no struct changed; x2i_conv3x3_image_bf16 and x2i_vae_posterior_bf16
  *     (the VAE encoder), the ControlNeXt backward and x2i_flow_match_noise_bf16 / x2i_mse_loss_grad_bf16 / x2i_mse_loss_workspace_floats (the head of
- *     the LightControl training step) were added under the same version: new entry points only, no struct or existing signature changed; 4 appended `w_group` to x2i_gemm_args, 0 = what version 3 did, and added the *_grouped entry points).  Since version 1: x2i_gemm_args grew `workspace` / `workspace_bytes`, x2i_qkv_desc `q_scale`
+ *     the LightControl training step) and x2i_adamw8_blockwise_bf16 (block-wise 8-bit AdamW) were added under the same version: new entry points only, no struct or existing signature changed; 4 appended `w_group` to x2i_gemm_args, 0 = what version 3 did, and added the *_grouped entry points).  Since version 1: x2i_gemm_args grew `workspace` / `workspace_bytes`, x2i_qkv_desc `q_scale`
  *     and x2i_conv_desc a ninth field (version 2); version 3 re-defines that field as `pad_w_p1` (0 = same padding as `pad`, so that a
  *     zero-initialised descriptor means what it meant in version 1), appends `out_w`, `out_h`, `out_row_pitch` (0 = computed / dense) and the `moments` fields (NULL = off) to it, gives `up` the value 2, and appends `vt_perm` to x2i_qkv_desc (0 = the old layout).  A caller built against another version must not load this
  *     library (x2i_amd/_lib.py checks).
@@ -546,6 +546,19 @@ int x2i_clip_coef_f32(const float* sumsq, float max_norm, float* out, x2i_stream
 /* AdamW step (torch.optim.AdamW semantics, :447-459) on bf16 parameters, f32 gradients (scaled by *grad_coef when non-NULL) and f32 moments */
 int x2i_adamw_bf16(void* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                    float bias_correction1, float bias_correction2, const float* grad_coef, x2i_stream_t stream);
+/* The same step with block-wise 8-bit moments (the reference's --use_8bit_adam, train/train_qwenvl.py:437-447; csrc/optim8.hip), for EVERY block of
+ * every parameter in one launch.  A block is 256 consecutive elements of one parameter (the last block of a parameter may hold fewer).  State: one
+ * uint8 code per element and moment (code_m, code_v: [256 num_blocks]) and one f32 absmax per block and moment; a moment's value is
+ * map[code] * absmax with map_signed (first moment) / map_unsigned (second moment) two sorted 256-entry f32 tables in [-1, 1] / [0, 1] (zero at
+ * index 127 / 0).  Block b owns elements [256 b, 256 b + 256) of g and of the code arrays (the caller pads; padding is neither read by an
+ * update nor written) and the parameter elements block_table[b] = {address of the block's first bf16 element, number of valid elements 1..256}
+ * (int64 pairs, device memory, built once by the caller).  Per element: m = beta1 m_old + (1 - beta1) g', v = beta2 v_old + (1 - beta2) g'^2,
+ * the parameter update of x2i_adamw_bf16 from these UNQUANTISED moments (rounded once to bf16), then the block's new absmax (max |m|, max v) and
+ * the code of the entry nearest to m / absmax (v / absmax); absmax 0 gives the zero entry, a positive v never the zero entry.  All state is
+ * the caller's; X2I_ERR_ARG for a null pointer, num_blocks <= 0, or block_table / g not 16-byte, codes / absmax / maps not 4-byte aligned. */
+int x2i_adamw8_blockwise_bf16(const int64_t* block_table, const float* g, void* code_m, void* code_v, float* absmax_m, float* absmax_v,
+                              const float* map_signed, const float* map_unsigned, int64_t num_blocks, float lr, float beta1, float beta2, float eps,
+                              float weight_decay, float bias_correction1, float bias_correction2, const float* grad_coef, x2i_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * ControlNeXt backward: the trainable side of the LightControl step (lightcontrol/train_lightcontrol.py:572-588, :769-775: the control nets'

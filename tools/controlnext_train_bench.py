@@ -23,6 +23,7 @@ def main():
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--batches", default="1,2")
     ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--use_8bit_adam", action="store_true", help="block-wise 8-bit AdamW moments (stands where the reference selects bnb.optim.AdamW8bit; here x2i_amd.optim.FlatAdamW8bit on HIP)")
     a = ap.parse_args()
     from oracle import flux as OF
     from x2i_amd.lightcontrol import ControlNeXtModel
@@ -33,7 +34,7 @@ def main():
         m.load_state_dict({k: v.to(torch.bfloat16) for k, v in OF.random_controlnext_state_dict(seed=i).items()}, strict=True)
         m.compose = False
         nets.append(m)
-    tr = ControlNeXtTrainer(nets)
+    tr = ControlNeXtTrainer(nets, use_8bit_adam=a.use_8bit_adam)
     scale = (a.size / 1024) ** 2
     for B in [int(b) for b in a.batches.split(",")]:
         hint = torch.rand((B, 3, a.size, a.size), device="cuda") * 2 - 1

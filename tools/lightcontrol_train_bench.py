@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--text", type=int, default=512)
     ap.add_argument("--batches", default="1,2")
     ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--use_8bit_adam", action="store_true", help="block-wise 8-bit AdamW moments (stands where the reference selects bnb.optim.AdamW8bit; here x2i_amd.optim.FlatAdamW8bit on HIP)")
     a = ap.parse_args()
     from oracle import flux as OF
     from x2i_amd.flux import FluxTransformer2DModel
@@ -40,7 +41,7 @@ def main():
         n = ControlNeXtModel(device=dev)
         n.load_state_dict({k: v.to(torch.bfloat16) for k, v in OF.random_controlnext_state_dict(seed=i).items()}, strict=True)
         nets.append(n)
-    tr = ControlNeXtTrainer(nets)
+    tr = ControlNeXtTrainer(nets, use_8bit_adam=a.use_8bit_adam)
     step = LightControlTrainStep(m, tr)
     sched = FlowMatchEulerDiscreteScheduler(shift=3.0, use_dynamic_shifting=True)
     lat = a.size // 8

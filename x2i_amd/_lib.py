@@ -117,6 +117,7 @@ SIGNATURES = {
     "x2i_sum_partials": [_vp, _i32, _i64, _i32, _vp, _i32, _vp],
     "x2i_clip_coef_f32": [_vp, _f32, _vp, _vp],
     "x2i_adamw_bf16": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp],
+    "x2i_adamw8_blockwise_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp],
     "x2i_conv_wgrad_workspace_floats": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64)],
     "x2i_conv_wgrad_bf16": [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
     "x2i_conv_stem_wgrad_workspace_floats": [_i32, _i32, _i32, _i32, C.POINTER(C.c_int64)],

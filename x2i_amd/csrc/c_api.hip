@@ -448,6 +448,13 @@ int x2i_adamw_bf16(void* p, const float* g, float* m, float* v, int64_t n, float
   return x2i_launch_adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, grad_coef, (hipStream_t)stream);
 }
 
+int x2i_adamw8_blockwise_bf16(const int64_t* block_table, const float* g, void* code_m, void* code_v, float* absmax_m, float* absmax_v,
+                              const float* map_signed, const float* map_unsigned, int64_t num_blocks, float lr, float beta1, float beta2, float eps,
+                              float weight_decay, float bias_correction1, float bias_correction2, const float* grad_coef, x2i_stream_t stream) {
+  return x2i_launch_adamw8((const long long*)block_table, g, code_m, code_v, absmax_m, absmax_v, map_signed, map_unsigned, num_blocks, lr, beta1, beta2,
+                           eps, weight_decay, bias_correction1, bias_correction2, grad_coef, (hipStream_t)stream);
+}
+
 int x2i_attention_bwd_bf16(const void* Q, const void* K, const void* V, const void* QT, const void* KT, const void* dO, const void* dOT, float* lse2,
                            const float* D, void* dQ, void* dK, void* dV, int32_t B, int32_t H, int32_t S, int32_t Spad, float scale,
                            int32_t have_lse, x2i_stream_t stream) {

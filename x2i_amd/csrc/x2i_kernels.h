@@ -101,6 +101,10 @@ int x2i_launch_attention_bwd(const void* Q, const void* K, const void* V, const 
                              int have_lse, hipStream_t stream);
 int x2i_launch_attention_bwd_prep(const void* dO, long long do_bs, int lddo, const void* O, long long o_bs, int ldo, float* Dv, int B, int H,
                                   int S, int Spad, hipStream_t stream);
+/* ---- block-wise 8-bit AdamW (optim8.hip): one launch over the caller's per-block table {address of the block's first bf16 parameter, valid count} */
+int x2i_launch_adamw8(const long long* table, const float* g, void* cm, void* cv, float* am, float* av, const float* map_s, const float* map_u,
+                      long long nblocks, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, const float* coef,
+                      hipStream_t stream);
 /* ---- head of the LightControl training step (train.hip); the workspace query returns -1 for a size the launcher refuses */
 int x2i_launch_flow_match_noise(const void* x, const void* noise, const float* sigma, void* noisy, void* target, int B, int C, int h, int w,
                                 hipStream_t stream);

@@ -16,11 +16,13 @@ The reference trains its 19 ControlNeXt nets behind a frozen FLUX.1-dev transfor
                                   every injection the image rows of the residual-stream gradient ARE d loss / d control output i
                                   (hidden += out * 1.0) and go to ControlNeXtTrainer.backward_net in place -- no snapshots; the chain stops
                                   behind injection 0 (what lies below is frozen, and no control output depends on it)
-  ControlNeXtTrainer.step         global-norm clip over all nets, AdamW (:769-775): FlatAdamW.step (x2i_amd/optim.py)
+  ControlNeXtTrainer.step         global-norm clip over all nets, AdamW (:769-775): FlatAdamW.step (x2i_amd/optim.py), or with
+                                  ControlNeXtTrainer(use_8bit_adam=True) FlatAdamW8bit.step, the block-wise 8-bit moments that stand where
+                                  the reference's --use_8bit_adam selects bnb.optim.AdamW8bit (:559-569)
 
 The transformer stays frozen: no weight gradient of it is computed.  VAE encoding of the target image is the caller's business
-(x2i_amd.vae.AutoencoderKL(with_encoder=True)); the training program around the step (arguments, data, lr schedule, checkpoint loop), the 8-bit
-optimizer and the MLLM that makes the prompt embeddings are out of scope; checkpoints.save_control_nets writes the nets.
+(x2i_amd.vae.AutoencoderKL(with_encoder=True)); the training program around the step (arguments, data, lr schedule, checkpoint loop) and the MLLM
+that makes the prompt embeddings are out of scope; checkpoints.save_control_nets writes the nets.
 """
 import torch
 

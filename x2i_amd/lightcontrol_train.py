@@ -26,7 +26,7 @@ import torch
 
 from . import ops
 from .ops import ACT_RELU, ACT_SILU
-from .optim import FlatAdamW
+from .optim import EightBitOption, FlatAdamW
 
 # ---------------------------------------------------------------------------------------------------- host-side data-gradient repacks
 # (device-agnostic torch index plumbing: they run wherever the weight lives)
@@ -98,15 +98,16 @@ def _skinny_bwd(dy, W):
     return torch.cat([ops.skinny_linear_bwd(dy[i:i + 8].contiguous(), W) for i in range(0, dy.shape[0], 8)])
 
 
-class ControlNeXtTrainer(FlatAdamW):
+class ControlNeXtTrainer(EightBitOption, FlatAdamW):
     """The control nets of a LightControl step as the trainable side: forward with saves, backward from d loss / d control output, then
     (all-reduce,) global-norm clip over all nets' parameters together (the reference clips controlnet.parameters(), train_lightcontrol.py:769-772)
     and AdamW (:582-588, :773-775).  Parameters stay the nets' bf16 tensors, updated in place; gradients and the two moments are f32 in one flat
     buffer each (FlatAdamW), in the order of the reference ModuleList's named_parameters() ("{i}.<name>"): named_grads() has the key set of
     controlnet.named_parameters() on the ModuleList, which is also what checkpoints.save_control_nets writes.  After the update step() drops
-    every net's weight-derived caches (ControlNeXtModel.invalidate_weight_caches) and the saved activations."""
+    every net's weight-derived caches (ControlNeXtModel.invalidate_weight_caches) and the saved activations.  `use_8bit_adam=True` (the
+    reference's --use_8bit_adam, :559-569) gives the same trainer over FlatAdamW8bit: block-wise 8-bit moments, x2i_amd/optim.py."""
 
-    def __init__(self, nets, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=1.0, process_group=None):
+    def __init__(self, nets, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=1.0, process_group=None, *, use_8bit_adam=False):
         self.nets = list(nets)
         super().__init__((("%d.%s" % (i, n), p) for i, net in enumerate(self.nets) for n, p in net.named_parameters()),
                          lr, betas, eps, weight_decay, max_grad_norm, process_group)

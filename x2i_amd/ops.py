@@ -929,6 +929,14 @@ def adamw_(p, g, m, v, *, lr, beta1, beta2, eps, weight_decay, step, coef=None):
     return p
 
 
+def adamw8_(table, g, code_m, code_v, absmax_m, absmax_v, map_signed, map_unsigned, *, lr, beta1, beta2, eps, weight_decay, step, coef=None):
+    """Block-wise 8-bit AdamW (include/x2i.h: x2i_adamw8_blockwise_bf16): ONE launch over every block of the int64 [blocks, 2] table
+    {address of the block's first bf16 parameter element, valid count}; g f32 / code_m, code_v uint8 [256 blocks], absmax f32 [blocks]."""
+    check(_lib.load().x2i_adamw8_blockwise_bf16(_p(table), _p(g), _p(code_m), _p(code_v), _p(absmax_m), _p(absmax_v), _p(map_signed),
+                                                _p(map_unsigned), table.shape[0], float(lr), float(beta1), float(beta2), float(eps),
+                                                float(weight_decay), 1.0 - beta1 ** step, 1.0 - beta2 ** step, _p(coef), _stream()), "adamw8")
+
+
 def attention_bwd(Q, K, V, QT, KT, dOh, dOT, lse2, Dv, dQ, dK, dV, B, H, S, Spad, scale, have_lse=False):
     """Fused attention backward (include/x2i.h: x2i_attention_bwd_bf16); have_lse: lse2 was written by attention_lse()."""
     check(_lib.load().x2i_attention_bwd_bf16(_p(Q), _p(K), _p(V), _p(QT), _p(KT), _p(dOh), _p(dOT), _p(lse2), _p(Dv), _p(dQ), _p(dK), _p(dV), B, H, S,

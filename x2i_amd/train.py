@@ -25,7 +25,7 @@ import torch
 
 from . import ops
 from .ops import ACT_GELU_ERF, ACT_GELU_TANH, ACT_NONE, ACT_SILU
-from .optim import FlatAdamW
+from .optim import EightBitOption, FlatAdamW
 
 
 def _gcd_rows(*ns):
@@ -451,14 +451,15 @@ class DistillBackward:
         return st
 
 
-class ProjectorTrainer(FlatAdamW):
+class ProjectorTrainer(EightBitOption, FlatAdamW):
     """The trainable half of the reference's step: Proj7Exp forward with saved activations, its backward (weight gradients), gradient
     all-reduce over the data-parallel group (what DistributedDataParallel does for the reference, train/train_qwenvl.py:483),
     `clip_grad_norm_` (:628) and `torch.optim.AdamW` (:447-459, :630).  Parameters stay the module's bf16 tensors; gradients and the two
     moments are f32 in ONE flat buffer each (FlatAdamW; a single RCCL all-reduce per step; the reference's moments are bf16 -- stated difference,
-    results agree with torch.optim.AdamW on bf16 parameters to bf16 rounding, tests/test_train_gpu.py)."""
+    results agree with torch.optim.AdamW on bf16 parameters to bf16 rounding, tests/test_train_gpu.py).  `use_8bit_adam=True` (the reference's
+    --use_8bit_adam, :437-447) gives the same trainer over FlatAdamW8bit: block-wise 8-bit moments, x2i_amd/optim.py."""
 
-    def __init__(self, proj, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=1.0, process_group=None):
+    def __init__(self, proj, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=1.0, process_group=None, *, use_8bit_adam=False):
         super().__init__(proj.named_parameters(), lr, betas, eps, weight_decay, max_grad_norm, process_group)
         self.proj = proj
         self.saved = None

@@ -44,6 +44,7 @@ def parse_args(argv=None):
     p.add_argument("--adam_weight_decay", type=float, default=1e-2)
     p.add_argument("--adam_epsilon", type=float, default=1e-08)
     p.add_argument("--max_grad_norm", type=float, default=1.0)
+    p.add_argument("--use_8bit_adam", action="store_true", help="block-wise 8-bit AdamW moments (stands where the reference selects bnb.optim.AdamW8bit; here x2i_amd.optim.FlatAdamW8bit on HIP)")
     p.add_argument("--temperature", type=float, default=3.0, help="temperature0 of the distillation loss (:612)")
     p.add_argument("--local_infer_world_size", type=int, default=0, help="teacher ranks per node (0: every rank trains)")
     p.add_argument("--synthetic", action="store_true", help="random-init transformer and random batches at the reference's shapes")
@@ -134,7 +135,8 @@ def run(args):
         St, lat_hw, mllm = 512, 64, None
     D = model.inner_dim
     trainer = ProjectorTrainer(proj, lr=args.learning_rate, betas=(args.adam_beta1, args.adam_beta2), eps=args.adam_epsilon,
-                               weight_decay=args.adam_weight_decay, max_grad_norm=args.max_grad_norm, process_group=train_pg)
+                               weight_decay=args.adam_weight_decay, max_grad_norm=args.max_grad_norm, process_group=train_pg,
+                               use_8bit_adam=args.use_8bit_adam)
     chain = DistillBackward(model)
     txt_ids = torch.zeros((St, 3), device=device)                                               # :551
     img_ids = FluxPipeline._prepare_latent_image_ids(1, lat_hw, lat_hw, device, torch.float32)   # :552
