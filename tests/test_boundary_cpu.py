@@ -89,3 +89,48 @@ def test_every_entry_point_is_listed_in_the_integration_table():
     missing = [n for n in sorted(declared) if "`%s`" % n not in md and n not in ("x2i_groupnorm_scratch_floats", "x2i_groupnorm_moments_scratch_floats")]
     assert not missing, missing
     assert "x2i_flux_" not in HDR  # no phantom handle API in the contract
+
+
+def header_prototypes():
+    """{export: (return type, [argument types])} of every prototype in include/x2i.h, as the ctypes objects the binding must use"""
+    from x2i_amd import _lib
+    structs = {"x2i_gemm_args": _lib.GemmArgs, "x2i_conv_desc": _lib.ConvDesc, "x2i_qkv_desc": _lib.QkvDesc, "x2i_fp8_desc": _lib.Fp8Desc}
+    scalars = {"int32_t": C.c_int32, "int": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "x2i_stream_t": C.c_void_p}
+
+    def ctype(decl, named):
+        """`const float* x` / `int32_t B` (named) or a bare return type -> the ctypes type"""
+        words = decl.replace("*", " * ").split()
+        const = "const" in words       # (an int64_t* is a result the callee writes; a const int64_t* is device memory like any other pointer)
+        words = [w for w in words if w != "const"]
+        if named and words[-1] != "*":
+            words = words[:-1]          # the parameter's name
+        base, stars = words[0], words.count("*")
+        assert words[1:] == ["*"] * stars and stars <= 1, decl
+        if not stars:
+            return scalars[base]
+        if base in structs:
+            return C.POINTER(structs[base])
+        return {("int64_t", False): C.POINTER(C.c_int64), ("char", True): C.c_char_p}.get((base, const), C.c_void_p)
+
+    text = re.sub(r"/\*.*?\*/", "", HDR, flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"^(int|int64_t|const char\*)\s+(x2i_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        params = " ".join(params.split())
+        out[name] = (ctype(ret, False), [] if params == "void" else [ctype(p, True) for p in params.split(",")])
+    return out
+
+
+def test_every_prototype_matches_the_binding_table():
+    """include/x2i.h against x2i_amd/_lib.py, export by export: the return type and every argument type, in order -- an int32 in the table where
+    the header says int64_t would truncate a stride without any error."""
+    from x2i_amd import _lib
+    want = header_prototypes()
+    assert len(want) == 80 and set(want) == set(_lib.SIGNATURES) == set(_lib.RESTYPES)
+    assert want["x2i_last_error"] == (C.c_char_p, []) and want["x2i_streamk_workspace_bytes"] == (C.c_int64, [])
+    assert want["x2i_gemm_qkv_fp8"][1] == [C.POINTER(_lib.GemmArgs), C.POINTER(_lib.Fp8Desc), C.POINTER(_lib.QkvDesc), C.c_void_p]
+    assert want["x2i_get_option"][1] == [C.c_char_p, C.POINTER(C.c_int64)]
+    for name, (ret, args) in sorted(want.items()):
+        assert _lib.RESTYPES[name] == ret, name
+        assert len(_lib.SIGNATURES[name]) == len(args), name
+        for i, (got, exp) in enumerate(zip(_lib.SIGNATURES[name], args)):
+            assert got == exp, "%s: argument %d is %s in the binding, %s in the header" % (name, i, got.__name__, exp.__name__)

@@ -60,8 +60,16 @@ class Fp8Desc(C.Structure):
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
-# name -> argtypes (restype is int for all but the two below); mirrors include/x2i.h exactly
-SIGNATURES = {
+# Every export of include/x2i.h, in one table: name -> argtypes, or (restype, argtypes) where the return type is not int.
+# tests/test_boundary_cpu.py checks it against the header's prototypes, argument by argument.
+_EXPORTS = {
+    "x2i_abi_version": [],
+    "x2i_last_error": (C.c_char_p, []),
+    "x2i_is_ablation_build": [],
+    "x2i_streamk_workspace_bytes": (_i64, []),
+    "x2i_groupnorm_scratch_floats": (_i64, [_i32, _i32]),
+    "x2i_groupnorm_moments_scratch_floats": (_i64, [_i32, _i32]),
+    "x2i_conv_moments_scratch_floats": (_i64, [_i32, _i32, _i32]),
     "x2i_gemm_bf16": [C.POINTER(GemmArgs), _vp],
     "x2i_conv2d_nhwc_bf16": [C.POINTER(GemmArgs), C.POINTER(ConvDesc), _vp],
     "x2i_gemm_qkv_bf16": [C.POINTER(GemmArgs), C.POINTER(QkvDesc), _vp],
@@ -138,6 +146,8 @@ SIGNATURES = {
     "x2i_set_option": [C.c_char_p, _i64],
     "x2i_get_option": [C.c_char_p, C.POINTER(C.c_int64)],
 }
+SIGNATURES = {name: sig[1] if isinstance(sig, tuple) else sig for name, sig in _EXPORTS.items()}
+RESTYPES = {name: sig[0] if isinstance(sig, tuple) else C.c_int for name, sig in _EXPORTS.items()}
 
 _lib = None
 
@@ -155,21 +165,10 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:
         raise X2IError("x2i_amd: cannot load %s: %s" % (LIB_PATH, e))
-    lib.x2i_abi_version.restype = C.c_int
-    lib.x2i_last_error.restype = C.c_char_p
-    lib.x2i_groupnorm_scratch_floats.argtypes = [_i32, _i32]
-    lib.x2i_groupnorm_scratch_floats.restype = C.c_int64
-    lib.x2i_is_ablation_build.restype = C.c_int
-    lib.x2i_groupnorm_moments_scratch_floats.argtypes = [_i32, _i32]
-    lib.x2i_groupnorm_moments_scratch_floats.restype = C.c_int64
-    lib.x2i_conv_moments_scratch_floats.argtypes = [_i32, _i32, _i32]
-    lib.x2i_conv_moments_scratch_floats.restype = C.c_int64
-    lib.x2i_streamk_workspace_bytes.argtypes = []
-    lib.x2i_streamk_workspace_bytes.restype = C.c_int64
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.argtypes = argtypes
-        fn.restype = C.c_int
+        fn.restype = RESTYPES[name]
     if lib.x2i_abi_version() != ABI_VERSION:
         raise X2IError("x2i_amd: %s reports ABI version %d, this binding is written against %d (stale build? run `python -m x2i_amd.build`)"
                        % (LIB_PATH, lib.x2i_abi_version(), ABI_VERSION))

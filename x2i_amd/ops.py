@@ -2,15 +2,18 @@
 HIP stream; every computation happens in libx2i_hip.so.  All wrappers enqueue on torch's current stream, so they can
 be captured with torch.cuda.graph().
 """
+import contextlib
 import ctypes as C
+import threading
+import weakref
 
 import torch
 
 from . import _lib
-from ._lib import QkvDesc, ACT_GELU_ERF, ACT_GELU_TANH, ACT_NONE, ACT_SILU, GemmArgs, check  # noqa: F401
+from ._lib import ACT_GELU_ERF, ACT_GELU_TANH, ACT_NONE, ACT_RELU, ACT_SILU, ConvDesc, Fp8Desc, GemmArgs, QkvDesc, check  # noqa: F401
 
-
-import contextlib
+FP8 = torch.float8_e4m3fn
+E4M3_MAX = 448.0
 
 
 @contextlib.contextmanager
@@ -40,9 +43,6 @@ def _stream():
 # across streams here (a stream that takes over waits for the stream that issued the previous workspace-carrying GEMM), and a graph
 # captured under streamk_scope must not be replayed concurrently with other GEMM launches on its device (FluxPipeline and
 # GraphedDistillStep replay on the caller's one stream); streamk_check() turns a violation into an exception.
-import threading
-import weakref
-
 SK_ERR_SLOT = 256  # csrc/gemm_device.h: flags[SK_ERR_SLOT] = a chained segment gave up waiting for its predecessor
 _sk_eager = {}
 _sk_last_stream = {}   # device index -> torch stream of the last eager workspace-carrying GEMM
@@ -117,12 +117,6 @@ def _sk_workspace():
     return ws
 
 
-def _set_ws(a):
-    ws = _sk_workspace()
-    if ws is not None:
-        a.workspace, a.workspace_bytes = ws.buf.data_ptr(), ws.nbytes
-
-
 def option_epoch():
     """x2i_set_option changes since import (x2i_amd/_lib.py): part of FluxPipeline's graph key."""
     return _lib.option_epoch()
@@ -146,6 +140,24 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _off(t, elems):
+    """t's address `elems` ELEMENTS in (its dtype gives the bytes: an offset into an e4m3 tensor counts bytes); null for None"""
+    return C.c_void_p(t.data_ptr() + elems * t.element_size()) if t is not None else C.c_void_p(0)
+
+
+_scratch_bufs = {}
+
+
+def _scratch(device, kind, floats, least=0):
+    """Cached f32 scratch of at least `floats` elements, one buffer per (device, kind) that grows when a call needs more; launches on one stream
+    reuse it in order.  A kind that is the size itself (the group norms') is one buffer per exact size."""
+    key = (device, kind)
+    buf = _scratch_bufs.get(key)
+    if buf is None or buf.numel() < floats:
+        buf = _scratch_bufs[key] = torch.empty(max(int(floats), least), device=device, dtype=torch.float32)
+    return buf
+
+
 def _req(t, dtype, name):
     if t.device.type != "cuda":
         raise _lib.X2IError("x2i_amd: %s must live on the GPU (got %s); the HIP path has no CPU fallback" % (name, t.device))
@@ -155,6 +167,28 @@ def _req(t, dtype, name):
 
 def pad128(n):
     return (n + 127) // 128 * 128
+
+
+def _gemm_struct(A, W, bias, out, M, N, K, batch, lda, ldw, ldc, a_offset=0, a_batch_stride=0, c_offset=0, c_batch_stride=0, act=ACT_NONE,
+                 gate=None, gate_batch_stride=0, res=None, res_offset=0, res_batch_stride=0, ldr=0, out2=None, act2=0, bias2=None, bias2_batch_stride=0,
+                 w_batch_stride=0, w_group=0, out_f32=False, ws=None):
+    """The one place an x2i_gemm_args is filled (field order of include/x2i.h).  Offsets count elements of the tensor they move in, as _off's do
+    (plain integers here: no ctypes object per pointer on the hottest path); `out` None: no C (the fused-QKV epilogue writes Q / K / VT); ws: the
+    stream-K workspace to attach, None for none.  (The GEMM wrappers pass everything by position: binding thirty keywords costs more than filling the struct.)"""
+    # (`off and off * size`: the usual zero offset costs no element_size() call)
+    return GemmArgs(A.data_ptr() + (a_offset and a_offset * A.element_size()), a_batch_stride, lda,
+                    W.data_ptr(), ldw,
+                    None if bias is None else bias.data_ptr(),
+                    None if out is None else out.data_ptr() + (c_offset and c_offset * out.element_size()), c_batch_stride, ldc,
+                    None if out2 is None else out2.data_ptr() + (c_offset and c_offset * out2.element_size()), act2,
+                    None if gate is None else gate.data_ptr(), gate_batch_stride,
+                    None if res is None else res.data_ptr() + (res_offset and res_offset * res.element_size()), res_batch_stride, ldr,
+                    None if bias2 is None else bias2.data_ptr(), bias2_batch_stride,
+                    w_batch_stride,
+                    M, N, K, batch,
+                    act, 1 if out_f32 else 0,
+                    None if ws is None else ws.buf.data_ptr(), 0 if ws is None else ws.nbytes,
+                    w_group)   # > 0: grouped weights, W [groups, N, K] / bias [groups, N], w_group consecutive batch items per group (include/x2i.h)
 
 
 def _gemm_args(A, W, bias=None, out=None, *, M=None, batch=1, a_batch_stride=0, lda=None, c_batch_stride=0, ldc=None,
@@ -172,32 +206,10 @@ def _gemm_args(A, W, bias=None, out=None, *, M=None, batch=1, a_batch_stride=0, 
         if batch > 1:
             c_batch_stride = M * N
     ldc = N if ldc is None else ldc
-    esz_c = 4 if out_f32 else 2
-    a = GemmArgs()
-    a.A = A.data_ptr() + a_offset * 2
-    a.a_batch_stride = a_batch_stride
-    a.lda = lda
-    a.W = W.data_ptr()
-    a.ldw = W.stride(-2)  # row stride of the [.., N, K] weight (a leading batch dimension is addressed by w_batch_stride)
-    a.bias = bias.data_ptr() if bias is not None else None
-    a.C = out.data_ptr() + c_offset * esz_c
-    a.c_batch_stride = c_batch_stride
-    a.ldc = ldc
-    a.C2 = (out2.data_ptr() + c_offset * 2) if out2 is not None else None
-    a.act2 = act2
-    a.gate = gate.data_ptr() if gate is not None else None
-    a.gate_batch_stride = gate_batch_stride
-    a.res = (res.data_ptr() + res_offset * 2) if res is not None else None
-    a.res_batch_stride = res_batch_stride
-    a.ldr = (ldc if ldr is None else ldr)
-    a.bias2 = bias2.data_ptr() if bias2 is not None else None
-    a.bias2_batch_stride = bias2_batch_stride
-    a.w_batch_stride = w_batch_stride
-    a.w_group = w_group   # > 0: grouped weights, W [groups, N, K] / bias [groups, N], w_group consecutive batch items per group (include/x2i.h)
-    a.M, a.N, a.K, a.batch = M, N, K, batch
-    a.act = act
-    a.out_f32 = 1 if out_f32 else 0
-    _set_ws(a)
+    # (ldw: row stride of the [.., N, K] weight; a leading batch dimension is addressed by w_batch_stride)
+    a = _gemm_struct(A, W, bias, out, M, N, K, batch, lda, W.stride(-2), ldc, a_offset, a_batch_stride, c_offset, c_batch_stride, act,
+                     gate, gate_batch_stride, res, res_offset, res_batch_stride, ldc if ldr is None else ldr, out2, act2, bias2, bias2_batch_stride,
+                     w_batch_stride, w_group, out_f32, _sk_workspace())
     return a, out
 
 
@@ -241,28 +253,16 @@ def gemm_qkv(A, W, bias, Q, K, VT, norm_q, norm_k, cos, sin, **kw):
 
 
 def _gemm_qkv_args(A, W, bias, Q, K, VT, norm_q, norm_k, cos, sin, *, M, H, Spad, tok_off, rows_per_sample, batch=1, a_batch_stride=0,
-             lda=None, a_offset=0, eps=1e-6, q_scale=1.0, vt_perm=False, _act2=0, _bias2=None):
-    _req(A, torch.bfloat16, "A")
-    _req(W, torch.bfloat16, "W")
-    a = GemmArgs()
-    a.A = A.data_ptr() + a_offset * 2
-    a.a_batch_stride = a_batch_stride
-    a.lda = A.shape[-1] if lda is None else lda
-    a.W = W.data_ptr()
-    a.ldw = W.stride(-2)
-    a.bias = bias.data_ptr() if bias is not None else None
-    a.C = None
-    a.c_batch_stride, a.ldc = 0, 3 * H * 128
-    a.C2, a.act2, a.gate, a.gate_batch_stride, a.res, a.res_batch_stride, a.ldr = None, _act2, None, 0, None, 0, 0
-    a.bias2, a.bias2_batch_stride, a.w_batch_stride = (_bias2.data_ptr() if _bias2 is not None else None), 0, 0   # (_act2 / _bias2: tools only)
-    a.M, a.N, a.K, a.batch = M, 3 * H * 128, W.shape[-1], batch
-    a.act, a.out_f32 = ACT_NONE, 0
-    _set_ws(a)
-    q = QkvDesc()
-    q.norm_q, q.norm_k, q.cos, q.sin = norm_q.data_ptr(), norm_k.data_ptr(), cos.data_ptr(), (sin.data_ptr() if sin is not None else None)   # sin=None: `cos` is the pair-form table (rope_pairs)
-    q.Q, q.K, q.VT = Q.data_ptr(), K.data_ptr(), VT.data_ptr()
-    q.H, q.Spad, q.tok_off, q.rows_per_sample, q.eps, q.q_scale = H, Spad, tok_off, rows_per_sample, eps, q_scale
-    q.vt_perm = 1 if vt_perm else 0
+             lda=None, a_offset=0, eps=1e-6, q_scale=1.0, vt_perm=False, _act2=0, _bias2=None, _operands=torch.bfloat16):
+    # (_act2 / _bias2: tools only; _operands: FP8 from gemm_qkv_fp8)
+    suffix = "" if _operands is torch.bfloat16 else "8"
+    _req(A, _operands, "A" + suffix)
+    _req(W, _operands, "W" + suffix)
+    a = _gemm_struct(A, W, bias, None, M, 3 * H * 128, W.shape[-1], batch, A.shape[-1] if lda is None else lda, W.stride(-2), 3 * H * 128,
+                     a_offset, a_batch_stride, act2=_act2, bias2=_bias2, ws=_sk_workspace())
+    # sin=None: `cos` is the pair-form table (rope_pairs)
+    q = QkvDesc(norm_q.data_ptr(), norm_k.data_ptr(), cos.data_ptr(), _p(sin), Q.data_ptr(), K.data_ptr(), VT.data_ptr(), H, Spad, tok_off,
+                rows_per_sample, eps, q_scale, 1 if vt_perm else 0)
     return a, q
 
 
@@ -278,12 +278,10 @@ def attention(Q, K, VT, out, B, H, S, Spad, ldo, o_batch_stride, scale, o_offset
         # with the stream-K workspace of this stream / graph (the GEMMs' one): a partly filled last round of work items is cut along the key axis over
         # all CUs, chained through the workspace -- bit-identical to the undivided launch (include/x2i.h: x2i_attention_vp_ws_bf16)
         ws = _sk_workspace()
-        check(lib.x2i_attention_vp_ws_bf16(_p(Q), _p(K), _p(VT), C.c_void_p(out.data_ptr() + o_offset * 2), B, H, S, Spad, ldo,
-                                           o_batch_stride, scale, C.c_void_p(ws.buf.data_ptr()) if ws is not None else None,
-                                           ws.nbytes if ws is not None else 0, _stream()), "attention_vp")
+        check(lib.x2i_attention_vp_ws_bf16(_p(Q), _p(K), _p(VT), _off(out, o_offset), B, H, S, Spad, ldo, o_batch_stride, scale,
+                                           _p(ws.buf) if ws is not None else None, ws.nbytes if ws is not None else 0, _stream()), "attention_vp")
         return out
-    check(lib.x2i_attention_bf16(_p(Q), _p(K), _p(VT), C.c_void_p(out.data_ptr() + o_offset * 2), B, H, S, Spad, ldo,
-                                 o_batch_stride, scale, _stream()), "attention")
+    check(lib.x2i_attention_bf16(_p(Q), _p(K), _p(VT), _off(out, o_offset), B, H, S, Spad, ldo, o_batch_stride, scale, _stream()), "attention")
     return out
 
 
@@ -300,9 +298,8 @@ def ln_modulate(X, Y, B, S, D, S0, shift0, scale0, shift1, scale1, mod_bs, eps=1
     ldy = D if ldy is None else ldy
     x_bs = S * ldx if x_bs is None else x_bs
     y_bs = S * ldy if y_bs is None else y_bs
-    check(lib.x2i_ln_modulate_bf16(C.c_void_p(X.data_ptr() + 2 * x_offset), x_bs, ldx, C.c_void_p(Y.data_ptr() + 2 * y_offset),
-                                   y_bs, ldy, B, S, D, S0, _p(shift0), _p(scale0), _p(shift1), _p(scale1), mod_bs, eps,
-                                   _stream()), "ln_modulate")
+    check(lib.x2i_ln_modulate_bf16(_off(X, x_offset), x_bs, ldx, _off(Y, y_offset), y_bs, ldy, B, S, D, S0, _p(shift0), _p(scale0), _p(shift1),
+                                   _p(scale1), mod_bs, eps, _stream()), "ln_modulate")
     return Y
 
 
@@ -449,9 +446,6 @@ def to_f32(x):
 
 
 # ---------------------------------------------------------------------------------------------------- ControlNeXt ops
-from ._lib import ACT_RELU, ConvDesc  # noqa: E402
-
-
 def conv2d_nhwc(x, w_packed, bias, H, W, Cin, Cout, KH, KW, stride, pad, out=None, act=ACT_NONE, bias2=None, res=None,
                 c_offset=0, c_batch_stride=None, ldc=None, res_offset=0, res_batch_stride=None, ldr=None, up=False, pad_w=None, B=None,
                 a_batch_stride=None, a_offset=0, out_w=None, out_h=None, out_row_pitch=0, moments=None, moments_accumulate=False, w_group=0):
@@ -475,37 +469,18 @@ def conv2d_nhwc(x, w_packed, bias, H, W, Cin, Cout, KH, KW, stride, pad, out=Non
     OW = (W * uw + 2 * pw - KW) // stride + 1 if out_w is None else out_w
     if out is None:
         out = torch.empty((B, OH, OW, Cout), device=x.device, dtype=torch.bfloat16)
-    a = GemmArgs()
-    a.A = x.data_ptr() + 2 * a_offset
-    a.a_batch_stride = H * W * Cin if a_batch_stride is None else a_batch_stride
-    a.lda = Cin
-    a.W = w_packed.data_ptr()
-    a.ldw = KH * KW * Cin
-    a.bias = bias.data_ptr() if bias is not None else None
-    a.C = out.data_ptr() + 2 * c_offset
-    a.c_batch_stride = OH * OW * Cout if c_batch_stride is None else c_batch_stride
-    a.ldc = Cout if ldc is None else ldc
-    a.C2 = None
-    a.gate = None
-    a.res = (res.data_ptr() + 2 * res_offset) if res is not None else None
-    a.res_batch_stride = (OH * OW * Cout if res_batch_stride is None else res_batch_stride)
-    a.ldr = (Cout if ldr is None else ldr)
-    a.bias2 = bias2.data_ptr() if bias2 is not None else None
-    a.bias2_batch_stride = bias2.stride(0) if bias2 is not None else 0
-    a.M, a.N, a.K, a.batch = OH * OW, Cout, KH * KW * Cin, B
-    a.act = act
-    a.out_f32 = 0
-    a.w_batch_stride = Cout * KH * KW * Cin if w_group else 0
-    a.w_group = w_group
+    # no stream-K workspace on the convolution; res_batch_stride / ldr carry their defaults with or without a residual
+    a = _gemm_struct(x, w_packed, bias, out, OH * OW, Cout, KH * KW * Cin, B, Cin, KH * KW * Cin, Cout if ldc is None else ldc,
+                     a_offset, H * W * Cin if a_batch_stride is None else a_batch_stride, c_offset,
+                     OH * OW * Cout if c_batch_stride is None else c_batch_stride, act, None, 0, res, res_offset,
+                     OH * OW * Cout if res_batch_stride is None else res_batch_stride, Cout if ldr is None else ldr, None, 0, bias2,
+                     bias2.stride(0) if bias2 is not None else 0, Cout * KH * KW * Cin if w_group else 0, w_group)
     d = ConvDesc(H, W, Cin, KH, KW, stride, pad, up, 0 if pad_w is None else pad_w + 1, 0 if out_w is None else out_w,
                  0 if out_h is None else out_h, out_row_pitch)
     if moments is not None:
         _req(moments, torch.float32, "moments")
-        n = int(lib.x2i_conv_moments_scratch_floats(a.M, a.N, a.batch))
-        key = (x.device, "conv_moments")
-        if key not in _gn_scratch or _gn_scratch[key].numel() < n:
-            _gn_scratch[key] = torch.empty(n, device=x.device, dtype=torch.float32)
-        d.moments, d.moments_scratch, d.moments_accumulate = moments.data_ptr(), _gn_scratch[key].data_ptr(), 1 if moments_accumulate else 0
+        scratch = _scratch(x.device, "conv_moments", int(lib.x2i_conv_moments_scratch_floats(OH * OW, Cout, B)))
+        d.moments, d.moments_scratch, d.moments_accumulate = moments.data_ptr(), scratch.data_ptr(), 1 if moments_accumulate else 0
     check(lib.x2i_conv2d_nhwc_bf16(C.byref(a), C.byref(d), _stream()), "conv2d_nhwc")
     return out
 
@@ -537,11 +512,8 @@ def conv3x3_image(x_nchw, w, bias, moments=None):
     mp = sp = None
     if moments is not None:
         _req(moments, torch.float32, "moments")
-        n = int(lib.x2i_conv_moments_scratch_floats(H * W, Cout, B))
-        key = (x_nchw.device, "conv_moments")
-        if key not in _gn_scratch or _gn_scratch[key].numel() < n:
-            _gn_scratch[key] = torch.empty(n, device=x_nchw.device, dtype=torch.float32)
-        mp, sp = moments.data_ptr(), _gn_scratch[key].data_ptr()
+        scratch = _scratch(x_nchw.device, "conv_moments", int(lib.x2i_conv_moments_scratch_floats(H * W, Cout, B)))
+        mp, sp = moments.data_ptr(), scratch.data_ptr()
     check(lib.x2i_conv3x3_image_bf16(_p(x_nchw), _p(w), _p(bias), _p(out), B, Cin, H, W, Cout, mp, sp, _stream()), "conv3x3_image")
     return out
 
@@ -580,9 +552,6 @@ def conv_stem(x_nhwc, w, bias, Cout):
     return out
 
 
-_gn_scratch = {}
-
-
 def groupnorm_nhwc(x, weight, bias, G, eps, act=ACT_NONE, pre_add=None, post_add=None, out=None, w_group=0):
     """GroupNorm on NHWC bf16 [B, ..., C] with fused pre-add (f32 [B,C]), activation and post-add (bf16 like x).
     w_group > 0: weight / bias are [groups, C] and item b uses row b // w_group (x2i_groupnorm_nhwc_grouped_bf16)."""
@@ -591,12 +560,9 @@ def groupnorm_nhwc(x, weight, bias, G, eps, act=ACT_NONE, pre_add=None, post_add
     B, Cc = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * Cc)
     out = torch.empty_like(x) if out is None else out
-    n = lib.x2i_groupnorm_scratch_floats(B, G)
-    key = (x.device, n)
-    if key not in _gn_scratch:
-        _gn_scratch[key] = torch.empty(n, device=x.device, dtype=torch.float32)
+    n = lib.x2i_groupnorm_scratch_floats(B, G)   # (the scratch is keyed by its exact size)
     check(lib.x2i_groupnorm_nhwc_grouped_bf16(_p(x), _p(out), B, HW, Cc, G, _p(weight), _p(bias), w_group, eps, act, _p(pre_add), _p(post_add),
-                                              _p(_gn_scratch[key]), _stream()), "groupnorm_nhwc")
+                                              _p(_scratch(x.device, n, n)), _stream()), "groupnorm_nhwc")
     return out
 
 
@@ -621,12 +587,9 @@ def groupnorm_nhwc_from_moments(x, moments, weight, bias, G, eps, act=ACT_NONE, 
     B, Cc = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * Cc)
     out = torch.empty_like(x) if out is None else out
-    n = lib.x2i_groupnorm_scratch_floats(B, G)
-    key = (x.device, n)
-    if key not in _gn_scratch:
-        _gn_scratch[key] = torch.empty(n, device=x.device, dtype=torch.float32)
+    n = lib.x2i_groupnorm_scratch_floats(B, G)   # (the scratch is keyed by its exact size)
     check(lib.x2i_groupnorm_nhwc_from_moments_grouped_bf16(_p(x), _p(out), B, HW, Cc, G, _p(weight), _p(bias), w_group, eps, act, _p(moments),
-                                                           _p(pre_add), _p(post_add), _p(_gn_scratch[key]), _stream()), "groupnorm_nhwc_from_moments")
+                                                           _p(pre_add), _p(post_add), _p(_scratch(x.device, n, n)), _stream()), "groupnorm_nhwc_from_moments")
     return out
 
 
@@ -640,12 +603,6 @@ def softmax_rows_(x, scale=1.0):
 
 
 # ---------------------------------------------------------------------------------------------------- fp8 (e4m3) path
-from ._lib import Fp8Desc  # noqa: E402
-
-FP8 = torch.float8_e4m3fn
-E4M3_MAX = 448.0
-
-
 def quantize_rows_fp8(x, static_inv_scale=None):
     """bf16 [rows, cols] -> (e4m3 [rows, cols], f32 [rows] scales) with scale = amax / 448 per row; or, with
     `static_inv_scale`, (e4m3, None) with y = sat(x * static_inv_scale)."""
@@ -658,6 +615,10 @@ def quantize_rows_fp8(x, static_inv_scale=None):
     check(lib.x2i_quantize_rows_fp8(_p(x), rows, cols, x.stride(-2) if x.dim() > 1 else cols, _p(y), cols, _p(scale),
                                     1.0 if static_inv_scale is None else float(static_inv_scale), _stream()), "quantize_rows_fp8")
     return y, scale
+
+
+def _fp8_desc(a_scale, a_scale_batch_stride, w_scale, alpha, out_fp8=False, out_inv_scale=1.0):
+    return Fp8Desc(_p(a_scale), a_scale_batch_stride, _p(w_scale), float(alpha), 1 if out_fp8 else 0, float(out_inv_scale))
 
 
 def gemm_fp8(A8, W8, bias=None, out=None, *, M=None, N=None, K=None, batch=1, a_batch_stride=0, lda=None, a_offset=0, a_scale=None,
@@ -677,30 +638,10 @@ def gemm_fp8(A8, W8, bias=None, out=None, *, M=None, N=None, K=None, batch=1, a_
         if batch > 1:
             c_batch_stride = M * N
     ldc = N if ldc is None else ldc
-    esz = 1 if out_fp8 else 2
-    a = GemmArgs()
-    a.A = A8.data_ptr() + a_offset
-    a.a_batch_stride, a.lda = a_batch_stride, lda
-    a.W, a.ldw = W8.data_ptr(), W8.stride(-2)
-    a.bias = bias.data_ptr() if bias is not None else None
-    a.C = out.data_ptr() + c_offset * esz
-    a.c_batch_stride, a.ldc = c_batch_stride, ldc
-    a.C2, a.act2 = None, 0
-    a.gate = gate.data_ptr() if gate is not None else None
-    a.gate_batch_stride = gate_batch_stride
-    a.res = (res.data_ptr() + res_offset * 2) if res is not None else None
-    a.res_batch_stride = res_batch_stride
-    a.ldr = ldc if ldr is None else ldr
-    a.bias2, a.bias2_batch_stride, a.w_batch_stride = (_bias2.data_ptr() if _bias2 is not None else None), 0, 0   # (_act2 / _bias2: tools only)
-    a.act2 = _act2
-    a.M, a.N, a.K, a.batch = M, N, K, batch
-    a.act, a.out_f32 = act, 0
-    _set_ws(a)
-    f = Fp8Desc()
-    f.a_scale = a_scale.data_ptr() if a_scale is not None else None
-    f.a_scale_batch_stride = a_scale_batch_stride
-    f.w_scale = w_scale.data_ptr() if w_scale is not None else None
-    f.alpha, f.out_fp8, f.out_inv_scale = float(alpha), 1 if out_fp8 else 0, float(out_inv_scale)
+    a = _gemm_struct(A8, W8, bias, out, M, N, K, batch, lda, W8.stride(-2), ldc, a_offset, a_batch_stride, c_offset, c_batch_stride, act,
+                     gate, gate_batch_stride, res, res_offset, res_batch_stride, ldc if ldr is None else ldr, act2=_act2, bias2=_bias2,
+                     ws=_sk_workspace())   # (_act2 / _bias2: tools only)
+    f = _fp8_desc(a_scale, a_scale_batch_stride, w_scale, alpha, out_fp8, out_inv_scale)
     check(lib.x2i_gemm_fp8(C.byref(a), C.byref(f), _stream()), "gemm_fp8")
     return out
 
@@ -709,33 +650,10 @@ def gemm_qkv_fp8(A8, W8, bias, Q, K, VT, norm_q, norm_k, cos, sin, *, M, H, Spad
                  a_batch_stride=0, lda=None, a_offset=0, a_scale=None, a_scale_batch_stride=0, w_scale=None, alpha=1.0, eps=1e-6, q_scale=1.0,
                  vt_perm=False):
     """gemm_qkv on e4m3 operands (include/x2i.h: x2i_gemm_qkv_fp8): dequantised accumulators, then the same fused epilogue."""
-    lib = _lib.load()
-    _req(A8, FP8, "A8")
-    _req(W8, FP8, "W8")
-    a = GemmArgs()
-    a.A = A8.data_ptr() + a_offset
-    a.a_batch_stride = a_batch_stride
-    a.lda = A8.shape[-1] if lda is None else lda
-    a.W, a.ldw = W8.data_ptr(), W8.stride(-2)
-    a.bias = bias.data_ptr() if bias is not None else None
-    a.C = None
-    a.c_batch_stride, a.ldc = 0, 3 * H * 128
-    a.C2, a.act2, a.gate, a.gate_batch_stride, a.res, a.res_batch_stride, a.ldr = None, 0, None, 0, None, 0, 0
-    a.bias2, a.bias2_batch_stride, a.w_batch_stride = None, 0, 0
-    a.M, a.N, a.K, a.batch = M, 3 * H * 128, W8.shape[-1], batch
-    a.act, a.out_f32 = ACT_NONE, 0
-    _set_ws(a)
-    f = Fp8Desc()
-    f.a_scale = a_scale.data_ptr() if a_scale is not None else None
-    f.a_scale_batch_stride = a_scale_batch_stride
-    f.w_scale = w_scale.data_ptr() if w_scale is not None else None
-    f.alpha, f.out_fp8, f.out_inv_scale = float(alpha), 0, 1.0
-    q = QkvDesc()
-    q.norm_q, q.norm_k, q.cos, q.sin = norm_q.data_ptr(), norm_k.data_ptr(), cos.data_ptr(), (sin.data_ptr() if sin is not None else None)   # sin=None: `cos` is the pair-form table (rope_pairs)
-    q.Q, q.K, q.VT = Q.data_ptr(), K.data_ptr(), VT.data_ptr()
-    q.H, q.Spad, q.tok_off, q.rows_per_sample, q.eps, q.q_scale = H, Spad, tok_off, rows_per_sample, eps, q_scale
-    q.vt_perm = 1 if vt_perm else 0
-    check(lib.x2i_gemm_qkv_fp8(C.byref(a), C.byref(f), C.byref(q), _stream()), "gemm_qkv_fp8")
+    a, q = _gemm_qkv_args(A8, W8, bias, Q, K, VT, norm_q, norm_k, cos, sin, M=M, H=H, Spad=Spad, tok_off=tok_off, rows_per_sample=rows_per_sample,
+                          batch=batch, a_batch_stride=a_batch_stride, lda=lda, a_offset=a_offset, eps=eps, q_scale=q_scale, vt_perm=vt_perm, _operands=FP8)
+    f = _fp8_desc(a_scale, a_scale_batch_stride, w_scale, alpha)
+    check(_lib.load().x2i_gemm_qkv_fp8(C.byref(a), C.byref(f), C.byref(q), _stream()), "gemm_qkv_fp8")
 
 
 def ln_modulate_fp8(X, Y, Y8, row_scale, B, S, D, S0, shift0, scale0, shift1, scale1, mod_bs, eps=1e-6, x_bs=None, ldx=None,
@@ -748,17 +666,15 @@ def ln_modulate_fp8(X, Y, Y8, row_scale, B, S, D, S0, shift0, scale0, shift1, sc
     x_bs = S * ldx if x_bs is None else x_bs
     y_bs = S * ldy if y_bs is None else y_bs
     y8_bs = S * ldy8 if y8_bs is None else y8_bs
-    yp = C.c_void_p(Y.data_ptr() + 2 * y_offset) if Y is not None else C.c_void_p(0)
-    check(lib.x2i_ln_modulate_fp8(C.c_void_p(X.data_ptr() + 2 * x_offset), x_bs, ldx, yp, y_bs, ldy,
-                                  C.c_void_p(Y8.data_ptr() + y8_offset), y8_bs, ldy8, _p(row_scale), B, S, D, S0, _p(shift0), _p(scale0),
-                                  _p(shift1), _p(scale1), mod_bs, eps, _stream()), "ln_modulate_fp8")
+    check(lib.x2i_ln_modulate_fp8(_off(X, x_offset), x_bs, ldx, _off(Y, y_offset), y_bs, ldy, _off(Y8, y8_offset), y8_bs, ldy8, _p(row_scale),
+                                  B, S, D, S0, _p(shift0), _p(scale0), _p(shift1), _p(scale1), mod_bs, eps, _stream()), "ln_modulate_fp8")
     return Y8
 
 
 def attention_e4m3out(Q, K, VT, out8, B, H, S, Spad, ldo, o_batch_stride, scale, o_offset=0, out_inv_scale=1.0):
     """attention() writing e4m3 (include/x2i.h: x2i_attention_e4m3out); ldo / o_batch_stride / o_offset in bytes."""
     lib = _lib.load()
-    check(lib.x2i_attention_e4m3out(_p(Q), _p(K), _p(VT), C.c_void_p(out8.data_ptr() + o_offset), B, H, S, Spad, ldo, o_batch_stride,
+    check(lib.x2i_attention_e4m3out(_p(Q), _p(K), _p(VT), _off(out8, o_offset), B, H, S, Spad, ldo, o_batch_stride,
                                     scale, out_inv_scale, _stream()), "attention_e4m3out")
     return out8
 
@@ -766,8 +682,8 @@ def attention_e4m3out(Q, K, VT, out8, B, H, S, Spad, ldo, o_batch_stride, scale,
 def gated_residual_(X, T, gate, B, S, D, x_bs, ldx, t_bs, ldt, gate_bs, x_offset=0, t_offset=0):
     """X <- bf16(X + gate[b] * T) in place (include/x2i.h: x2i_gated_residual_bf16); offsets / strides in elements."""
     lib = _lib.load()
-    check(lib.x2i_gated_residual_bf16(C.c_void_p(X.data_ptr() + 2 * x_offset), x_bs, ldx, C.c_void_p(T.data_ptr() + 2 * t_offset), t_bs, ldt,
-                                      _p(gate), gate_bs, B, S, D, _stream()), "gated_residual")
+    check(lib.x2i_gated_residual_bf16(_off(X, x_offset), x_bs, ldx, _off(T, t_offset), t_bs, ldt, _p(gate), gate_bs, B, S, D, _stream()),
+          "gated_residual")
     return X
 
 
@@ -789,10 +705,6 @@ def transpose(x, out=None, *, batch=1, R=None, C=None, in_bs=0, ld_in=None, out_
     check(lib.x2i_transpose_bf16(_off(x, in_offset), in_bs, ld_in, _off(out, out_offset),
                                  out_bs, ld_out, batch, R, C, _stream()), "transpose")
     return out
-
-
-def _off(t, elems):
-    return C.c_void_p(t.data_ptr() + elems * t.element_size())
 
 
 def softmax_pad_(x, nz, Rt, Rv, Ct, Cv, scale, ld=None):
@@ -821,8 +733,8 @@ def ln_mod_bwd(X, dY, mult, dXin, dXout, partial, *, B, S, D, R, mult_is_scale=T
     dy_bs = S * ldy if dy_bs is None else dy_bs
     dx_bs = S * lddx if dx_bs is None else dx_bs
     check(_lib.load().x2i_ln_mod_bwd_bf16(_off(X, x_offset), x_bs, ldx, _off(dY, dy_offset), dy_bs, ldy, _p(mult), mult_bs,
-                                          1 if mult_is_scale else 0, _off(dXin, dx_offset) if dXin is not None else C.c_void_p(0),
-                                          _off(dXout, dx_offset), dx_bs, lddx, B, S, D, R, _p(partial), float(eps), _stream()), "ln_mod_bwd")
+                                          1 if mult_is_scale else 0, _off(dXin, dx_offset), _off(dXout, dx_offset), dx_bs, lddx, B, S, D, R, _p(partial),
+                                          float(eps), _stream()), "ln_mod_bwd")
 
 
 def gate_bwd(dX, T, gate, G, dT, partial, *, B, S, D, R, gate_bs=0, dx_bs=None, lddx=None, t_bs=None, ldt=None, g_bs=None, ldg=None,
@@ -836,8 +748,7 @@ def gate_bwd(dX, T, gate, G, dT, partial, *, B, S, D, R, gate_bs=0, dx_bs=None, 
     t_bs = S * ldt if t_bs is None else t_bs
     g_bs = S * ldg if g_bs is None else g_bs
     dt_bs = S * lddt if dt_bs is None else dt_bs
-    check(_lib.load().x2i_gate_bwd_bf16(_off(dX, dx_offset), dx_bs, lddx, _off(T, t_offset) if T is not None else C.c_void_p(0), t_bs, ldt,
-                                        _p(gate), gate_bs, _off(G, g_offset) if G is not None else C.c_void_p(0), g_bs, ldg,
+    check(_lib.load().x2i_gate_bwd_bf16(_off(dX, dx_offset), dx_bs, lddx, _off(T, t_offset), t_bs, ldt, _p(gate), gate_bs, _off(G, g_offset), g_bs, ldg,
                                         _off(dT, dt_offset), dt_bs, lddt, B, S, D, R, _p(partial), _stream()), "gate_bwd")
 
 
@@ -945,7 +856,7 @@ def attention_bwd(Q, K, V, QT, KT, dOh, dOT, lse2, Dv, dQ, dK, dV, B, H, S, Spad
 
 def attention_lse(Q, K, VT, out, lse2, B, H, S, Spad, ldo, o_batch_stride, scale, o_offset=0):
     """attention() that also writes the log2-sum-exp statistics lse2 f32 [B,H,Spad] (x2i_attention_lse_bf16)."""
-    check(_lib.load().x2i_attention_lse_bf16(_p(Q), _p(K), _p(VT), C.c_void_p(out.data_ptr() + o_offset * 2), _p(lse2), B, H, S, Spad, ldo,
+    check(_lib.load().x2i_attention_lse_bf16(_p(Q), _p(K), _p(VT), _off(out, o_offset), _p(lse2), B, H, S, Spad, ldo,
                                              o_batch_stride, float(scale), _stream()), "attention_lse")
 
 
@@ -955,17 +866,7 @@ def attention_bwd_prep(dO, O, Dv, B, H, S, Spad, *, do_bs, lddo, o_bs, ldo, do_o
 
 
 # ---------------------------------------------------------------------------------------------------- ControlNeXt backward
-_bwd_ws = {}
-
-
-def _bwd_workspace(device, floats, kind):
-    """Caller-owned f32 scratch of the backward entry points, one growing buffer per (device, kind); launches on one stream reuse it in order."""
-    key = (device, kind)
-    if key not in _bwd_ws or _bwd_ws[key].numel() < floats:
-        _bwd_ws[key] = torch.empty(max(int(floats), 1), device=device, dtype=torch.float32)
-    return _bwd_ws[key]
-
-
+# (the caller-owned f32 workspaces of these entry points are _scratch buffers, never empty: least=1)
 def _query(fn, *args):
     n = C.c_int64(0)
     check(fn(*args, C.byref(n)), fn.__name__)
@@ -990,7 +891,7 @@ def conv_wgrad(x, dy, dw, db, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, *, B
     if x.numel() < B * H * W * Cin or dy.numel() < dy_offset + (B - 1) * dbs + OH * OW * ldy - (ldy - Cout) or dw.numel() != Cout * Cin * KH * KW or \
             (db is not None and db.numel() != Cout):
         raise _lib.X2IError("conv_wgrad: x, dy, dw or db is smaller than the shape arguments say")
-    ws = _bwd_workspace(x.device, conv_wgrad_workspace_floats(B, OH, OW, Cin, Cout, KH, KW), "conv_wgrad")
+    ws = _scratch(x.device, "conv_wgrad", conv_wgrad_workspace_floats(B, OH, OW, Cin, Cout, KH, KW), least=1)
     check(lib.x2i_conv_wgrad_bf16(_p(x), _off(dy, dy_offset), dbs, ldy, _p(dw), _p(db), B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad,
                                   1 if accumulate else 0, _p(ws), ws.numel(), _stream()), "conv_wgrad")
     return dw
@@ -1007,7 +908,7 @@ def conv_stem_wgrad(x, dy, dw, db, accumulate=False):
     Cout = dy.shape[-1]
     if x.shape[-1] != 3 or tuple(dy.shape) != (B, (H + 1) // 2, (W + 1) // 2, Cout) or dw.numel() != Cout * 27 or (db is not None and db.numel() != Cout):
         raise _lib.X2IError("conv_stem_wgrad: x [B, H, W, 3], dy [B, H/2, W/2, Cout], dw [Cout, 3, 3, 3], db [Cout]")
-    ws = _bwd_workspace(x.device, _query(lib.x2i_conv_stem_wgrad_workspace_floats, B, H, W, Cout), "conv_stem_wgrad")
+    ws = _scratch(x.device, "conv_stem_wgrad", _query(lib.x2i_conv_stem_wgrad_workspace_floats, B, H, W, Cout), least=1)
     check(lib.x2i_conv_stem_wgrad_bf16(_p(x), _p(dy), _p(dw), _p(db), B, H, W, Cout, 1 if accumulate else 0, _p(ws), ws.numel(), _stream()),
           "conv_stem_wgrad")
     return dw
@@ -1027,7 +928,7 @@ def groupnorm_bwd(x, dy, weight, bias, G, eps, act=ACT_NONE, pre_add=None, dpre=
             any(t is not None and t.numel() != n for t, n in ((pre_add, B * Cc), (dpre, B * Cc), (dw, Cc), (db, Cc))):
         raise _lib.X2IError("groupnorm_bwd: dy / dx / dx_in shaped like x, pre_add / dpre [B, C], dw / db [C]")
     dx = torch.empty_like(x) if dx is None else dx
-    ws = _bwd_workspace(x.device, _query(lib.x2i_groupnorm_bwd_workspace_floats, B, HW, Cc, G), "groupnorm_bwd")
+    ws = _scratch(x.device, "groupnorm_bwd", _query(lib.x2i_groupnorm_bwd_workspace_floats, B, HW, Cc, G), least=1)
     check(lib.x2i_groupnorm_nhwc_bwd_bf16(_p(x), _p(dy), _p(weight), _p(bias), _p(pre_add), _p(dx), _p(dx_in), _p(dw), _p(db), _p(dpre), B, HW, Cc, G,
                                           float(eps), act, 1 if in_relu else 0, 1 if accumulate else 0, _p(ws), ws.numel(), _stream()),
           "groupnorm_bwd")
@@ -1085,7 +986,7 @@ def mse_loss_grad(pred, target, grad_scale=1.0, d_pred=None, loss=None):
     if d_pred.shape != pred.shape or d_pred.dtype != torch.bfloat16 or not d_pred.is_contiguous():
         raise _lib.X2IError("mse_loss_grad: d_pred must be a contiguous bf16 tensor shaped like pred")
     nb = mse_loss_workspace_floats(n)
-    ws = _bwd_workspace(pred.device, nb, "mse_loss")
+    ws = _scratch(pred.device, "mse_loss", nb, least=1)
     check(lib.x2i_mse_loss_grad_bf16(_p(pred), _p(target), _p(d_pred), n, float(grad_scale), _p(ws), ws.numel(), _stream()), "mse_loss_grad")
     loss = torch.empty((1,), device=pred.device, dtype=torch.float32) if loss is None else loss
     reduce_rows(ws, loss, np_=nb, len_=1, in_ps=1, alpha=1.0 / n)
