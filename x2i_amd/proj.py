@@ -249,15 +249,16 @@ class ProjFrontStage(nn.Module):
 
 class _ProjT5(nn.Module):
     """Legacy Proj / Proj2 / Proj3 (model_internvl/proj.py:149-211): LayerNorm -> Conv2d(C->1, 5x5) -> LayerNorm front stage and an
-    MLP / MLP2 head on the HIP path around a `transformers` T5Stack encoder (gated-gelu, relative attention bias), which stays on
-    PyTorch-ROCm as SURVEY.md section 8 row A3 allows.  Same constructor arguments and state-dict keys (norm0.*, conv.*, norm1.*,
+    MLP / MLP2 head on the HIP path around a T5Stack encoder (gated-gelu, relative attention bias).  By default that is the `transformers`
+    class on PyTorch-ROCm, as SURVEY.md section 8 row A3 allows; hip_t5=True builds x2i_amd.t5.T5Stack from the same configuration instead
+    (same parameter names, the encoder on the HIP path too).  Same constructor arguments and state-dict keys (norm0.*, conv.*, norm1.*,
     t5stack.*, mlp.*) as the reference classes; no reference script imports them (checkpoint compatibility only)."""
 
     mlp_cls = None      # MLP for Proj, MLP2 for Proj2 / Proj3
     t5_first = False    # Proj3 runs the T5Stack on every layer's sequence BEFORE the layer-fusion stage (:203-210)
 
     def __init__(self, in_channels=2, kernel_size=5, input_dim=896, output_dim0=768, output_dim1=4096, num_layers=4, num_heads=12,
-                 layer_norm_eps=1e-6, head_dim=64, device="cuda", dtype=torch.bfloat16):
+                 layer_norm_eps=1e-6, head_dim=64, device="cuda", dtype=torch.bfloat16, hip_t5=False):
         super().__init__()
         from transformers import T5Config
         from transformers.models.t5.modeling_t5 import T5Stack
@@ -273,7 +274,11 @@ class _ProjT5(nn.Module):
         conv.bias = _param(1, device=device, dtype=dtype)
         self.conv = conv
         self.norm1 = _LN(input_dim, device, dtype)
-        self.t5stack = T5Stack(config).to(device=device, dtype=dtype).eval().requires_grad_(False)
+        if hip_t5:
+            from .t5 import T5Stack as HipT5Stack
+            self.t5stack = HipT5Stack(config, device=device, dtype=dtype).eval()
+        else:
+            self.t5stack = T5Stack(config).to(device=device, dtype=dtype).eval().requires_grad_(False)
         self.mlp = self.mlp_cls(input_dim, output_dim1, output_dim1, output_dim0, layer_norm_eps, device=device, dtype=dtype)
 
     def _front(self, x):
