@@ -123,6 +123,19 @@ def load_vae(flux_path, device, synthetic=False):
     return AutoencoderKL.from_pretrained(flux_path, subfolder="vae", device=device)
 
 
+def load_text_encoders(flux_path, device, synthetic=False):
+    """Both prompt encoders on the HIP path (x2i_amd.text_encoders): `text_encoder/` (CLIP) and `text_encoder_2/` (T5) of the diffusers
+    pipeline directory; synthetic: FLUX's two encoder shapes (CLIP-L text, T5-XXL) with seeded random weights."""
+    from ..text_encoders import TextEncoders
+    if synthetic:
+        from ..clip import CLIPTextModel
+        from ..t5 import T5EncoderModel
+        t5 = T5EncoderModel(device=device, d_model=4096, d_kv=64, num_heads=64, d_ff=10240, num_layers=24, vocab_size=32128)
+        t5.encoder.init_random_(5)
+        return TextEncoders(CLIPTextModel(device=device, eos_token_id=2).init_random_(4), t5)
+    return TextEncoders.from_pretrained(flux_path, device)
+
+
 class SyntheticConditioner:
     """Stands in for the MLLM: seeded hidden states of the right [B, C, S, H] shape and activation scale."""
 
