@@ -87,6 +87,62 @@ class HiddenStateSlab:
         return self.slab
 
 
+class HipPrefill:
+    """HiddenStateSlab's `prefill(model, **inputs)` / `capture(run)` with the decoder stack itself on the HIP path (x2i_amd/qwen.py:
+    Qwen2DecoderStack, a bf16 copy of the decoder's weights on its device; the token table is shared).  During the call the decoder
+    module's `forward` is replaced ON THE INSTANCE: the surrounding model still builds `inputs_embeds` (vision / audio towers, the
+    embedding merge), `attention_mask` and `position_ids` as it always does, the replacement runs the HIP stack on them -- which writes
+    the [B, C, S, H] slab directly -- and hands the surrounding model the library's output object with last_hidden_state = slab[:, -1].
+    The original `forward` is restored afterwards, on exceptions too.  Only the FIRST decoder pass is served (the prompt pass): the stack
+    keeps no key/value cache, so a second pass -- a decode step of generate() -- raises; such callers need --full_generate."""
+
+    def __init__(self, model, check_mask=True):
+        from .qwen import Qwen2DecoderStack
+        self.decoder = find_decoder(model)
+        self.stack = Qwen2DecoderStack.from_hf(self.decoder)
+        self.n_layers = len(self.decoder.layers)
+        self.C = self.n_layers + 1
+        self.check_mask = check_mask
+        self.slab = None
+
+    def _forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None, use_cache=None, **kw):
+        from transformers.modeling_outputs import BaseModelOutputWithPast
+        if self.slab is not None:
+            raise RuntimeError("handoff.HipPrefill: the decoder ran a second time (a decode step of generate()?); the HIP stack serves the "
+                               "prompt pass only and keeps no key/value cache -- run with --full_generate (and without --hip_decoder) instead")
+        if isinstance(attention_mask, dict):
+            raise RuntimeError("handoff.HipPrefill: the decoder was handed prepared mask tensors (generate()?); it needs the 0/1 [B, S] attention_mask")
+        if past_key_values is not None and past_key_values.get_seq_length() > 0:
+            raise RuntimeError("handoff.HipPrefill: a non-empty key/value cache was passed; the HIP stack serves the prompt pass only (--full_generate)")
+        if inputs_embeds is not None:
+            inputs_embeds = inputs_embeds.to(torch.bfloat16)
+        self.slab = self.stack(inputs_embeds=inputs_embeds, input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
+                               check_mask=self.check_mask)
+        return BaseModelOutputWithPast(last_hidden_state=self.slab[:, -1], past_key_values=None)
+
+    @torch.no_grad()
+    def prefill(self, model, **inputs):
+        return self.capture(lambda: model(**inputs, use_cache=False))
+
+    @torch.no_grad()
+    def capture(self, run):
+        self.slab = None
+        had = "forward" in self.decoder.__dict__
+        saved = self.decoder.__dict__.get("forward")
+        self.decoder.forward = self._forward
+        try:
+            run()
+        finally:
+            if had:
+                self.decoder.forward = saved
+            else:
+                del self.decoder.forward
+        if self.slab is None:
+            raise RuntimeError("handoff: the decoder stack did not run")
+        slab, self.slab = self.slab, None
+        return slab
+
+
 def prefill_hidden_states(model, dtype=torch.bfloat16, **inputs):
     """Convenience wrapper: [B, C, S, H] conditioning tensor of `inputs` from one forward of `model`."""
     return HiddenStateSlab(find_decoder(model), dtype).prefill(model, **inputs)

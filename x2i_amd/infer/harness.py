@@ -68,6 +68,9 @@ def build_parser(family):
     p.add_argument("--no_graph", action="store_true")
     p.add_argument("--full_generate", action="store_true",
                    help="run the MLLM's 128-token generate() as the reference does instead of the single prefill forward")
+    p.add_argument("--hip_decoder", action="store_true",
+                   help="run the MLLM's decoder stack over the prompt on the HIP path (x2i_amd/qwen.py) instead of the library's forward; "
+                        "prefill only, so not with --full_generate or --use_answer")
     p.add_argument("--decode", action="store_true", help="with --synthetic: also run the (random-weight) VAE decoder and save images")
     return p
 

@@ -14,7 +14,7 @@ class QwenVLConditioner:
     """Qwen2_5_VLForConditionalGeneration prompt pass; inputs padded to 512 tokens, images resized to 128x128, videos at
     1 fps / 128*128 pixels, generate(max_new_tokens=128, output_hidden_states=True) -- infer/inference_qwenvl.py:136-180."""
 
-    def __init__(self, path, device, use_answer=False, prefill_only=True):
+    def __init__(self, path, device, use_answer=False, prefill_only=True, hip_decoder=False):
         from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
         self.model = Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
         self.processor = AutoProcessor.from_pretrained(path)
@@ -22,9 +22,12 @@ class QwenVLConditioner:
         # the prompt-pass states are all the reference keeps unless --use_answer: take them from ONE forward, written by
         # hooks straight into the [B,C,S,H] buffer (x2i_amd/handoff.py), instead of a 128-token generate() + torch.cat
         self.slab = None
+        if hip_decoder and not (prefill_only and not use_answer):
+            raise ValueError("--hip_decoder serves the prompt pass only: not with --full_generate or --use_answer")
         if prefill_only and not use_answer:
-            from ..handoff import HiddenStateSlab, find_decoder
-            self.slab = HiddenStateSlab(find_decoder(self.model))
+            from ..handoff import HiddenStateSlab, HipPrefill, find_decoder
+            # hip_decoder: the same one forward with the decoder stack itself on the HIP path (x2i_amd/qwen.py)
+            self.slab = HipPrefill(self.model) if hip_decoder else HiddenStateSlab(find_decoder(self.model))
 
     @torch.no_grad()
     def __call__(self, videos=None, images=None, audios=None, text_prompt=None):
@@ -79,7 +82,8 @@ def main(argv=None):
     kind = "qwen" + args.qwen_size
     device = "cuda:%d" % int(__import__("os").environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(device)
-    cond = SyntheticConditioner(kind, device) if args.synthetic else QwenVLConditioner(args.qwen_path, device, args.use_answer, prefill_only=not args.full_generate)
+    cond = SyntheticConditioner(kind, device) if args.synthetic else QwenVLConditioner(args.qwen_path, device, args.use_answer, prefill_only=not args.full_generate,
+                                                                                            hip_decoder=args.hip_decoder)
     Harness(args, kind, cond, device).run_tasks(tasks(args))
 
 

@@ -1,0 +1,330 @@
+"""The Qwen2 decoder prefill on the HIP path: a drop-in for the decoder stack inside every MLLM the reference conditions on -- `transformers`'
+Qwen2Model (MiniCPM-o's Qwen2.5-7B, InternVL2.5's Qwen2.5-3B / Qwen2-0.5B) and Qwen2_5_VLTextModel (Qwen2.5-VL 3B / 7B) -- run ONCE over
+the prompt and returning every layer's hidden state as the projector's input [B, C, S, H] (x2i_amd/handoff.py has the layout's story).
+
+Launch list of one layer (every launch in libx2i_hip.so; include/x2i_qwen.h, x2i_t5.h and x2i.h):
+  rms_rows      input_layernorm (Qwen2RMSNorm == T5LayerNorm)                 x2i_t5_rms_rows_bf16   (one launch per sample, see below)
+  gemm          stacked q|k|v projection + bias                               x2i_gemm_bf16
+  rope_split    rotate-half RoPE on q, k -> Q, K [B,H*,Spad,dk], V^T          x2i_qwen_rope_split_bf16
+  attention     causal, grouped key/value heads, per-sample key range         x2i_qwen_attention_bf16
+  gemm          o_proj + residual (one rounding)                              x2i_gemm_bf16
+  rms_rows      post_attention_layernorm
+  gemm          stacked [gate_proj; up_proj]
+  swiglu        silu(a) * b                                                   x2i_qwen_swiglu_bf16
+  gemm          down_proj + residual -> the next entry of the slab
+and one final rms_rows.  The slab IS the residual stream: layer i reads slab[:, i] and its down projection writes slab[:, i + 1] through
+the GEMM's residual epilogue (batch = B, M = S, the slab's batch stride); the last layer writes a scratch buffer that the final norm reads.
+No stack / cat copy.  The norm kernel addresses its rows by one stride, and the samples of slab[:, i] are C*S*H apart, so the two norms that
+touch the slab (input_layernorm reading it, the final norm writing it) are launched once per sample: nine launches per layer at B = 1,
+8 + B otherwise.
+
+Parameter names are the library's, so a decoder's state dict loads strictly; the q|k|v weights and biases and the gate|up weights are views
+into stacked storage (as T5Stack's are).  The vision and audio towers and the embedding merge stay on PyTorch: the stack takes
+`inputs_embeds` (or `input_ids`, a torch gather from embed_tokens).
+"""
+import torch
+import torch.nn as nn
+
+from . import ops, qwen_ops, t5_ops
+
+_FIELDS = dict(hidden_size=3584, num_attention_heads=28, num_key_value_heads=4, intermediate_size=18944, num_hidden_layers=28, rms_norm_eps=1e-6,
+               vocab_size=152064, hidden_act="silu", head_dim=None, rope_theta=1000000.0, rope_type="default", mrope_section=None,
+               layer_types=None, use_sliding_window=False)
+
+
+def rope_tables(position_ids, dk, theta, mrope_section=None, _scratch=None):
+    """f32 (cos, sin) [B, S, dk/2] in plain torch on the ids' device: the HALF tables of the library's rotary embedding (its own are these
+    concatenated with themselves), evaluated as the library evaluates them in float32 -- inv_freq = 1 / theta^(2k/dk) in f32, the angle its
+    f32 product with the position.  position_ids: [B, S], or [3, B, S] with mrope_section (e.g. [16, 24, 24]): chunk i of the dk/2
+    frequencies takes the positions of axis i % 3, which is what apply_multimodal_rotary_pos_emb selects.
+    (_scratch: a dict of preallocated buffers, the stack's; then only cos and sin are allocated.)"""
+    dev = position_ids.device
+    half = dk // 2
+    sc = {} if _scratch is None else _scratch
+    inv_freq = sc.get("inv_freq")
+    if inv_freq is None:
+        inv_freq = sc["inv_freq"] = (1.0 / (theta ** (torch.arange(0, dk, 2, dtype=torch.float) / dk))).to(dev)
+    if position_ids.dim() == 3:
+        if position_ids.shape[0] != 3 or mrope_section is None or sum(mrope_section) != half:
+            raise ValueError("rope_tables: position_ids [3, B, S] need an mrope_section that sums to dk/2 = %d (got %s, %r)"
+                             % (half, tuple(position_ids.shape), mrope_section))
+    elif position_ids.dim() != 2:
+        raise ValueError("rope_tables: position_ids must be [B, S] or [3, B, S] (got %s)" % (tuple(position_ids.shape),))
+    pos = sc.get("posf")
+    if pos is None or pos.shape != position_ids.shape:
+        pos = sc["posf"] = torch.empty(position_ids.shape, device=dev, dtype=torch.float32)
+    pos.copy_(position_ids)
+    B, S = position_ids.shape[-2:]
+    ang = sc.get("ang")
+    if ang is None or ang.shape != (B, S, half):
+        ang = sc["ang"] = torch.empty((B, S, half), device=dev, dtype=torch.float32)
+    if position_ids.dim() == 2:
+        torch.mul(pos[..., None], inv_freq, out=ang)
+    else:
+        c0 = 0
+        for i, n in enumerate(mrope_section):
+            torch.mul(pos[i % 3][..., None], inv_freq[c0:c0 + n], out=ang[..., c0:c0 + n])
+            c0 += n
+    return torch.cos(ang), torch.sin(ang)
+
+
+def key_ranges(attention_mask):
+    """(k_lo, k_hi) int32 [B] of a 0/1 mask [B, S] whose valid keys are one contiguous run per sample: k_lo the first valid position, k_hi =
+    k_lo + their count (an all-zero row gives the empty range [0, 0)).  Torch ops on the mask's device, no synchronisation."""
+    m = attention_mask != 0
+    k_lo = m.to(torch.int32).argmax(-1).to(torch.int32)   # the first maximum: the first valid position (0 for an all-zero row)
+    return k_lo, k_lo + m.sum(-1, dtype=torch.int32)
+
+
+def mask_state(attention_mask):
+    """(ok, all_ones) of a 0/1 mask [B, S] in ONE host read: ok -- every sample's valid keys are a non-empty contiguous run"""
+    m = attention_mask != 0
+    S = m.shape[-1]
+    cnt = m.sum(-1)
+    first = m.to(torch.int32).argmax(-1)
+    last = S - 1 - m.flip(-1).to(torch.int32).argmax(-1)
+    ok = ((cnt > 0) & (last - first + 1 == cnt)).all()
+    return tuple(bool(v) for v in torch.stack((ok, (cnt == S).all())).tolist())
+
+
+class _WB(nn.Module):
+    def __init__(self, weight, bias=None):
+        super().__init__()
+        as_param = lambda t: t if isinstance(t, nn.Parameter) else nn.Parameter(t, requires_grad=False)
+        self.weight = as_param(weight)
+        if bias is not None:
+            self.bias = as_param(bias)
+
+
+def _rope_fields(config):
+    """rope_theta / rope_type / mrope_section of a library config: `rope_parameters` (5.x) or `rope_theta` + `rope_scaling` (4.x, remote code)"""
+    rp = getattr(config, "rope_parameters", None) or getattr(config, "rope_scaling", None) or {}
+    out = {}
+    theta = rp.get("rope_theta", getattr(config, "rope_theta", None))
+    if theta is not None:
+        out["rope_theta"] = float(theta)
+    out["rope_type"] = rp.get("rope_type", rp.get("type", "default")) or "default"
+    if rp.get("mrope_section") is not None:
+        out["mrope_section"] = list(rp["mrope_section"])
+    return out
+
+
+def _config_fields(config, kw):
+    f = dict(_FIELDS)
+    if config is not None:
+        for k in f:
+            f[k] = getattr(config, k, f[k])
+        f.update(_rope_fields(config))
+    unknown = set(kw) - set(f)
+    if unknown:
+        raise TypeError("Qwen2DecoderStack: unknown configuration fields %s" % sorted(unknown))
+    f.update(kw)
+    return f
+
+
+class Qwen2DecoderStack(nn.Module):
+    """Prefill-only drop-in for transformers' Qwen2Model / Qwen2_5_VLTextModel (the module handoff.find_decoder finds).
+    forward(...) -> the hidden-state slab bf16 [B, num_layers + 1, S, H]."""
+
+    def __init__(self, config=None, embed_tokens=None, device="cuda", dtype=torch.bfloat16, **kw):
+        super().__init__()
+        f = _config_fields(config, kw)
+        if dtype != torch.bfloat16:
+            raise ValueError("x2i_amd: the HIP path computes in bf16 (fp32 statistics/accumulation)")
+        if f["hidden_act"] != "silu":
+            raise ValueError("x2i_amd Qwen2DecoderStack: hidden_act=%r is not built (silu only)" % (f["hidden_act"],))
+        if f["layer_types"] is not None and any(t != "full_attention" for t in f["layer_types"]):
+            raise ValueError("x2i_amd Qwen2DecoderStack: sliding-window layers are not built (layer_types=%r)" % (f["layer_types"],))
+        if f["layer_types"] is None and f["use_sliding_window"]:
+            raise ValueError("x2i_amd Qwen2DecoderStack: sliding-window layers are not built (use_sliding_window=True)")
+        if f["rope_type"] not in ("default", "mrope"):
+            raise ValueError("x2i_amd Qwen2DecoderStack: rope type %r is not built (default and mrope only)" % (f["rope_type"],))
+        D, Hq, Hkv, F = f["hidden_size"], f["num_attention_heads"], f["num_key_value_heads"], f["intermediate_size"]
+        dk = f["head_dim"] or D // Hq
+        if dk not in (64, 128):
+            raise ValueError("x2i_amd Qwen2DecoderStack: the HIP attention kernel is built for head widths 64 and 128 (got %r)" % (dk,))
+        if Hkv <= 0 or Hq % Hkv:
+            raise ValueError("x2i_amd Qwen2DecoderStack: num_attention_heads must be a multiple of num_key_value_heads")
+        if D % 8 or F % 8 or f["num_hidden_layers"] < 1:
+            raise ValueError("x2i_amd Qwen2DecoderStack: hidden_size and intermediate_size must be multiples of 8, and there must be a layer")
+        if f["mrope_section"] is not None and sum(f["mrope_section"]) != dk // 2:
+            raise ValueError("x2i_amd Qwen2DecoderStack: mrope_section %r does not sum to head_dim / 2 = %d" % (f["mrope_section"], dk // 2))
+        f["head_dim"] = dk
+        self.config = type("Qwen2DecoderStackConfig", (), dict(f))()
+        nq, nkv = Hq * dk, Hkv * dk
+        dev = torch.device(device)
+        self._fused = {}
+        self._views = []
+
+        def param(*shape):
+            return nn.Parameter(torch.empty(shape, device=dev, dtype=dtype), requires_grad=False)
+
+        def view(name, r0, r1):
+            p = nn.Parameter(self._fused[name][r0:r1], requires_grad=False)
+            self._views.append((p, name, slice(r0, r1)))
+            return p
+
+        self.embed_tokens = _WB(embed_tokens if embed_tokens is not None else param(f["vocab_size"], D))
+        layers = []
+        for i in range(f["num_hidden_layers"]):
+            self._fused["%d.qkv.w" % i] = torch.empty((nq + 2 * nkv, D), device=dev, dtype=dtype)
+            self._fused["%d.qkv.b" % i] = torch.empty((nq + 2 * nkv,), device=dev, dtype=dtype)
+            self._fused["%d.gu" % i] = torch.empty((2 * F, D), device=dev, dtype=dtype)
+            att = nn.Module()
+            for nm, r0, r1 in (("q_proj", 0, nq), ("k_proj", nq, nq + nkv), ("v_proj", nq + nkv, nq + 2 * nkv)):
+                att.add_module(nm, _WB(view("%d.qkv.w" % i, r0, r1), view("%d.qkv.b" % i, r0, r1)))
+            att.add_module("o_proj", _WB(param(D, nq)))
+            mlp = nn.Module()
+            mlp.add_module("gate_proj", _WB(view("%d.gu" % i, 0, F)))
+            mlp.add_module("up_proj", _WB(view("%d.gu" % i, F, 2 * F)))
+            mlp.add_module("down_proj", _WB(param(D, F)))
+            layer = nn.Module()
+            layer.add_module("self_attn", att)
+            layer.add_module("mlp", mlp)
+            layer.add_module("input_layernorm", _WB(param(D)))
+            layer.add_module("post_attention_layernorm", _WB(param(D)))
+            layers.append(layer)
+        self.layers = nn.ModuleList(layers)
+        self.norm = _WB(param(D))
+        self._ws = {}
+
+    # ------------------------------------------------------------------ nn.Module plumbing
+    @property
+    def dtype(self):
+        return torch.bfloat16
+
+    @property
+    def device(self):
+        return self.norm.weight.device
+
+    def _apply(self, fn, recurse=True):
+        # the stacked q|k|v and gate|up parameters are views: move the storage, re-point the views, then the ordinary parameters
+        for k in list(self._fused):
+            new = fn(self._fused[k])
+            if new.dtype != torch.bfloat16:
+                raise ValueError("x2i_amd Qwen2DecoderStack is bf16-only")
+            self._fused[k] = new
+        for p, name, sl in self._views:
+            p.data = self._fused[name][sl]
+        self._ws = {}
+        return super()._apply(fn, recurse)
+
+    @classmethod
+    def from_hf(cls, decoder, device=None):
+        """A copy of an instantiated library decoder (Qwen2Model / Qwen2_5_VLTextModel) on `device` (default: the decoder's).  The token
+        table is shared with the decoder, not copied, when it already is a bf16 tensor on that device."""
+        w = decoder.embed_tokens.weight
+        device = w.device if device is None else torch.device(device)
+        share = w.dtype == torch.bfloat16 and w.device == device
+        m = cls(decoder.config, embed_tokens=w.detach() if share else None, device=device)
+        sd = {k: v.detach().to(device=device, dtype=torch.bfloat16) for k, v in decoder.state_dict().items()}
+        m.load_state_dict(sd, strict=True)
+        return m
+
+    @torch.no_grad()
+    def init_random_(self, seed=0):
+        """Random weights in place on the device (tools and smoke runs; there are no checkpoints offline): linears N(0, 1 / fan_in), biases
+        0.1 N(0, 1), norms 1 + 0.1 N(0, 1), token table N(0, 1)."""
+        gen = torch.Generator(device=self.device).manual_seed(seed)
+        for n, p in self.named_parameters():
+            r = torch.randn(p.shape, device=p.device, generator=gen)
+            if n.endswith("norm.weight") or n.endswith("layernorm.weight"):
+                p.copy_(1.0 + 0.1 * r)
+            elif p.dim() == 1:
+                p.copy_(0.1 * r)
+            elif n.startswith("embed_tokens"):
+                p.copy_(r)
+            else:
+                p.copy_(r * p.shape[1] ** -0.5)
+        return self
+
+    # ------------------------------------------------------------------ workspace
+    def _workspace(self, B, S):
+        ws = self._ws.get((B, S))
+        if ws is not None:
+            return ws
+        c = self.config
+        D, dk, Hq, Hkv, F = c.hidden_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads, c.intermediate_size
+        nq, nkv, Spad = Hq * dk, Hkv * dk, qwen_ops.pad64(S)
+        dev = self.device
+        bf = dict(device=dev, dtype=torch.bfloat16)
+        # Q, K, V^T are zeroed once: rope_split writes rows / columns < S only, and the attention kernel needs the rest finite
+        ws = dict(Spad=Spad, X1=torch.empty((B * S, D), **bf), X2=torch.empty((B * S, D), **bf), NRM=torch.empty((B * S, D), **bf),
+                  QKV=torch.empty((B * S, nq + 2 * nkv), **bf), Q=torch.zeros((B, Hq, Spad, dk), **bf), K=torch.zeros((B, Hkv, Spad, dk), **bf),
+                  VT=torch.zeros((B, Hkv, dk, Spad), **bf), ATT=torch.empty((B * S, nq), **bf), HH=torch.empty((B * S, 2 * F), **bf),
+                  G=torch.empty((B * S, F), **bf), arange=torch.arange(S, device=dev)[None].expand(B, S), rope={})
+        self._ws = {(B, S): ws}  # keep one shape resident
+        return ws
+
+    # ------------------------------------------------------------------ forward
+    @torch.no_grad()
+    def forward(self, inputs_embeds=None, input_ids=None, attention_mask=None, position_ids=None, check_mask=True, use_cache=None,
+                past_key_values=None, **unused):
+        """-> bf16 [B, C, S, H], C = num_layers + 1: entry i < L is the INPUT of layer i, the last entry the final norm's output (the HF
+        `hidden_states` convention).  attention_mask: None or 0/1 [B, S] whose valid keys are one contiguous run per sample (left, right or
+        two-sided padding); check_mask=True verifies that with one host read (ValueError otherwise), False skips the check (graph capture).
+        position_ids: None (arange(S), as the library's forward), [B, S], or [3, B, S] / [4, B, S] for M-RoPE (of four, the first -- the text
+        positions the library builds its mask from -- is dropped).  After the first call at a (B, S) a forward allocates the slab and the two
+        RoPE tables and nothing else (with a mask: the two range vectors and their torch temporaries too).  Rows before a left-padded
+        sample's first valid token hold finite values that the library does not define."""
+        if (input_ids is None) == (inputs_embeds is None):
+            raise ValueError("Qwen2DecoderStack: pass exactly one of input_ids and inputs_embeds")
+        if use_cache or past_key_values is not None:
+            raise ValueError("x2i_amd Qwen2DecoderStack: prefill only; use_cache=True and past_key_values are not built")
+        c = self.config
+        D, dk, Hq, Hkv, F, eps, L = c.hidden_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads, c.intermediate_size, c.rms_norm_eps, len(self.layers)
+        nq, C = Hq * dk, len(self.layers) + 1
+        B, S = (input_ids if input_ids is not None else inputs_embeds).shape[:2]
+        k_lo = k_hi = None
+        if attention_mask is not None:
+            if tuple(attention_mask.shape) != (B, S):
+                raise ValueError("x2i_amd Qwen2DecoderStack: attention_mask must be a 0/1 [B, S] = [%d, %d] tensor (got %s)" % (B, S, tuple(attention_mask.shape)))
+            all_ones = False
+            if check_mask:
+                ok, all_ones = mask_state(attention_mask)
+                if not ok:
+                    raise ValueError("x2i_amd Qwen2DecoderStack: the valid keys of every sample must be one non-empty contiguous run of attention_mask")
+            if not all_ones:
+                k_lo, k_hi = key_ranges(attention_mask)
+        ws = self._workspace(B, S)
+        X1, X2, NRM, QKV, Q, K, VT, ATT, HH, G, Spad = (ws[k] for k in ("X1", "X2", "NRM", "QKV", "Q", "K", "VT", "ATT", "HH", "G", "Spad"))
+        dev = X1.device
+        if position_ids is None:
+            position_ids = ws["arange"]
+        elif position_ids.dim() == 3 and position_ids.shape[0] == 4:
+            position_ids = position_ids[1:]
+        if position_ids.dim() == 3 and c.mrope_section is None:
+            raise ValueError("x2i_amd Qwen2DecoderStack: three position axes need an mrope_section in the configuration")
+        if tuple(position_ids.shape[-2:]) != (B, S):
+            position_ids = position_ids.expand(*position_ids.shape[:-2], B, S)
+        cos, sin = rope_tables(position_ids.to(dev), dk, c.rope_theta, c.mrope_section, _scratch=ws["rope"])
+        slab = torch.empty((B, C, S, D), device=dev, dtype=torch.bfloat16)
+        if input_ids is not None:
+            if input_ids.device != dev:
+                raise ops._lib.X2IError("x2i_amd: input_ids must live on the model's device (got %s)" % input_ids.device)
+            for b in range(B):
+                torch.index_select(self.embed_tokens.weight, 0, input_ids[b], out=slab[b, 0])   # the token lookup is a torch gather
+        else:
+            ops._req(inputs_embeds, torch.bfloat16, "inputs_embeds")
+            slab[:, 0].copy_(inputs_embeds)
+        M, sbs, SD = B * S, C * S * D, S * D
+        scale = dk ** -0.5
+        for i, layer in enumerate(self.layers):
+            for b in range(B):   # (the samples of slab[:, i] are C*S*D apart; the norm's rows have one stride)
+                t5_ops.rms_rows(slab[b, i], layer.input_layernorm.weight, eps, out=NRM[b * S:(b + 1) * S])
+            ops.gemm(NRM, self._fused["%d.qkv.w" % i], self._fused["%d.qkv.b" % i], out=QKV, M=M)
+            qwen_ops.rope_split(QKV, cos, sin, Q, K, VT, B, S, Spad, Hq, Hkv, dk)
+            qwen_ops.attention(Q, K, VT, ATT, B, Hq, Hkv, S, Spad, dk, scale, nq, S * nq, k_lo, k_hi)
+            ops.gemm(ATT, layer.self_attn.o_proj.weight, out=X1, M=S, batch=B, a_batch_stride=S * nq, c_batch_stride=SD, ldc=D,
+                     res=slab, res_offset=i * SD, res_batch_stride=sbs, ldr=D)
+            t5_ops.rms_rows(X1, layer.post_attention_layernorm.weight, eps, out=NRM)
+            ops.gemm(NRM, self._fused["%d.gu" % i], out=HH, M=M)
+            qwen_ops.swiglu(HH, out=G)
+            if i + 1 < L:
+                ops.gemm(G, layer.mlp.down_proj.weight, out=slab, M=S, batch=B, a_batch_stride=S * F, c_offset=(i + 1) * SD, c_batch_stride=sbs,
+                         ldc=D, res=X1, res_batch_stride=SD, ldr=D)
+            else:
+                ops.gemm(G, layer.mlp.down_proj.weight, out=X2, M=M, res=X1, ldr=D)
+        for b in range(B):
+            t5_ops.rms_rows(X2[b * S:(b + 1) * S], self.norm.weight, eps, out=slab[b, L])
+        return slab
