@@ -1,4 +1,4 @@
-/* x2i_clip.h -- extension header of libx2i_hip.so: the CLIP text encoder's kernels (csrc/clip.hip).
+/* x2i_clip.h -- extension header of libx2i_hip.so: the CLIP text encoder's kernels (csrc/clip.hip, csrc/encoder_attention.hip).
  *
  * The conventions are those of x2i.h and x2i_t5.h (device pointers owned by the caller, raw bf16 storage, `stream` a hipStream_t
  * passed as void* and the last argument, work enqueued and never synchronised, no allocation, 0 or a negative X2I_ERR_* code with

@@ -1,4 +1,4 @@
-/* x2i_qwen.h -- extension header of libx2i_hip.so: the Qwen2 decoder prefill's kernels (csrc/qwen.hip).
+/* x2i_qwen.h -- extension header of libx2i_hip.so: the Qwen2 decoder prefill's kernels (csrc/qwen.hip, csrc/encoder_attention.hip).
  *
  * The conventions are those of x2i.h, x2i_t5.h and x2i_clip.h (device pointers owned by the caller, raw bf16 storage, `stream` a
  * hipStream_t passed as void* and the last argument, work enqueued and never synchronised, no allocation, 0 or a negative X2I_ERR_*

@@ -1,4 +1,4 @@
-/* x2i_t5.h -- extension header of libx2i_hip.so: the T5 encoder's kernels (csrc/t5.hip).
+/* x2i_t5.h -- extension header of libx2i_hip.so: the T5 encoder's kernels (csrc/t5.hip, csrc/encoder_attention.hip).
  *
  * The conventions are those of x2i.h (device pointers owned by the caller, raw bf16 storage, `stream` a hipStream_t passed as
  * void*, work enqueued and never synchronised, no allocation, 0 or a negative X2I_ERR_* code with the message in

@@ -108,6 +108,19 @@ def test_attention_masks_future_keys_by_index_under_adversarial_magnitudes(clip_
     CR.check_attention("clip_attention anti, flipped future", O2, CR.attention_reference(Q, K2, V, S, SCALE), CR.TOL_O)
 
 
+@pytest.mark.parametrize("B,H,S", [(2, 3, 77), (1, 2, 130)])
+def test_attention_is_the_qwen_kernel_without_groups_or_ranges(clip_ops, B, H, S):
+    """x2i_clip_attention_bf16 launches the causal kernel of x2i_qwen_attention_bf16 with Hq = Hkv and no key ranges: the two entry points
+    agree bit for bit.  Ragged in one query block; a second query block, one row reaching tile 2, Spad = 192 (no multiple of 128)"""
+    from x2i_amd import qwen_ops
+    Q, K, V = CR.attention_inputs(B, H, S, 64, seed=3000 * S + H, device=DEV)
+    O, _ = run_attention(clip_ops, Q, K, V, S)
+    buf = poisoned(B, S, H * 64)
+    qwen_ops.attention(Q, K, V.transpose(-1, -2).contiguous(), buf, B, H, H, S, Q.shape[2], 64, SCALE, H * 64, S * H * 64)
+    assert torch.equal(buf.reshape(B, S, H, 64).permute(0, 2, 1, 3), O)
+    assert not bool(is_sentinel(buf).any())
+
+
 def test_attention_refuses_other_head_widths(clip_ops):
     from x2i_amd._lib import X2IError
     Q, K, V = CR.attention_inputs(1, 1, 6, 64, seed=1, device=DEV)

@@ -176,6 +176,25 @@ def load():
     return lib
 
 
+def bind_extension(lib, exports, header_name):
+    """Set the prototypes of an extension header on lib, the CDLL object of load(); the caller does so once per CDLL object.  exports:
+    name -> argtypes, all returning int; such entry points are not in _EXPORTS (include/x2i.h's table is closed under its ABI version), so a
+    missing symbol means a stale build."""
+    for name, argtypes in exports.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise X2IError("x2i_amd: %s does not export %s (include/%s) (stale build? run `python -m x2i_amd.build`)" % (LIB_PATH, name, header_name))
+        fn.argtypes = argtypes
+        fn.restype = C.c_int
+    return lib
+
+
+def pad64(n):
+    """The padded sequence length (Spad) of the extensions' Q / K / V^T: the next multiple of the 64-key attention tile."""
+    return (n + 63) // 64 * 64
+
+
 _option_epoch = 0
 
 

@@ -1,0 +1,106 @@
+// Pieces the encoder extension files share (t5.hip, clip.hip, qwen.hip, encoder_attention.hip): the attention kernel's constants and its
+// LDS-DMA load, the bf16 chunk unpacker, the V -> V^T tile transposer of the two head-split kernels and the row-chunk activation kernel
+// behind the gated GELU, SwiGLU and quick-GELU entry points.  Other .hip files keep private helpers of the same names in their own anonymous
+// namespaces, so these stay out of x2i_common.h and stand in the anonymous namespace too: every includer gets its own copy, and a file that has
+// both this header and a helper of its own of one of these names does not compile.
+#pragma once
+#include "x2i_common.h"
+
+namespace {
+
+constexpr int KVB = 64;               // keys per attention tile
+constexpr float NEG_BIG = -1.0e30f;   // a masked score
+constexpr float M_FLOOR = -1.0e15f;   // where the causal mode's running maximum starts (encoder_attention.hip)
+constexpr float LOG2E = 1.4426950408889634f;
+constexpr int RELBIAS_RMAX = 2047;   // largest clamp distance of the relative-bias mode: the table region of the LDS image is 16 KiB
+
+__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+__device__ __forceinline__ void unpack8(const uint4& p, float (&v)[8]) {
+  v[0] = __uint_as_float(p.x << 16); v[1] = __uint_as_float(p.x & 0xffff0000u);
+  v[2] = __uint_as_float(p.y << 16); v[3] = __uint_as_float(p.y & 0xffff0000u);
+  v[4] = __uint_as_float(p.z << 16); v[5] = __uint_as_float(p.z & 0xffff0000u);
+  v[6] = __uint_as_float(p.w << 16); v[7] = __uint_as_float(p.w & 0xffff0000u);
+}
+
+inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// ------------------------------------------------------------------------------------------------------------------- V -> V^T
+// The whole workgroup (256 threads) transposes tokens s0 .. s0+63 of one head: v points at the head's dk columns of token 0 (row stride
+// ld), vt at the head's VT rows [dk][Spad].  V goes through an LDS tile [64 tokens][dk + 2] and leaves as 16-byte pieces of VT rows
+// (scalar stores in the one piece that straddles S: columns >= S stay untouched).  dk <= 128.
+__device__ __forceinline__ void v_tile_to_vt(const bf16_t* __restrict__ v, long long ld, bf16_t* __restrict__ vt, int s0, int S, int Spad, int dk) {
+  __shared__ uint32_t tile[64 * (128 + 2) / 2];
+  const int tid = threadIdx.x;
+  const int ck = dk >> 3;           // 16-byte chunks per head row
+  const int pitch = (dk + 2) >> 1;  // LDS row pitch in dwords
+  for (int c = tid; c < 64 * ck; c += 256) {
+    const int tok = c / ck, ch = c - tok * ck;
+    const int s = s0 + tok;
+    uint4 p = make_uint4(0u, 0u, 0u, 0u);
+    if (s < S) p = *(const uint4*)(v + s * ld + ch * 8);
+    uint32_t* t = tile + tok * pitch + ch * 4;
+    t[0] = p.x; t[1] = p.y; t[2] = p.z; t[3] = p.w;
+  }
+  __syncthreads();
+  const bf16_t* tb = (const bf16_t*)tile;
+  for (int i = tid; i < dk * 8; i += 256) {
+    const int tc = i & 7, d = i >> 3;
+    const int s = s0 + tc * 8;
+    if (s >= S) continue;
+    bf16_t e[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) e[j] = tb[(tc * 8 + j) * (2 * pitch) + d];
+    bf16_t* dst = vt + (long long)d * Spad + s;
+    if (s + 8 <= S) {
+      *(uint4*)dst = make_uint4(e[0] | ((uint32_t)e[1] << 16), e[2] | ((uint32_t)e[3] << 16), e[4] | ((uint32_t)e[5] << 16), e[6] | ((uint32_t)e[7] << 16));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (s + j < S) dst[j] = e[j];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------- row activations
+// One thread per 16-byte chunk of Y: y = bf16(act(a)), or with GATED, rows [a (F) | b (F)] -> y = bf16(act(a) * b).
+struct GeluTanhAct { __device__ __forceinline__ float operator()(float x) const { return gelu_tanh_f(x); } };
+struct SiluAct { __device__ __forceinline__ float operator()(float x) const { return silu_f(x); } };
+struct QuickGeluAct { __device__ __forceinline__ float operator()(float x) const { return quick_gelu_f(x); } };
+
+template <class Act, bool GATED>
+__global__ __launch_bounds__(256) void row_act_kernel(const bf16_t* __restrict__ X, long long ldx, bf16_t* __restrict__ Y, long long ldy,
+                                                      long long rows, int F) {
+  const Act act;
+  const int nc = F >> 3;
+  const long long total = rows * nc;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long row = i / nc;
+    const int c = (int)(i - row * nc);
+    const bf16_t* src = X + row * ldx + c * 8;
+    float a[8], g[8];
+    unpack8(*(const uint4*)src, a);
+    if constexpr (GATED) unpack8(*(const uint4*)(src + F), g);
+    uint32_t o[4];
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) {
+      // one rounding: the activation stays f32 until the gate has multiplied it (the library rounds it to bf16 in between)
+      if constexpr (GATED) o[j >> 1] = pack_bf16x2(__fmul_rn(act(a[j]), g[j]), __fmul_rn(act(a[j + 1]), g[j + 1]));
+      else o[j >> 1] = pack_bf16x2(act(a[j]), act(a[j + 1]));
+    }
+    *(uint4*)(Y + row * ldy + c * 8) = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+template <class Act, bool GATED>
+int launch_row_act(const char* what, const void* X, long long ldx, void* Y, long long ldy, long long rows, int F, hipStream_t stream) {
+  const long long chunks = rows * (F / 8);
+  const unsigned blocks = (unsigned)((chunks + 255) / 256 < 8192 ? (chunks + 255) / 256 : 8192);
+  hipLaunchKernelGGL((row_act_kernel<Act, GATED>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)X, ldx, (bf16_t*)Y, ldy, rows, F);
+  return x2i_check_launch(what);
+}
+
+}  // namespace

@@ -134,6 +134,11 @@ __device__ __forceinline__ void norm_rope8(const float (&x)[8], float r, const f
 }
 __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.7071067811865476f)); }
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
+// x * sigmoid(1.702 x) = x / (1 + exp2(-1.702 log2(e) x)): the form (and the v_exp_f32 / v_rcp_f32 pair) of silu_f
+__device__ __forceinline__ float quick_gelu_f(float x) {
+  constexpr float C = (float)(-1.702 * 1.4426950408889634);
+  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(C * x));
+}
 
 // activation codes shared by every kernel and by the C ABI (include/x2i.h)
 enum { X2I_ACT_NONE = 0, X2I_ACT_GELU_TANH = 1, X2I_ACT_GELU_ERF = 2, X2I_ACT_SILU = 3, X2I_ACT_RELU = 4 };

@@ -39,6 +39,20 @@ int x2i_launch_attention_pp(const void* Q, const void* K, const void* VT, void* 
 // hand-scheduled one-wave-per-SIMD form (attention_w4.hip, generated K-tile loop); X2I_ERR_STATE = not served (alignment)
 int x2i_launch_attention_w4(const void* Q, const void* K, const void* VT, void* O, int B, int H, int S, int Spad, int ldo, long long o_bs,
                             float scale_log2, int prescale, hipStream_t stream, float* lse, int out8, float oinv);
+/* ---- the encoder extensions' attention (encoder_attention.hip), behind x2i_t5_attention_bf16 / x2i_clip_attention_bf16 / x2i_qwen_attention_bf16.
+   The refusals those entry points share, under the entry point's name and in two parts, because each entry point has checks of its own (R, scale)
+   between them: _shape is the Spad rule; _launch the work-item count and the alignment of the output rows and of Q, K, VT, where `heads` is the
+   entry point's name for the query head count and `align_tail` what its alignment message says about k_lo / k_hi (null pointers where it has none) */
+int x2i_encoder_attention_refuse_shape(const char* name, int B, int H, int S, int Spad);
+int x2i_encoder_attention_refuse_launch(const char* name, const char* heads, const char* align_tail, const void* Q, const void* K, const void* VT,
+                                        const void* k_lo, const void* k_hi, const void* O, int B, int H, int S, int dk, int ldo, long long o_bs);
+int x2i_launch_encoder_attention_relbias(const void* Q, const void* K, const void* VT, const float* tab, void* O, int B, int H, int S, int Spad,
+                                         int dk, int R, int ldo, long long o_bs, hipStream_t stream);   // T5; dk 32 / 64 / 128
+int x2i_launch_encoder_attention_causal(const void* Q, const void* K, const void* VT, const int* k_lo, const int* k_hi, void* O, int B, int Hq,
+                                        int Hkv, int S, int Spad, int dk, float scale, int ldo, long long o_bs,
+                                        hipStream_t stream);   // Qwen2; dk 64 / 128; k_lo, k_hi both null: the whole prefix
+int x2i_launch_encoder_attention_causal_plain(const void* Q, const void* K, const void* VT, void* O, int B, int H, int S, int Spad, float scale,
+                                              int ldo, long long o_bs, hipStream_t stream);   // CLIP; dk 64, ungrouped heads, the whole prefix
 int x2i_launch_qkv_split(const void* qkv0, const void* qkv1, int ld0, int ld1, int B, int S, int S0, int H,
                          const void* nq0, const void* nk0, const void* nq1, const void* nk1, const float* cosp,
                          const float* sinp, void* Q, void* K, void* VT, int Spad, float eps, hipStream_t stream);

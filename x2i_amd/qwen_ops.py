@@ -1,4 +1,4 @@
-"""ctypes binding and torch-tensor wrappers of the extension header include/x2i_qwen.h: the Qwen2 decoder prefill's kernels (csrc/qwen.hip).
+"""ctypes binding and torch-tensor wrappers of the extension header include/x2i_qwen.h: the Qwen2 decoder prefill's kernels (csrc/qwen.hip, csrc/encoder_attention.hip).
 
 The three entry points are not in _lib._EXPORTS (include/x2i.h's table is closed under ABI version 5); they get their argtypes on the
 CDLL object of _lib.load() the first time this module is used.  Like ops.py, t5_ops.py and clip_ops.py: PyTorch supplies device memory and
@@ -21,6 +21,9 @@ _EXPORTS = {
     "x2i_qwen_swiglu_bf16": [_vp, _i64, _vp, _i64, _i64, _i32, _vp],
 }
 
+pad64 = _lib.pad64
+
+
 _bound = None
 
 
@@ -29,20 +32,8 @@ def load():
     global _bound
     lib = _lib.load()
     if _bound is not lib:
-        for name, argtypes in _EXPORTS.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise X2IError("x2i_amd: %s does not export %s (include/x2i_qwen.h) (stale build? run `python -m x2i_amd.build`)"
-                               % (_lib.LIB_PATH, name))
-            fn.argtypes = argtypes
-            fn.restype = C.c_int
-        _bound = lib
+        _bound = _lib.bind_extension(lib, _EXPORTS, "x2i_qwen.h")
     return lib
-
-
-def pad64(n):
-    return (n + 63) // 64 * 64
 
 
 def _range(t, B, name):
