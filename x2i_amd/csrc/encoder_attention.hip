@@ -1,6 +1,7 @@
-// The one flash-attention kernel of the encoder extensions: T5's relative-position-bias attention (include/x2i_t5.h) and the causal
-// attention of the CLIP text encoder and the Qwen2 decoder prefill (include/x2i_clip.h, include/x2i_qwen.h).  The extern "C" entry points
-// stay in t5.hip, clip.hip and qwen.hip and come here through the launchers at the end (x2i_kernels.h).  bf16 in and out, f32 arithmetic.
+// The one flash-attention kernel of the encoder extensions: T5's relative-position-bias attention (include/x2i_t5.h), the causal attention
+// of the CLIP text encoder and the Qwen2 decoder prefill (include/x2i_clip.h, include/x2i_qwen.h) and the segmented attention of the
+// Qwen2.5-VL vision tower (include/x2i_vit.h).  The extern "C" entry points stay in t5.hip, clip.hip, qwen.hip and vit.hip and come here
+// through the launchers at the end (x2i_kernels.h).  bf16 in and out, f32 arithmetic.
 //
 // The mapping is that of attention.hip (its 4-wave plain-HIP kernel) with the head width as a template parameter
 //   * one workgroup = 4 waves, each wave owns 32 query rows; K / V^T stream through LDS in 64-key tiles, double-buffered LDS-DMA
@@ -40,15 +41,31 @@
 //     than THR exactly as it would leave NEG_BIG, and l > 0 in every written row
 //
 // CAUSAL_PLAIN (CLIP, 64-wide heads): CAUSAL with rep = 1 and the range [0, S) known at compile time; the same values bit for bit
+//
+// SEGMENT (the Qwen2.5-VL vision tower): bidirectional, a key range [rlo, rhi) per QUERY ROW (device memory [B][S], clamped into [0, S];
+// [0, S) without the arrays): the windows and frames of one packed sequence, whose boundaries fall anywhere inside a tile, a wave or a
+// workgroup.  CAUSAL's scale, M_FLOOR and zero rows
+//   * a lane owns one query row, so the range is two integers per lane; the wave reduces them to the union of its rows' non-empty ranges and
+//     to their intersection, the workgroup reduces the four unions through LDS: the walk runs from min(rlo) / 64 to (max(rhi) - 1) / 64 and
+//     is derived here, not taken from the host and not assumed monotonic in the row
+//   * a wave computes a tile only between the first and the last tile of its union; in a tile that is not wholly inside the intersection
+//     the scores outside the lane's own range become NEG_BIG before the maximum and the sum see them (a ragged last tile: rhi <= S)
+//   * the defer-max test is per row here, not per wave: the rows of a wave belong to different segments, and a row's result is a function
+//     of its own range alone, bit for bit (encoder_attention_tile.inc)
+//   * heads of 80 (DW = 80 in DK = 128): Q / K rows and the V^T head are 128 wide, and the tiles are staged whole; the score product takes
+//     the 5 of 8 d-steps that hold data and the P V product 3 of 4 d-blocks, so columns 80..127 of Q / K and rows 96..127 of V^T never
+//     reach an MFMA; rows 80..95 of V^T give rows 80..95 of O^T -- an MFMA's output row depends on that row of V^T alone -- which the
+//     epilogue does not store.  The result does not depend on what the padding holds
 #include "encoder_common.h"
 #include "x2i_kernels.h"
 #include <type_traits>
 
 namespace {
 
-enum { RELBIAS = 0, CAUSAL = 1, CAUSAL_PLAIN = 2 };
+enum { RELBIAS = 0, CAUSAL = 1, CAUSAL_PLAIN = 2, SEGMENT = 3 };
 
-template <int DK, int MODE>
+// DW: the head's width of data inside rows of DK elements (SEGMENT's 80-wide heads stored 128 wide); DW == DK everywhere else
+template <int DK, int MODE, int DW = DK>
 __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                               const bf16_t* __restrict__ VT, const float* __restrict__ tab,
                                                               const int* __restrict__ k_lo, const int* __restrict__ k_hi,
@@ -61,8 +78,9 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
   constexpr int CK = DK / 8;            // 16-byte chunks per K row
   constexpr int RPB = 16 / CK;          // K rows per 256-byte bank row
   constexpr int CH = DK / 32;           // chunks per thread per tile (64 * CK / 256)
-  constexpr int NDS = DK / 16;          // d-steps of the score product
-  constexpr int NDB = DK / 32;          // 32-wide d-blocks of O^T
+  constexpr int NDS = DW / 16;          // d-steps of the score product (those that hold data)
+  constexpr int NDB = (DW + 31) / 32;   // 32-wide d-blocks of O^T (the last one of DW = 80 is half data; its other half is never stored)
+  static_assert(DW <= DK && DW % 16 == 0 && (MODE == SEGMENT || DW == DK), "a narrower head is SEGMENT's");
   constexpr int THR = 8;                // defer-max threshold (exp2 domain), as attention.hip
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -87,7 +105,39 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
   const bf16_t* Vh = VT + bg * DK * Spad;
   float* tl = (float*)(smem + 2 * (KTILE + VTILE));
   int klo = 0, khi = S;
-  if constexpr (MODE == RELBIAS) {
+  // SEGMENT only.  rlo, rhi: this lane's key range.  Wave-uniform: w_lomax / w_himin, the range that every row of the wave shares (a tile
+  // inside it needs no mask), and tw_lo, the first tile the wave computes (t_wave below is the last)
+  [[maybe_unused]] int rlo = 0, rhi = 0, w_lomax = 0, w_himin = 0, tw_lo = 0, seg_lo = 0, seg_hi = 0, seg_wave = -1;
+  if constexpr (MODE == SEGMENT) {
+    // the row's key range (k_lo / k_hi are [B][S] here), clamped into [0, S]: the host never sees these values, and no tile outside
+    // [0, Spad) may be staged.  Rows >= S (never written) take row S - 1's, so that no lane of a computing wave is special
+    const long long ri = (long long)b * S + min(q0 + li, S - 1);
+    rlo = k_lo ? min(max(k_lo[ri], 0), S) : 0;
+    rhi = k_hi ? min(max(k_hi[ri], 0), S) : S;
+    // union (an empty row adds nothing to it) and intersection over the wave's 32 rows; both half-waves hold the same rows
+    int ulo = rhi > rlo ? rlo : S, uhi = rhi > rlo ? rhi : 0, ilo = rlo, ihi = rhi;
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) {
+      ulo = min(ulo, __shfl_xor(ulo, o));
+      uhi = max(uhi, __shfl_xor(uhi, o));
+      ilo = max(ilo, __shfl_xor(ilo, o));
+      ihi = min(ihi, __shfl_xor(ihi, o));
+    }
+    ulo = __builtin_amdgcn_readfirstlane(ulo);
+    uhi = __builtin_amdgcn_readfirstlane(uhi);
+    w_lomax = __builtin_amdgcn_readfirstlane(ilo);
+    w_himin = __builtin_amdgcn_readfirstlane(ihi);
+    if (q0 >= S) { ulo = S; uhi = 0; }   // (wave-uniform) a wave past S computes nothing and asks for no tile
+    if (uhi > ulo) { tw_lo = ulo / KVB; seg_wave = (uhi - 1) / KVB; }
+    // the workgroup's walk: the union over its four waves, through LDS (behind the tiles, which nothing has touched yet)
+    int* red = (int*)tl;
+    if (lane == 0) { red[wave] = ulo; red[4 + wave] = uhi; }
+    __syncthreads();
+    seg_lo = min(min(red[0], red[1]), min(red[2], red[3]));
+    seg_hi = max(max(red[4], red[5]), max(red[6], red[7]));
+    seg_lo = __builtin_amdgcn_readfirstlane(seg_lo);
+    seg_hi = __builtin_amdgcn_readfirstlane(seg_hi);
+  } else if constexpr (MODE == RELBIAS) {
     // the head's bias table into LDS, in the exp2 domain
     for (int i = tid; i < 2 * R + 1; i += NT) tl[i] = tab[(long long)h * (2 * R + 1) + i] * LOG2E;
   } else if constexpr (RANGED) {
@@ -149,7 +199,11 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
   // causal modes only.  t_wave (wave-uniform): the last tile this wave computes (the one its first row lies in), and none for a wave past S or
   // wholly before klo.  qlim: the last key of this lane's row
   [[maybe_unused]] int t_wave = 0, qlim = 0;
-  if constexpr (MODE != RELBIAS) {
+  if constexpr (MODE == SEGMENT) {
+    t_lo = seg_lo / KVB;
+    ntiles = seg_hi > seg_lo ? (seg_hi - 1) / KVB - t_lo + 1 : 0;
+    t_wave = seg_wave;
+  } else if constexpr (MODE != RELBIAS) {
     t_lo = klo / KVB;
     const int t_hi = (min(min(S, qt * 128 + 128), khi) - 1) / KVB;
     ntiles = khi > klo ? t_hi - t_lo + 1 : 0;
@@ -185,13 +239,14 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
   // CAUSAL: the zero row, selected on a row sum that no counted key entered: rows before klo, an empty range, and waves that computed no tile
   // (their accumulators are still 0; 0 * finite V^T is 0 in the rows of a computing wave)
   const float inv = (MODE == RELBIAS || l_run > 0.f) ? 1.f / l_run : 0.f;
-  bf16_t* orow = O + (long long)b * o_bs + (long long)q * ldo + h * DK;
+  bf16_t* orow = O + (long long)b * o_bs + (long long)q * ldo + h * DW;
   if ((((uintptr_t)O) & 15) == 0 && (ldo & 7) == 0 && (o_bs & 7) == 0) {
     // half-wave exchange: two 8-byte fragments of neighbouring d-groups become one 16-byte store per lane
 #pragma unroll
     for (int db = 0; db < NDB; ++db)
 #pragma unroll
       for (int g = 0; g < 4; g += 2) {
+        if (db * 32 + 8 * g >= DW) continue;   // (compile time) the padding of a narrower head
         const uint32_t a0 = pack_bf16x2(oacc[db][4 * g] * inv, oacc[db][4 * g + 1] * inv);
         const uint32_t a1 = pack_bf16x2(oacc[db][4 * g + 2] * inv, oacc[db][4 * g + 3] * inv);
         const uint32_t b0 = pack_bf16x2(oacc[db][4 * g + 4] * inv, oacc[db][4 * g + 5] * inv);
@@ -205,6 +260,7 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
     for (int db = 0; db < NDB; ++db)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
+        if (db * 32 + 8 * g >= DW) continue;   // (compile time)
         const int d = db * 32 + 8 * g + 4 * hi;
         *(uint2*)(orow + d) = make_uint2(pack_bf16x2(oacc[db][4 * g] * inv, oacc[db][4 * g + 1] * inv),
                                          pack_bf16x2(oacc[db][4 * g + 2] * inv, oacc[db][4 * g + 3] * inv));
@@ -212,15 +268,16 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
   }
 }
 
-template <int DK, int MODE>
+template <int DK, int MODE, int DW = DK>
 int launch(const char* what, const void* Q, const void* K, const void* VT, const float* tab, const int* k_lo, const int* k_hi, void* O, int B, int H,
            int rep, int S, int Spad, int R, float scale2, int ldo, long long o_bs, hipStream_t stream) {
   constexpr int TILES = 2 * 2 * KVB * DK * 2;
-  const int rc = x2i_ensure_dynamic_smem((const void*)encoder_attn_kernel<DK, MODE>, TILES + (MODE == RELBIAS ? (2 * RELBIAS_RMAX + 2) * 4 : 0));
+  constexpr int TAIL = MODE == SEGMENT ? 32 : 0;   // SEGMENT: the four waves' key ranges
+  const int rc = x2i_ensure_dynamic_smem((const void*)encoder_attn_kernel<DK, MODE, DW>, TILES + TAIL + (MODE == RELBIAS ? (2 * RELBIAS_RMAX + 2) * 4 : 0));
   if (rc) return rc;
-  const size_t shm = TILES + (MODE == RELBIAS ? (size_t)((2 * R + 1 + 3) & ~3) * 4 : 0);
+  const size_t shm = TILES + TAIL + (MODE == RELBIAS ? (size_t)((2 * R + 1 + 3) & ~3) * 4 : 0);
   const dim3 grid((unsigned)(((S + 127) / 128) * H * B));
-  hipLaunchKernelGGL((encoder_attn_kernel<DK, MODE>), grid, dim3(256), shm, stream, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)VT, tab, k_lo,
+  hipLaunchKernelGGL((encoder_attn_kernel<DK, MODE, DW>), grid, dim3(256), shm, stream, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)VT, tab, k_lo,
                      k_hi, (bf16_t*)O, H, rep, S, Spad, R, scale2, ldo, o_bs, B);
   return x2i_check_launch(what);
 }
@@ -264,4 +321,14 @@ int x2i_launch_encoder_attention_causal(const void* Q, const void* K, const void
 int x2i_launch_encoder_attention_causal_plain(const void* Q, const void* K, const void* VT, void* O, int B, int H, int S, int Spad, float scale,
                                               int ldo, long long o_bs, hipStream_t stream) {
   return launch<64, CAUSAL_PLAIN>("clip_attention", Q, K, VT, nullptr, nullptr, nullptr, O, B, H, 1, S, Spad, 0, scale * LOG2E, ldo, o_bs, stream);
+}
+
+// The Qwen2.5-VL vision tower: bidirectional, a key range per query row (row_lo, row_hi: [B][S], or both null for [0, S)); heads of 80 are
+// the 128-wide tile with 5 of its 8 d-steps and 3 of its 4 d-blocks
+int x2i_launch_encoder_attention_segment(const void* Q, const void* K, const void* VT, const int* row_lo, const int* row_hi, void* O, int B, int H,
+                                         int S, int Spad, int dk, float scale, int ldo, long long o_bs, hipStream_t stream) {
+  const char* what = "vit_attention";
+  if (dk == 64) return launch<64, SEGMENT>(what, Q, K, VT, nullptr, row_lo, row_hi, O, B, H, 1, S, Spad, 0, scale * LOG2E, ldo, o_bs, stream);
+  if (dk == 80) return launch<128, SEGMENT, 80>(what, Q, K, VT, nullptr, row_lo, row_hi, O, B, H, 1, S, Spad, 0, scale * LOG2E, ldo, o_bs, stream);
+  return launch<128, SEGMENT>(what, Q, K, VT, nullptr, row_lo, row_hi, O, B, H, 1, S, Spad, 0, scale * LOG2E, ldo, o_bs, stream);
 }

@@ -2,13 +2,14 @@
 // with LAST (a compile-time bool) set where the walk knows that this is the last tile.  Not a translation unit of its own.
 // Names it takes from the including scope:
 //   the frame's     n (index of the tile in the walk), LAST
-//   template        DK, MODE; constants KTILE, VTILE, NDS, NDB, THR, RANGED (and KVB, NEG_BIG, LOG2E, RELBIAS of the file)
+//   template        DK, MODE; constants KTILE, VTILE, NDS, NDB, THR, RANGED (and KVB, NEG_BIG, LOG2E, RELBIAS, SEGMENT of the file)
 //   read            smem, tl, qf, stage, t_lo, ntiles, t_wave, q0, q, qlim, klo, khi, S, R, scale2, hi, k_row_off, k_swz, v_row_off, v_swz
+//                   SEGMENT: tw_lo, rlo, rhi, w_lomax, w_himin
 //   read and written  oacc, m_run, l_run
     const int t = t_lo + n;
     const int buf = n & 1;
     if (MODE == RELBIAS ? !LAST : n + 1 < ntiles) stage(buf ^ 1, (t + 1) * KVB);   // (workgroup-uniform)
-    if (MODE == RELBIAS || t <= t_wave) {                // (wave-uniform)
+    if (MODE == RELBIAS || (t <= t_wave && (MODE != SEGMENT || t >= tw_lo))) {   // (wave-uniform)
       const char* kb = smem + buf * (KTILE + VTILE);
       const char* vb = kb + KTILE;
 
@@ -54,6 +55,23 @@
               if (key >= S) sacc[u][r] = NEG_BIG;
             }
         }
+      } else if constexpr (MODE == SEGMENT) {
+        // ---- scores into the exp2 domain: one multiply by scale * log2 e
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) sacc[u][r] *= scale2;
+        if (kv0 < w_lomax || kv0 + KVB > w_himin) {   // (wave-uniform) the tile is not wholly inside every row's range (a ragged last tile: rhi <= S)
+          const int dn = rlo - kv0 - 8 * hi;
+          const int up = rhi - kv0 - 8 * hi;
+#pragma unroll
+          for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int c = u * 32 + 16 * (r >> 3) + (r & 7);
+              if (c < dn || c >= up) sacc[u][r] = NEG_BIG;
+            }
+        }
       } else {
         // ---- scores into the exp2 domain: one multiply by scale * log2 e
 #pragma unroll
@@ -83,7 +101,12 @@
       // (A row's first real score leaves NEG_BIG or M_FLOOR by far more than THR, so the test fails and m_new is real; a CAUSAL row that has
       // seen no counted key keeps M_FLOOR, against which a masked score still exponentiates to 0.)
       float m_new = fmaxf(m_run, mx);
-      if (__all(m_new - m_run <= (float)THR)) m_new = m_run;
+      if constexpr (MODE == SEGMENT) {
+        // per ROW: the rows of a wave belong to different segments, and a wave-wide test would let the scores of one segment decide which
+        // reference another segment's rows exponentiate against -- the same value, other roundings.  A row's result is a function of its
+        // own range alone, bit for bit; the rescale below is still skipped when no row moved (and multiplies the others by exactly 1)
+        if (m_new - m_run <= (float)THR) m_new = m_run;
+      } else if (__all(m_new - m_run <= (float)THR)) m_new = m_run;
       const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
       float psum = 0.f;
 #pragma unroll

@@ -39,7 +39,8 @@ int x2i_launch_attention_pp(const void* Q, const void* K, const void* VT, void* 
 // hand-scheduled one-wave-per-SIMD form (attention_w4.hip, generated K-tile loop); X2I_ERR_STATE = not served (alignment)
 int x2i_launch_attention_w4(const void* Q, const void* K, const void* VT, void* O, int B, int H, int S, int Spad, int ldo, long long o_bs,
                             float scale_log2, int prescale, hipStream_t stream, float* lse, int out8, float oinv);
-/* ---- the encoder extensions' attention (encoder_attention.hip), behind x2i_t5_attention_bf16 / x2i_clip_attention_bf16 / x2i_qwen_attention_bf16.
+/* ---- the encoder extensions' attention (encoder_attention.hip), behind x2i_t5_attention_bf16 / x2i_clip_attention_bf16 / x2i_qwen_attention_bf16 /
+   x2i_vit_attention_bf16.
    The refusals those entry points share, under the entry point's name and in two parts, because each entry point has checks of its own (R, scale)
    between them: _shape is the Spad rule; _launch the work-item count and the alignment of the output rows and of Q, K, VT, where `heads` is the
    entry point's name for the query head count and `align_tail` what its alignment message says about k_lo / k_hi (null pointers where it has none) */
@@ -53,6 +54,9 @@ int x2i_launch_encoder_attention_causal(const void* Q, const void* K, const void
                                         hipStream_t stream);   // Qwen2; dk 64 / 128; k_lo, k_hi both null: the whole prefix
 int x2i_launch_encoder_attention_causal_plain(const void* Q, const void* K, const void* VT, void* O, int B, int H, int S, int Spad, float scale,
                                               int ldo, long long o_bs, hipStream_t stream);   // CLIP; dk 64, ungrouped heads, the whole prefix
+int x2i_launch_encoder_attention_segment(const void* Q, const void* K, const void* VT, const int* row_lo, const int* row_hi, void* O, int B, int H,
+                                         int S, int Spad, int dk, float scale, int ldo, long long o_bs,
+                                         hipStream_t stream);   // Qwen2.5-VL vision tower; dk 64 / 80 (stored 128 wide) / 128; ranges [B][S] or both null
 int x2i_launch_qkv_split(const void* qkv0, const void* qkv1, int ld0, int ld1, int B, int S, int S0, int H,
                          const void* nq0, const void* nk0, const void* nq1, const void* nk1, const float* cosp,
                          const float* sinp, void* Q, void* K, void* VT, int Spad, float eps, hipStream_t stream);

@@ -143,6 +143,55 @@ class HipPrefill:
         return slab
 
 
+def find_visual(model):
+    """The vision tower of a Qwen2.5-VL model: `model.visual` (Qwen2_5_VLModel) or `model.model.visual` (Qwen2_5_VLForConditionalGeneration)"""
+    for m in (model, getattr(model, "model", None)):
+        v = getattr(m, "visual", None) if m is not None else None
+        if isinstance(v, nn.Module):
+            return v
+    raise RuntimeError("handoff: no vision tower (model.visual / model.model.visual) found in %s" % type(model).__name__)
+
+
+class HipVision:
+    """The vision tower behind `model.visual` on the HIP path (x2i_amd/qwen_vision.py: Qwen2_5VisionTower, a bf16 copy of the tower's weights on
+    its device).  install() replaces the tower module's `forward` ON THE INSTANCE and remove() restores it; between the two the surrounding
+    model's get_image_features / get_video_features and its embedding merge run as they always do and get the library's output object from
+    the HIP tower.  Also a context manager.  Independent of HipPrefill: under either kind of slab, and under generate()."""
+
+    def __init__(self, model):
+        from .qwen_vision import Qwen2_5VisionTower
+        self.visual = find_visual(model)
+        self.tower = Qwen2_5VisionTower.from_hf(self.visual)
+        self.calls = 0
+        self._installed = False
+
+    def _forward(self, hidden_states, grid_thw=None, **kw):
+        self.calls += 1
+        return self.tower(hidden_states, grid_thw=grid_thw)
+
+    def install(self):
+        if not self._installed:
+            self._had = "forward" in self.visual.__dict__
+            self._saved = self.visual.__dict__.get("forward")
+            self.visual.forward = self._forward
+            self._installed = True
+        return self
+
+    def remove(self):
+        if self._installed:
+            if self._had:
+                self.visual.forward = self._saved
+            else:
+                del self.visual.forward
+            self._installed = False
+
+    def __enter__(self):
+        return self.install()
+
+    def __exit__(self, *exc):
+        self.remove()
+
+
 def prefill_hidden_states(model, dtype=torch.bfloat16, **inputs):
     """Convenience wrapper: [B, C, S, H] conditioning tensor of `inputs` from one forward of `model`."""
     return HiddenStateSlab(find_decoder(model), dtype).prefill(model, **inputs)

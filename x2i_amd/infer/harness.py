@@ -71,6 +71,9 @@ def build_parser(family):
     p.add_argument("--hip_decoder", action="store_true",
                    help="run the MLLM's decoder stack over the prompt on the HIP path (x2i_amd/qwen.py) instead of the library's forward; "
                         "prefill only, so not with --full_generate or --use_answer")
+    p.add_argument("--hip_vision", action="store_true",
+                   help="run the MLLM's vision tower (Qwen2.5-VL's model.visual) on the HIP path (x2i_amd/qwen_vision.py) instead of the "
+                        "library's forward; independent of --hip_decoder")
     p.add_argument("--decode", action="store_true", help="with --synthetic: also run the (random-weight) VAE decoder and save images")
     return p
 

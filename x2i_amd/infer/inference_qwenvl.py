@@ -14,7 +14,7 @@ class QwenVLConditioner:
     """Qwen2_5_VLForConditionalGeneration prompt pass; inputs padded to 512 tokens, images resized to 128x128, videos at
     1 fps / 128*128 pixels, generate(max_new_tokens=128, output_hidden_states=True) -- infer/inference_qwenvl.py:136-180."""
 
-    def __init__(self, path, device, use_answer=False, prefill_only=True, hip_decoder=False):
+    def __init__(self, path, device, use_answer=False, prefill_only=True, hip_decoder=False, hip_vision=False):
         from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
         self.model = Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
         self.processor = AutoProcessor.from_pretrained(path)
@@ -28,6 +28,13 @@ class QwenVLConditioner:
             from ..handoff import HiddenStateSlab, HipPrefill, find_decoder
             # hip_decoder: the same one forward with the decoder stack itself on the HIP path (x2i_amd/qwen.py)
             self.slab = HipPrefill(self.model) if hip_decoder else HiddenStateSlab(find_decoder(self.model))
+
+        # hip_vision: the vision tower behind model.visual on the HIP path (x2i_amd/qwen_vision.py), under either kind of slab and under
+        # generate() alike: the surrounding model still calls it through get_image_features / get_video_features
+        self.vision = None
+        if hip_vision:
+            from ..handoff import HipVision
+            self.vision = HipVision(self.model).install()
 
     @torch.no_grad()
     def __call__(self, videos=None, images=None, audios=None, text_prompt=None):
@@ -83,7 +90,7 @@ def main(argv=None):
     device = "cuda:%d" % int(__import__("os").environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(device)
     cond = SyntheticConditioner(kind, device) if args.synthetic else QwenVLConditioner(args.qwen_path, device, args.use_answer, prefill_only=not args.full_generate,
-                                                                                            hip_decoder=args.hip_decoder)
+                                                                                            hip_decoder=args.hip_decoder, hip_vision=args.hip_vision)
     Harness(args, kind, cond, device).run_tasks(tasks(args))
 
 

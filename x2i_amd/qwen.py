@@ -19,8 +19,9 @@ touch the slab (input_layernorm reading it, the final norm writing it) are launc
 8 + B otherwise.
 
 Parameter names are the library's, so a decoder's state dict loads strictly; the q|k|v weights and biases and the gate|up weights are views
-into stacked storage (as T5Stack's are).  The vision and audio towers and the embedding merge stay on PyTorch: the stack takes
-`inputs_embeds` (or `input_ids`, a torch gather from embed_tokens).
+into stacked storage (as T5Stack's are).  The audio towers and the embedding merge stay on PyTorch, and so do the vision towers but for
+Qwen2.5-VL's, which has a HIP path of its own (x2i_amd/qwen_vision.py): the stack takes `inputs_embeds` (or `input_ids`, a torch gather
+from embed_tokens).
 """
 import torch
 import torch.nn as nn
