@@ -79,8 +79,8 @@ const char* x2i_last_error(void);
  * kernel, 9 = the hand-scheduled one-wave-per-SIMD kernel for any scale, 12 = the hand-scheduled kernel on 16x16x32 MFMAs (V^T span-permuted by the
  * caller -- tools and tests); any other value: the 4-wave kernel),
  * "conv5_variant" (0),
- * "fp8" (0; 2 = x2i_ln_modulate_fp8 keeps its per-row kernel at D = 3072, bit-identical A/B); "last_gemm_tile" is a read-back for tests: the tile edge of the kernel the
- * last GEMM / conv launch took (256, 128, 0 = generic kernel; +1000 = a peeled 128^2 tail launch followed).  Unknown names
+ * "fp8" (0; 2 = x2i_ln_modulate_fp8 keeps its per-row kernel at D = 3072, bit-identical A/B); "last_gemm_tile" is a read-back for tests: the kernel form the
+ * last GEMM / conv launch took (256, 128, 0 = generic kernel; +1000 = a peeled 128^2 tail launch followed; every code: DESIGN.md section 4).  Unknown names
  * return X2I_ERR_ARG.  Every setting selects between
  * kernels with identical results (bit-identical where the tests say so); the measurement-only kernels ("wrong results by
  * design" instruments) are NOT in this library -- they are compiled only into libx2i_hip_ablate.so (-DX2I_ABLATION), where

@@ -58,7 +58,7 @@ X2IOptions make_options() {
   o.attn_streamk = env_int("X2I_ATTN_STREAMK", 1);
   o.conv5_variant = env_int("X2I_CONV5_VARIANT", 0);
   o.fp8 = env_int("X2I_FP8", 0);
-  o.last_gemm_tile = -1;
+  o.last_gemm_tile = X2I_FORM_NONE;
   o.attn_ablate = env_int("X2I_ATTN_ABLATE", 0);
   return o;
 }

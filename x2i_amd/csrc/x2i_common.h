@@ -54,12 +54,28 @@ struct X2IOptions {
                           // caller's workspace: bit-identical; default); 0 = whole items only                                X2I_ATTN_STREAMK
   int conv5_variant;      // matrix-core projector conv: 0 = automatic form choice; 1 = plain stages, 2 = pipelined, 3 = two row blocks   X2I_CONV5_VARIANT
   int fp8;                // 2 = x2i_ln_modulate_fp8 keeps its per-row kernel at the model's width (A/B against the four-rows-per-wave form); else unused   X2I_FP8
-  int last_gemm_tile;     // read-only introspection for the parity tests: tile edge of the kernel the last GEMM / conv launch used
-                          // (256, 128, 0 = generic kernel), + 1000 when a peeled 128^2 tail launch followed the 256^2 launch
+  int last_gemm_tile;     // read-only introspection for tests, bench.py and tools/: the X2IGemmForm of the last GEMM / conv launch
   // measurement-only library (libx2i_hip_ablate.so, -DX2I_ABLATION); ignored by the product library
   int attn_ablate;        // >= 100: attention_w16.hip cuts its stream-K items at key tile (value - 100) (tools/attn_sk_bench.py --cut)   X2I_ATTN_ABLATE
 };
 X2IOptions& x2i_options();
+// Kernel form of a GEMM / convolution launch, as gemm.hip's plan chooses it (form -> kernel -> condition) and as
+// X2IOptions::last_gemm_tile reads afterwards.  The values are read by tests, bench.py and tools/: they do not change.
+enum X2IGemmForm {
+  X2I_FORM_NONE = -1,            // no GEMM launched yet
+  X2I_FORM_GENERIC = 0,          // one thread per output (gemm.hip): tiny or unaligned problems
+  X2I_FORM_128 = 128,            // 128^2 tiles, one per workgroup (gemm128.hip); convolutions too
+  X2I_FORM_256 = 256,            // 256^2 tiles: persistent (gemm256p.hip; whole tiles or a stream-K last round), else one per workgroup
+                                 // (gemm256w.hip, four waves; gemm256.hip, eight waves: f32 outputs, gemm_w4 = 0, convolutions)
+  X2I_FORM_256_TAIL = 1256,      // ... whose thin last round was peeled off into a second launch of the 128^2 kernel
+  X2I_FORM_PAIR = 2256,          // two problems in ONE persistent launch (x2i_gemm_pair_bf16 / x2i_gemm_qkv_pair_bf16)
+  X2I_FORM_FX = 3256,            // parallel split with fix-up (gemm256p.hip FX), one problem or a grouped pair: other summation order
+  X2I_FORM_CONV256C = 5256,      // persistent four-wave convolution kernel, 256^2 tiles (gemm256c.hip): product K order
+  X2I_FORM_CONV512C = 5512,      // ... 512 x 128 tiles for at most 128 output channels (gemm512c.hip): product K order
+  X2I_FORM_FP8 = 7256,           // e4m3 operands, one 256^2 tile per workgroup, eight waves (gemm256_fp8.hip)
+  X2I_FORM_FP8_PERSIST = 8256,   // e4m3 operands, persistent four-wave form, whole tiles (gemm256p.hip)
+  X2I_FORM_FP8_STREAMK = 9256,   // ... with a stream-K last round
+};
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device) instead of once per launch
 int x2i_ensure_dynamic_smem(const void* kernel, int bytes);
 int x2i_num_cus();  // compute units of the current device (cached)

@@ -9,6 +9,19 @@ int x2i_launch_gemm_qkv(const x2i_gemm_args* a, const x2i_qkv_desc* qd, hipStrea
 int x2i_launch_gemm_pair(const x2i_gemm_args* a0, const x2i_qkv_desc* q0, const x2i_gemm_args* a1, const x2i_qkv_desc* q1, hipStream_t stream);
 int x2i_launch_gemm_fp8(const x2i_gemm_args* a, const x2i_fp8_desc* f, hipStream_t stream);
 int x2i_launch_gemm_qkv_fp8(const x2i_gemm_args* a, const x2i_fp8_desc* f, const x2i_qkv_desc* qd, hipStream_t stream);
+/* For tests only (bound by tests/test_gemm_plan_cpu.py itself; not part of include/x2i.h): the checks and the plan of a GEMM launch (gemm.hip), with
+   nothing launched and no device needed.  Arguments as for the launch: cd (convolution), qd (fused QKV), f (e4m3 operands), a1 / q1 (second problem
+   of x2i_gemm_pair_bf16 / x2i_gemm_qkv_pair_bf16) are null where they do not apply; cus = compute units to plan for.  Returns the launch's X2I code
+   (message: x2i_last_error) and on X2I_OK writes X2I_PLAN_DESCRIBE_LEN values:
+     out[0] = form (X2IGemmForm), out[1] = launches (1; 2 = a peeled 128^2 tail follows),
+     out[2 + 12 i ...], i = 0, 1 (zeros for a launch that is not there) = grid x, y, z, threads, dynamic LDS bytes, rows M of the launch, tilesM,
+       tilesN, gm, nbatch, sk_on, fx_v0 (a grouped pair: one launch, the GemmP fields of problem 0; a chunked convolution: the first chunk's launch),
+     out[26] = batch items per launch of a persistent convolution kernel (0: not chunked).
+   A pair that is not grouped runs as two launches: the first one's refusal is returned, else the second one's plan is described. */
+#define X2I_PLAN_DESCRIBE_PER_LAUNCH 12
+#define X2I_PLAN_DESCRIBE_LEN (2 + 2 * X2I_PLAN_DESCRIBE_PER_LAUNCH + 1)
+extern "C" int x2i_gemm_plan_describe(const x2i_gemm_args* a, const x2i_conv_desc* cd, const x2i_qkv_desc* qd, const x2i_fp8_desc* f,
+                                      const x2i_gemm_args* a1, const x2i_qkv_desc* q1, int cus, long long* out);
 int x2i_launch_quantize_rows_fp8(const void* x, long long rows, int cols, long long ldx, void* y, long long ldy, float* scale,
                                  float static_inv_scale, hipStream_t stream);
 int x2i_launch_ln_modulate_fp8(const void* X, long long x_bs, int ldx, void* Y, long long y_bs, int ldy, void* Y8, long long y8_bs,
