@@ -1,0 +1,195 @@
+#!/usr/bin/env python3
+"""Time Qwen2 decoding with a key/value cache on the HIP path (x2i_amd.handoff.HipGenerate over Qwen2DecoderStack.prefill / decode_step)
+against transformers' own cached `generate`, both in bf16 on the same GPU, in the same process, on the same random weights:
+  7b   Qwen2.5-7B's decoder (28 layers, hidden 3584, 28 q / 4 kv heads of 128, d_ff 18944) -- Qwen2.5-VL 7B, MiniCPM-o
+  3b   Qwen2.5-3B's decoder (36 layers, hidden 2048, 16 q / 2 kv heads of 128, d_ff 11008) -- Qwen2.5-VL 3B, InternVL2.5-4B
+as a Qwen2ForCausalLM with a small vocabulary (the lm_head stays on PyTorch on both sides and is not what is measured), prompt 512, 128
+greedy tokens, B = 1 and 4.  Three sides, interleaved (HIP eager, HIP graph-replayed, library, HIP eager, ...): each is timed as a whole
+generate of T tokens and of 1 token, wall clock around a synchronised call; ms per token = (t(T) - t(1)) / (T - 1), medians over --reps.
+The library runs generate(do_sample=False, use_cache=True, output_hidden_states=True), what the reference runs under --use_answer.
+
+Then, per x2i_qwen_decode_linear_bf16 shape of a step, the achieved weight bytes per second beside a copy of the same number of bytes in the
+same run.  A step streams every weight once, 15 GB for the 7B, so each launch is measured over a ring of distinct weights of over 1 GB
+(nothing is served from the Infinity Cache), the whole ring captured in one graph and replayed (no launch gaps of the host in it).  The copy
+is torch's vectorised copy kernel over the same ring: it reads AND writes, so its rate counts both directions.
+Output: stdout and, with --log, a file (profiles/qwen_decode_bench.log)."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from x2i_amd import qwen_decode_ops as qd  # noqa: E402
+from x2i_amd.handoff import HipGenerate  # noqa: E402
+
+CONFIGS = {
+    "7b": dict(hidden_size=3584, num_attention_heads=28, num_key_value_heads=4, intermediate_size=18944, num_hidden_layers=28, vocab_size=1024),
+    "3b": dict(hidden_size=2048, num_attention_heads=16, num_key_value_heads=2, intermediate_size=11008, num_hidden_layers=36, vocab_size=1024),
+}
+
+
+def library_model(c, seed=0):
+    """Qwen2ForCausalLM in bf16 on the GPU with Qwen2DecoderStack.init_random_'s kind of weights"""
+    from transformers import Qwen2Config, Qwen2ForCausalLM
+    cfg = Qwen2Config(max_position_embeddings=32768, rms_norm_eps=1e-6, hidden_act="silu", use_cache=True, tie_word_embeddings=False,
+                      bos_token_id=0, eos_token_id=None, pad_token_id=0, rope_parameters=dict(rope_type="default", rope_theta=1000000.0), **c)
+    cfg._attn_implementation = "sdpa"
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(torch.bfloat16)
+    try:
+        with torch.device("cuda"):
+            m = Qwen2ForCausalLM(cfg).eval().requires_grad_(False)
+    finally:
+        torch.set_default_dtype(old)
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    with torch.no_grad():
+        for n, p in m.named_parameters():
+            r = torch.randn(p.shape, device=p.device, generator=gen)
+            if n.endswith("norm.weight"):
+                p.copy_(1.0 + 0.1 * r)
+            elif p.dim() == 1:
+                p.copy_(0.1 * r)
+            elif "embed_tokens" in n:
+                p.copy_(r)
+            else:
+                p.copy_(r * p.shape[1] ** -0.5)
+    m.generation_config.eos_token_id = None
+    m.generation_config.pad_token_id = 0
+    return m
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def bench_generate(say, name, c, batches, S, T, reps):
+    model = library_model(c)
+    hg = HipGenerate(model, check_mask=False)
+    for B in batches:
+        ids = torch.randint(0, c["vocab_size"], (B, S), generator=torch.Generator().manual_seed(B)).cuda()
+        mask = torch.ones_like(ids)
+        sides = {
+            "hip eager": lambda n: hg.generate(model, max_new_tokens=n, graph=False, input_ids=ids, attention_mask=mask),
+            "hip graph": lambda n: hg.generate(model, max_new_tokens=n, graph=True, input_ids=ids, attention_mask=mask),
+            "library": lambda n: model.generate(input_ids=ids, attention_mask=mask, max_new_tokens=n, min_new_tokens=n, do_sample=False, use_cache=True,
+                                                output_hidden_states=True, return_dict_in_generate=True),
+        }
+        for fn in sides.values():       # warm-up: every side once at both lengths
+            fn(T)
+            fn(1)
+        per = {k: [] for k in sides}
+        one = {k: [] for k in sides}
+        for _ in range(reps):
+            for k, fn in sides.items():
+                tT, _ = wall(lambda: fn(T))
+                t1, _ = wall(lambda: fn(1))
+                per[k].append((tT - t1) / (T - 1))
+                one[k].append(t1)
+        for k in sides:
+            say("%-3s B=%d prompt %d, %d tokens, %-9s: %.3f ms per token (min %.3f .. max %.3f, %d reps); prompt pass + first token %.1f ms"
+                % (name, B, S, T, k, statistics.median(per[k]), min(per[k]), max(per[k]), reps, statistics.median(one[k])))
+        lib = statistics.median(per["library"])
+        say("%-3s B=%d                              : library / HIP eager %.2f x, library / HIP graph %.2f x; weights %.2f GB per token -> %.2f TB/s at the graph's rate"
+            % (name, B, lib / statistics.median(per["hip eager"]), lib / statistics.median(per["hip graph"]), decoder_bytes(c) / 1e9,
+               decoder_bytes(c) / (statistics.median(per["hip graph"]) * 1e-3) / 1e12))
+    del hg, model
+    torch.cuda.empty_cache()
+
+
+def decoder_bytes(c):
+    D, F = c["hidden_size"], c["intermediate_size"]
+    dk = D // c["num_attention_heads"]
+    nq, nkv = c["num_attention_heads"] * dk, c["num_key_value_heads"] * dk
+    return 2 * c["num_hidden_layers"] * (D * (nq + 2 * nkv) + nq * D + 3 * D * F)
+
+
+def graph_ms(body, reps):
+    """median ms of one replay of `body` captured in a graph"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        body()
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        body()
+    g.replay()
+    ms = []
+    for _ in range(reps):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        g.replay()
+        t1.record()
+        torch.cuda.synchronize()
+        ms.append(t0.elapsed_time(t1))
+    return statistics.median(ms)
+
+
+def bench_linears(say, name, c, batches, reps):
+    D, F = c["hidden_size"], c["intermediate_size"]
+    dk = D // c["num_attention_heads"]
+    nq, nkv = c["num_attention_heads"] * dk, c["num_key_value_heads"] * dk
+    shapes = [("qkv + bias", nq + 2 * nkv, D, False), ("o_proj + res", D, nq, False), ("gate|up gate", F, D, True), ("down + res", D, F, False)]
+    for label, N, K, gate in shapes:
+        rows = 2 * N if gate else N
+        nbytes = rows * K * 2
+        ring = max(4, -(-(1 << 30) // nbytes))
+        W = (torch.randn((ring, rows, K), device="cuda", dtype=torch.bfloat16) * K ** -0.5)
+        dst = torch.empty((rows, K), device="cuda", dtype=torch.bfloat16)
+        t_copy = graph_ms(lambda: [dst.copy_(W[i]) for i in range(ring)], reps) / ring
+        say("%-3s %-13s N=%-5d K=%-5d %6.1f MB: copy of the same bytes %.1f us = %.2f TB/s (read + write)"
+            % (name, label, N, K, nbytes / 1e6, t_copy * 1e3, 2 * nbytes / (t_copy * 1e-3) / 1e12))
+        for B in batches:
+            x = torch.randn((B, K), device="cuda").bfloat16()
+            res = None if gate or label.startswith("qkv") else torch.randn((B, N), device="cuda").bfloat16()
+            bias = torch.randn((rows,), device="cuda").bfloat16() if label.startswith("qkv") else None
+            out = torch.empty((B, N), device="cuda", dtype=torch.bfloat16)
+            t = graph_ms(lambda: [qd.linear(x, W[i], bias, res, out=out, gate=gate) for i in range(ring)], reps) / ring
+            say("%-3s %-13s N=%-5d K=%-5d B=%d          : decode_linear %.1f us = %.2f TB/s of weight (%.2f of the copy's time)"
+                % (name, label, N, K, B, t * 1e3, nbytes / (t * 1e-3) / 1e12, t / t_copy))
+        del W, dst
+        torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="7b,3b")
+    ap.add_argument("--batches", default="1,4")
+    ap.add_argument("--prompt", type=int, default=512)
+    ap.add_argument("--tokens", type=int, default=128)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--only", choices=("all", "generate", "linears"), default="all")
+    ap.add_argument("--log", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("qwen_decode_bench: no GPU visible; there is nothing to time on the CPU")
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    batches = [int(b) for b in a.batches.split(",")]
+    say("qwen_decode_bench: %s, torch %s, prompt %d, %d tokens, %d reps, sides interleaved" % (torch.cuda.get_device_name(0), torch.__version__, a.prompt,
+                                                                                                a.tokens, a.reps))
+    for name in a.configs.split(","):
+        if a.only in ("all", "generate"):
+            bench_generate(say, name, CONFIGS[name], batches, a.prompt, a.tokens, a.reps)
+        if a.only in ("all", "linears"):
+            with torch.no_grad():
+                bench_linears(say, name, CONFIGS[name], batches, 10)
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+        with open(a.log, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -143,6 +143,164 @@ class HipPrefill:
         return slab
 
 
+class GenerateResult:
+    """What HipGenerate.generate returns: prompt bf16 [B, C, S, H] (the prompt pass, HipPrefill's slab), answer bf16 [B, C, T - 1, H] (the
+    decode passes: column t is the pass whose input is generated token t; the pass of the last token never runs, the HF convention),
+    sequences int64 [B, S + T] (the prompt's ids, then the T generated tokens; the pad token after a sample's end token) and lengths int64
+    [B] (a sample's generated tokens up to and including its end token)."""
+
+    def __init__(self, prompt, answer, sequences, lengths):
+        self.prompt, self.answer, self.sequences, self.lengths = prompt, answer, sequences, lengths
+
+
+class HipGenerate:
+    """Greedy `generate(output_hidden_states=True)` with the decoder stack on the HIP path over the prompt AND over the generated tokens
+    (x2i_amd/qwen.py: Qwen2DecoderStack.prefill / decode_step on a key/value cache): what the reference conditions on under --use_answer
+    (infer/inference_qwenvl.py:125-129,176).  The prompt pass goes through the surrounding model exactly as HipPrefill's does -- `forward`
+    replaced on the instance and restored afterwards, on exceptions too -- so the model still builds inputs_embeds, mask and position ids
+    and applies its own lm_head.  Every later step is: a gather from embed_tokens, decode_step, model.get_output_embeddings(), the
+    optional `transformers` logits processors (torch), argmax.  With graph=True the gather, the step and the lm_head are captured ONCE in a
+    torch.cuda.graph (one stream, no parallel branches) and replayed; the processors and the argmax follow each replay as torch ops.
+    Finished samples are tracked on the device and the host looks once every `check_every` steps.  The cache and the graph captured on it
+    stay resident between calls and serve every later call of the same batch size and rounded capacity (prompt + new tokens)."""
+
+    def __init__(self, model, check_mask=True):
+        from .qwen import Qwen2DecoderStack
+        self.decoder = find_decoder(model)
+        self.stack = Qwen2DecoderStack.from_hf(self.decoder)
+        self.n_layers = len(self.decoder.layers)
+        self.C = self.n_layers + 1
+        self.check_mask = check_mask
+        self.slab = self._cache = None
+        self._state = {}
+
+    def _forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None, use_cache=None, **kw):
+        from transformers.modeling_outputs import BaseModelOutputWithPast
+        if self.slab is not None:
+            raise RuntimeError("handoff.HipGenerate: the surrounding model ran the decoder a second time; only its prompt pass goes through it")
+        if isinstance(attention_mask, dict):
+            raise RuntimeError("handoff.HipGenerate: the decoder was handed prepared mask tensors; it needs the 0/1 [B, S] attention_mask")
+        if past_key_values is not None and past_key_values.get_seq_length() > 0:
+            raise RuntimeError("handoff.HipGenerate: a non-empty key/value cache was passed; the HIP stack keeps its own")
+        if inputs_embeds is not None:
+            inputs_embeds = inputs_embeds.to(torch.bfloat16)
+        B, S = (input_ids if input_ids is not None else inputs_embeds).shape[:2]
+        # one cache stays resident, with the step captured on it: the next call at the same (B, cap) reuses both (a prefill resets the ranges
+        # and positions; what older generations left in K / V^T outside the new ranges is finite, which is all the kernels ask)
+        key = (B, (S + self._new_tokens + 63) // 64 * 64)
+        if self._state.get("key") != key:
+            self._state = dict(key=key, cache=self.stack.new_cache(B, key[1]))
+        self._cache = self._state["cache"]
+        self.slab = self.stack.prefill(self._cache, inputs_embeds=inputs_embeds, input_ids=input_ids, attention_mask=attention_mask,
+                                       position_ids=position_ids, check_mask=self.check_mask)
+        return BaseModelOutputWithPast(last_hidden_state=self.slab[:, -1], past_key_values=None)
+
+    @staticmethod
+    def refuse_sampling(generation_config):
+        if generation_config is not None and getattr(generation_config, "do_sample", False) and getattr(generation_config, "top_k", None) != 1:
+            raise ValueError("handoff.HipGenerate: greedy decoding only, and this generation_config samples (do_sample=True, top_k=%r); "
+                             "run with --full_generate (and without --hip_generate) instead" % (getattr(generation_config, "top_k", None),))
+
+    @torch.no_grad()
+    def generate(self, model, max_new_tokens=128, eos_token_id=None, pad_token_id=None, logits_processor=None, graph=True, check_every=16,
+                 generation_config=None, **inputs):
+        """-> GenerateResult.  inputs: the model's forward arguments of the prompt (input_ids required; attention_mask, pixel_values, ...).
+        eos_token_id: an id, a list of ids or None (never stop early); pad_token_id: what follows a sample's end token (default: the first
+        end token, else 0).  logits_processor: a list of callables (input_ids [B, len], scores f32 [B, V]) -> scores."""
+        self.refuse_sampling(generation_config if generation_config is not None else getattr(model, "generation_config", None))
+        if max_new_tokens < 1:
+            raise ValueError("handoff.HipGenerate: max_new_tokens must be at least 1")
+        ids = inputs.get("input_ids")
+        if ids is None:
+            raise ValueError("handoff.HipGenerate: input_ids are required (the generated tokens are appended to them)")
+        eos = [] if eos_token_id is None else ([int(eos_token_id)] if not isinstance(eos_token_id, (list, tuple)) else [int(e) for e in eos_token_id])
+        pad = int(pad_token_id) if pad_token_id is not None else (eos[0] if eos else 0)
+        processors = list(logits_processor or [])
+        head = model.get_output_embeddings()
+        self.slab = self._cache = None
+        self._new_tokens = max_new_tokens
+        had = "forward" in self.decoder.__dict__
+        saved = self.decoder.__dict__.get("forward")
+        self.decoder.forward = self._forward
+        try:
+            out = model(**inputs, use_cache=False)
+        finally:
+            if had:
+                self.decoder.forward = saved
+            else:
+                del self.decoder.forward
+        if self.slab is None:
+            raise RuntimeError("handoff: the decoder stack did not run")
+        prompt, cache, self.slab, self._cache = self.slab, self._cache, None, None
+        dev = prompt.device
+        B, C, S, H = prompt.shape
+        T = max_new_tokens
+        rows = torch.arange(B, device=dev)
+        last = (cache.k_hi - 1).long()                                   # the last valid token of each sample, under either padding
+        sequences = torch.full((B, S + T), pad, device=dev, dtype=torch.long)
+        sequences[:, :S] = ids
+        answer = torch.empty((B, C, max(T - 1, 0), H), device=dev, dtype=torch.bfloat16)
+        done = torch.zeros((B,), device=dev, dtype=torch.bool)
+        lengths = torch.zeros((B,), device=dev, dtype=torch.long)
+        eos_t = torch.tensor(eos, device=dev, dtype=torch.long) if eos else None
+        st = self._state
+        if "token" not in st:       # the captured step's input and output live with the cache
+            st["token"] = torch.empty((B,), device=dev, dtype=torch.long)
+            st["step_out"] = torch.empty((B, C, H), device=dev, dtype=torch.bfloat16)
+        token, step_out = st["token"], st["step_out"]
+
+        def pick(t, scores):
+            """token t from the f32 scores [B, V] of the pass before it: processors, argmax, the end-token bookkeeping, all on the device"""
+            for p in processors:
+                scores = p(sequences[:, :S + t], scores)
+            nxt = torch.where(done, torch.full_like(token, pad), scores.argmax(-1))
+            token.copy_(nxt)
+            sequences[:, S + t] = nxt
+            lengths.add_((~done).long())
+            if eos_t is not None:
+                done.logical_or_((nxt[:, None] == eos_t[None]).any(-1))
+
+        pick(0, out.logits[rows, last].float())
+        if st.get("head") is not head:      # (a graph holds the lm_head it was captured with)
+            st.pop("graph", None)
+            st["head"] = head
+        t = 1
+        while t < T:
+            if check_every and t % check_every == 0 and eos_t is not None and bool(done.all()):      # the one host read per check_every steps
+                break
+            if not graph:
+                cache_out = answer[:, :, t - 1]
+                self.stack.decode_step(cache, input_ids=token, out=cache_out)
+                logits = head(cache_out[:, -1])
+            else:
+                if "graph" not in st and not st.get("warm"):
+                    # the very first step runs eagerly on a side stream (the warm-up a capture needs); the next one is the capture
+                    side = torch.cuda.Stream()
+                    side.wait_stream(torch.cuda.current_stream())
+                    with torch.cuda.stream(side):
+                        self.stack.decode_step(cache, input_ids=token, out=step_out)
+                        logits = head(step_out[:, -1])
+                    torch.cuda.current_stream().wait_stream(side)
+                    st["warm"] = True
+                else:
+                    if "graph" not in st:
+                        g = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(g):
+                            self.stack.decode_step(cache, input_ids=token, out=step_out)
+                            st["logits"] = head(step_out[:, -1])
+                        cache.steps -= 1                 # (a capture runs nothing: the replay below is this step)
+                        st["graph"] = g
+                    st["graph"].replay()
+                    cache.steps += 1
+                    logits = st["logits"]
+                answer[:, :, t - 1].copy_(step_out)
+            pick(t, logits.float())
+            t += 1
+        n = int(lengths.max()) if eos_t is not None else T                # (tokens after every sample's end are dropped: one host read)
+        n = max(n, 1)
+        return GenerateResult(prompt, answer[:, :, :n - 1], sequences[:, :S + n], lengths)
+
+
 def find_visual(model):
     """The vision tower of a Qwen2.5-VL model: `model.visual` (Qwen2_5_VLModel) or `model.model.visual` (Qwen2_5_VLForConditionalGeneration)"""
     for m in (model, getattr(model, "model", None)):

@@ -74,6 +74,9 @@ def build_parser(family):
     p.add_argument("--hip_vision", action="store_true",
                    help="run the MLLM's vision tower (Qwen2.5-VL's model.visual) on the HIP path (x2i_amd/qwen_vision.py) instead of the "
                         "library's forward; independent of --hip_decoder")
+    p.add_argument("--hip_generate", action="store_true",
+                   help="run the MLLM's greedy 128-token generate() with the decoder stack on the HIP path over the prompt and over the "
+                        "generated tokens (key/value cache, x2i_amd/qwen.py decode_step); serves --use_answer; Qwen2.5-VL only")
     p.add_argument("--decode", action="store_true", help="with --synthetic: also run the (random-weight) VAE decoder and save images")
     return p
 

@@ -14,7 +14,7 @@ class QwenVLConditioner:
     """Qwen2_5_VLForConditionalGeneration prompt pass; inputs padded to 512 tokens, images resized to 128x128, videos at
     1 fps / 128*128 pixels, generate(max_new_tokens=128, output_hidden_states=True) -- infer/inference_qwenvl.py:136-180."""
 
-    def __init__(self, path, device, use_answer=False, prefill_only=True, hip_decoder=False, hip_vision=False):
+    def __init__(self, path, device, use_answer=False, prefill_only=True, hip_decoder=False, hip_vision=False, hip_generate=False):
         from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
         self.model = Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
         self.processor = AutoProcessor.from_pretrained(path)
@@ -24,7 +24,16 @@ class QwenVLConditioner:
         self.slab = None
         if hip_decoder and not (prefill_only and not use_answer):
             raise ValueError("--hip_decoder serves the prompt pass only: not with --full_generate or --use_answer")
-        if prefill_only and not use_answer:
+        # hip_generate: the whole greedy generate() with the decoder stack on the HIP path (handoff.HipGenerate): the generated tokens' states
+        # under --use_answer, the prompt's otherwise
+        self.generate = None
+        if hip_generate:
+            if hip_decoder:
+                raise ValueError("--hip_generate runs the prompt pass on the HIP path itself: not together with --hip_decoder")
+            from ..handoff import HipGenerate
+            HipGenerate.refuse_sampling(self.model.generation_config)
+            self.generate = HipGenerate(self.model)
+        elif prefill_only and not use_answer:
             from ..handoff import HiddenStateSlab, HipPrefill, find_decoder
             # hip_decoder: the same one forward with the decoder stack itself on the HIP path (x2i_amd/qwen.py)
             self.slab = HipPrefill(self.model) if hip_decoder else HiddenStateSlab(find_decoder(self.model))
@@ -55,6 +64,12 @@ class QwenVLConditioner:
         prompt = self.processor.apply_chat_template(message, tokenize=False, add_generation_prompt=True)
         inputs = self.processor(text=[prompt], images=image_list or None, videos=video_inputs, padding="max_length",
                                 max_length=512, truncation=True, return_tensors="pt").to(self.device)
+        if self.generate is not None:
+            gc = self.model.generation_config
+            out = self.generate.generate(self.model, max_new_tokens=128, eos_token_id=gc.eos_token_id, pad_token_id=gc.pad_token_id,
+                                         logits_processor=self.model._get_logits_processor(gc, input_ids_seq_length=inputs["input_ids"].shape[1],
+                                                                                               device=self.device), **inputs)
+            return out.answer if self.use_answer else out.prompt
         if self.slab is not None:
             return self.slab.prefill(self.model, **inputs)
         out = self.model.generate(**inputs, max_new_tokens=128, output_hidden_states=True, return_dict_in_generate=True)
@@ -90,7 +105,8 @@ def main(argv=None):
     device = "cuda:%d" % int(__import__("os").environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(device)
     cond = SyntheticConditioner(kind, device) if args.synthetic else QwenVLConditioner(args.qwen_path, device, args.use_answer, prefill_only=not args.full_generate,
-                                                                                            hip_decoder=args.hip_decoder, hip_vision=args.hip_vision)
+                                                                                            hip_decoder=args.hip_decoder, hip_vision=args.hip_vision,
+                                                                                            hip_generate=args.hip_generate)
     Harness(args, kind, cond, device).run_tasks(tasks(args))
 
 

@@ -22,6 +22,15 @@ Parameter names are the library's, so a decoder's state dict loads strictly; the
 into stacked storage (as T5Stack's are).  The audio towers and the embedding merge stay on PyTorch, and so do the vision towers but for
 Qwen2.5-VL's, which has a HIP path of its own (x2i_amd/qwen_vision.py): the stack takes `inputs_embeds` (or `input_ids`, a torch gather
 from embed_tokens).
+
+Decoding with a key/value cache (include/x2i_qwen_decode.h; the generated answer the reference conditions on under --use_answer) is three
+more methods: new_cache(B, capacity), prefill(cache, ...) -- forward's slab bit for bit, written through the cache's per-layer K / V^T with
+Spad = cap -- and decode_step(cache, ...), one token per sample, eight launches per layer:
+  rms_rows, decode_linear (q|k|v + bias), decode_rope_append (slot k_hi), decode_attention (keys [k_lo, k_hi + 1)), decode_linear (o_proj +
+  residual), rms_rows, decode_linear (gate|up with the SwiGLU gate), decode_linear (down_proj + residual -> the next entry of the output)
+The cache layout: a step appends at PHYSICAL slot k_hi[b] -- for a right-padded prompt the first padding slot -- so the valid keys stay one
+contiguous run under either padding; the token's POSITION comes from the RoPE table of the cache's next position, never from the slot.
+forward itself stays prefill only.
 """
 import torch
 import torch.nn as nn
@@ -125,7 +134,8 @@ def _config_fields(config, kw):
 
 class Qwen2DecoderStack(nn.Module):
     """Prefill-only drop-in for transformers' Qwen2Model / Qwen2_5_VLTextModel (the module handoff.find_decoder finds).
-    forward(...) -> the hidden-state slab bf16 [B, num_layers + 1, S, H]."""
+    forward(...) -> the hidden-state slab bf16 [B, num_layers + 1, S, H].  Decoding with a key/value cache is new_cache / prefill /
+    decode_step, below; forward itself keeps none."""
 
     def __init__(self, config=None, embed_tokens=None, device="cuda", dtype=torch.bfloat16, **kw):
         super().__init__()
@@ -268,14 +278,22 @@ class Qwen2DecoderStack(nn.Module):
         positions the library builds its mask from -- is dropped).  After the first call at a (B, S) a forward allocates the slab and the two
         RoPE tables and nothing else (with a mask: the two range vectors and their torch temporaries too).  Rows before a left-padded
         sample's first valid token hold finite values that the library does not define."""
-        if (input_ids is None) == (inputs_embeds is None):
-            raise ValueError("Qwen2DecoderStack: pass exactly one of input_ids and inputs_embeds")
         if use_cache or past_key_values is not None:
             raise ValueError("x2i_amd Qwen2DecoderStack: prefill only; use_cache=True and past_key_values are not built")
+        return self._prompt_pass(None, inputs_embeds, input_ids, attention_mask, position_ids, check_mask)
+
+    def _prompt_pass(self, cache, inputs_embeds, input_ids, attention_mask, position_ids, check_mask):
+        """forward's launches; with a cache (prefill) rope_split and the attention run with Spad = cap on the cache's own per-layer K / V^T, and
+        the cache's ranges and next positions are set: the same kernels on the same values, so the slab is bit-identical."""
+        if (input_ids is None) == (inputs_embeds is None):
+            raise ValueError("Qwen2DecoderStack: pass exactly one of input_ids and inputs_embeds")
         c = self.config
         D, dk, Hq, Hkv, F, eps, L = c.hidden_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads, c.intermediate_size, c.rms_norm_eps, len(self.layers)
         nq, C = Hq * dk, len(self.layers) + 1
         B, S = (input_ids if input_ids is not None else inputs_embeds).shape[:2]
+        if cache is not None and (cache.B != B or S + 1 > cache.cap):
+            raise ValueError("x2i_amd Qwen2DecoderStack.prefill: a prompt of [B, S] = [%d, %d] does not fit a cache of B = %d, cap = %d (S + 1 <= cap)"
+                             % (B, S, cache.B, cache.cap))
         k_lo = k_hi = None
         if attention_mask is not None:
             if tuple(attention_mask.shape) != (B, S):
@@ -290,6 +308,8 @@ class Qwen2DecoderStack(nn.Module):
         ws = self._workspace(B, S)
         X1, X2, NRM, QKV, Q, K, VT, ATT, HH, G, Spad = (ws[k] for k in ("X1", "X2", "NRM", "QKV", "Q", "K", "VT", "ATT", "HH", "G", "Spad"))
         dev = X1.device
+        if cache is not None:
+            Q, Spad = cache.Q, cache.cap
         if position_ids is None:
             position_ids = ws["arange"]
         elif position_ids.dim() == 3 and position_ids.shape[0] == 4:
@@ -299,6 +319,8 @@ class Qwen2DecoderStack(nn.Module):
         if tuple(position_ids.shape[-2:]) != (B, S):
             position_ids = position_ids.expand(*position_ids.shape[:-2], B, S)
         cos, sin = rope_tables(position_ids.to(dev), dk, c.rope_theta, c.mrope_section, _scratch=ws["rope"])
+        if cache is not None:
+            cache._set_prompt(S, k_lo, k_hi, attention_mask, position_ids.to(dev))
         slab = torch.empty((B, C, S, D), device=dev, dtype=torch.bfloat16)
         if input_ids is not None:
             if input_ids.device != dev:
@@ -311,6 +333,8 @@ class Qwen2DecoderStack(nn.Module):
         M, sbs, SD = B * S, C * S * D, S * D
         scale = dk ** -0.5
         for i, layer in enumerate(self.layers):
+            if cache is not None:
+                K, VT = cache.K[i], cache.VT[i]
             for b in range(B):   # (the samples of slab[:, i] are C*S*D apart; the norm's rows have one stride)
                 t5_ops.rms_rows(slab[b, i], layer.input_layernorm.weight, eps, out=NRM[b * S:(b + 1) * S])
             ops.gemm(NRM, self._fused["%d.qkv.w" % i], self._fused["%d.qkv.b" % i], out=QKV, M=M)
@@ -329,3 +353,158 @@ class Qwen2DecoderStack(nn.Module):
         for b in range(B):
             t5_ops.rms_rows(X2[b * S:(b + 1) * S], self.norm.weight, eps, out=slab[b, L])
         return slab
+
+    # ------------------------------------------------------------------ decoding with a key/value cache
+    def new_cache(self, B, capacity):
+        """A Qwen2DecodeCache for B samples and at least `capacity` keys per sample (prompt + generated tokens), rounded up to 64."""
+        return Qwen2DecodeCache(self, B, capacity)
+
+    @torch.no_grad()
+    def prefill(self, cache, inputs_embeds=None, input_ids=None, attention_mask=None, position_ids=None, check_mask=True, **unused):
+        """forward's arguments and forward's slab [B, C, S, H], bit for bit: the same launches, but rope_split and the attention run with
+        Spad = cap on the cache's own per-layer K / V^T.  Sets the cache's key ranges (from the mask) and every sample's next position: one
+        more than the largest position id of its valid tokens over all axes -- for plain Qwen2 the count of valid tokens, for Qwen2.5-VL what
+        the library's rope_deltas yields.  Refuses S + 1 > cap."""
+        if not isinstance(cache, Qwen2DecodeCache) or cache.owner() is not self:
+            raise ValueError("x2i_amd Qwen2DecoderStack.prefill: the cache must come from this stack's new_cache()")
+        return self._prompt_pass(cache, inputs_embeds, input_ids, attention_mask, position_ids, check_mask)
+
+    @torch.no_grad()
+    def decode_step(self, cache, inputs_embeds=None, input_ids=None, out=None):
+        """One token per sample against the cache: inputs_embeds bf16 [B, 1, H] (or [B, H]) or input_ids [B, 1] (or [B]) -> the hidden states
+        bf16 [B, C, 1, H] of that token (HF convention, as forward).  out: a [B, C, H] view to write instead, e.g. column t of a caller's
+        [B, C, T, H] answer slab, slab[:, :, t] (last stride 1, H-rows 16-byte aligned); it IS the residual stream, no copy.
+        The new key and value go to physical slot k_hi[b] (under right padding that overwrites the first padding slot), so the valid keys stay
+        the one run [k_lo, k_hi) under either padding; the position comes from the RoPE table of the cache's next position, not from the slot.
+        k_hi and the position then advance ON THE DEVICE: no host read, and after the first step no allocation but the output, so a step can
+        be captured in a graph and replayed (a replay does not pass through here: its caller counts the steps, cache.steps).  Launches per
+        layer: rms, qkv linear, rope_append, attention, o_proj linear + residual, rms, gate|up linear with the gate, down linear + residual."""
+        from . import qwen_decode_ops as qd
+        if (input_ids is None) == (inputs_embeds is None):
+            raise ValueError("Qwen2DecoderStack: pass exactly one of input_ids and inputs_embeds")
+        if not isinstance(cache, Qwen2DecodeCache) or cache.owner() is not self:
+            raise ValueError("x2i_amd Qwen2DecoderStack.decode_step: the cache must come from this stack's new_cache()")
+        if cache.steps is None:
+            raise ValueError("x2i_amd Qwen2DecoderStack.decode_step: prefill(cache, ...) comes first")
+        if cache.steps + 1 > cache.cap:
+            raise ValueError("x2i_amd Qwen2DecoderStack.decode_step: the cache is full (cap = %d keys)" % cache.cap)
+        c = self.config
+        D, dk, Hq, Hkv, F, eps, L = c.hidden_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads, c.intermediate_size, c.rms_norm_eps, len(self.layers)
+        B, cap, C = cache.B, cache.cap, L + 1
+        if out is None:
+            out4 = torch.empty((B, C, 1, D), device=cache.K.device, dtype=torch.bfloat16)
+            out = out4[:, :, 0]
+        else:
+            ops._req(out, torch.bfloat16, "out")
+            if tuple(out.shape) != (B, C, D) or out.stride(2) != 1 or out.stride(1) % 8 or out.stride(0) % 8 or out.data_ptr() % 16:
+                raise ValueError("x2i_amd Qwen2DecoderStack.decode_step: out must be a bf16 [B, C, H] = [%d, %d, %d] view with 16-byte aligned rows"
+                                 % (B, C, D))
+            out4 = out.unsqueeze(2)
+        if input_ids is not None:
+            if input_ids.device != out.device:
+                raise ops._lib.X2IError("x2i_amd: input_ids must live on the model's device (got %s)" % input_ids.device)
+            torch.index_select(self.embed_tokens.weight, 0, input_ids.reshape(B), out=cache.X0)
+        else:
+            ops._req(inputs_embeds, torch.bfloat16, "inputs_embeds")
+            cache.X0.copy_(inputs_embeds.reshape(B, D))
+        out[:, 0].copy_(cache.X0)
+        cos, sin = cache._step_tables()             # from the next position, which then advances; slot = k_hi, k_hi += 1
+        X1, X2, NRM, QKV, Qd, ATT, G, ws, slot, k_lo, k_hi = (cache.X1, cache.X2, cache.NRM, cache.QKV, cache.Qd, cache.ATT, cache.G, cache.ws,
+                                                              cache.slot, cache.k_lo, cache.k_hi)
+        sb, sc, scale = out.stride(0), out.stride(1), dk ** -0.5
+        for i, layer in enumerate(self.layers):
+            t5_ops.rms_rows(out[:, i], layer.input_layernorm.weight, eps, out=NRM, rows=B, ldx=sb)
+            qd.linear(NRM, self._fused["%d.qkv.w" % i], self._fused["%d.qkv.b" % i], out=QKV)
+            qd.rope_append(QKV, cos, sin, slot, Qd, cache.K[i], cache.VT[i], B, Hq, Hkv, cap, dk)
+            qd.attention(Qd, cache.K[i], cache.VT[i], k_lo, k_hi, ATT, ws, B, Hq, Hkv, cap, dk, scale)
+            qd.linear(ATT, layer.self_attn.o_proj.weight, res=out, res_offset=i * sc, ldr=sb, out=X1)
+            t5_ops.rms_rows(X1, layer.post_attention_layernorm.weight, eps, out=NRM)
+            qd.linear(NRM, self._fused["%d.gu" % i], gate=True, out=G)
+            if i + 1 < L:
+                qd.linear(G, layer.mlp.down_proj.weight, res=X1, out=out, y_offset=(i + 1) * sc, ldy=sb, B=B, N=D)
+            else:
+                qd.linear(G, layer.mlp.down_proj.weight, res=X1, out=X2)
+        t5_ops.rms_rows(X2, self.norm.weight, eps, out=out[:, L], rows=B, ldy=sb)
+        cache.steps += 1
+        return out4
+
+
+class Qwen2DecodeCache:
+    """The keys and values of one generation, and everything a decode step needs so that it allocates nothing (Qwen2DecoderStack.new_cache):
+      K  bf16 [L, B, Hkv, cap, dk], VT bf16 [L, B, Hkv, dk, cap]   zeroed once: the kernels need them finite, not empty
+      k_lo, k_hi int32 [B]    the valid keys of each sample, one contiguous run; a step appends at slot k_hi and advances it
+      pos int64 [B], or [3, B] with an mrope_section    the next position of each sample (the RoPE table's argument, not a slot)
+      steps    host-side count of an upper bound of k_hi (None before a prefill); a caller that replays a captured step adds to it itself
+    and the step's scratch rows, the prefill's Q [B, Hq, cap, dk] and the attention's split workspace."""
+
+    def __init__(self, stack, B, capacity):
+        import weakref
+        from . import qwen_decode_ops as qd
+        c = stack.config
+        D, dk, Hq, Hkv, F, L = c.hidden_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads, c.intermediate_size, len(stack.layers)
+        if B < 1 or capacity < 1:
+            raise ValueError("x2i_amd Qwen2DecodeCache: B and capacity must be positive (got %r, %r)" % (B, capacity))
+        if B > 8:
+            raise ValueError("x2i_amd Qwen2DecodeCache: the decode kernels take 1..8 samples (got B = %d)" % B)
+        if Hq // Hkv > 16:
+            raise ValueError("x2i_amd Qwen2DecodeCache: a group of %d query heads per key/value head is above 16" % (Hq // Hkv))
+        self.owner = weakref.ref(stack)
+        self.B, self.cap = B, qwen_ops.pad64(capacity)
+        cap, dev = self.cap, stack.device
+        bf = dict(device=dev, dtype=torch.bfloat16)
+        self.K = torch.zeros((L, B, Hkv, cap, dk), **bf)
+        self.VT = torch.zeros((L, B, Hkv, dk, cap), **bf)
+        self.Q = torch.zeros((B, Hq, cap, dk), **bf)
+        self.k_lo = torch.zeros((B,), device=dev, dtype=torch.int32)
+        self.k_hi = torch.zeros((B,), device=dev, dtype=torch.int32)
+        self.slot = torch.zeros((B,), device=dev, dtype=torch.int32)
+        self.mrope = c.mrope_section is not None
+        self.pos = torch.zeros((3, B) if self.mrope else (B,), device=dev, dtype=torch.int64)
+        self.steps = None
+        nq, nkv = Hq * dk, Hkv * dk
+        self.X0, self.X1, self.X2, self.NRM = (torch.empty((B, D), **bf) for _ in range(4))
+        self.QKV = torch.empty((B, nq + 2 * nkv), **bf)
+        self.Qd = torch.empty((B, Hq, dk), **bf)
+        self.ATT = torch.empty((B, nq), **bf)
+        self.G = torch.empty((B, F), **bf)
+        self.ws = torch.empty((qd.workspace_floats(B, Hq, cap, dk),), device=dev, dtype=torch.float32)
+        f32 = dict(device=dev, dtype=torch.float32)
+        self._inv_freq = (1.0 / (c.rope_theta ** (torch.arange(0, dk, 2, dtype=torch.float) / dk))).to(dev)    # rope_tables' own
+        self._section = c.mrope_section
+        self._posf = torch.empty(self.pos.shape, **f32)
+        self._ang, self._cos, self._sin = (torch.empty((B, dk // 2), **f32) for _ in range(3))
+
+    def _set_prompt(self, S, k_lo, k_hi, attention_mask, position_ids):
+        """After a prompt of S tokens: ranges from the mask ([0, S) without one), next position = 1 + the largest position id of the valid tokens"""
+        if k_lo is None:
+            if attention_mask is None:
+                self.k_lo.zero_()
+                self.k_hi.fill_(S)
+            else:
+                k_lo, k_hi = key_ranges(attention_mask)
+        if k_lo is not None:
+            self.k_lo.copy_(k_lo)
+            self.k_hi.copy_(k_hi)
+        pos = position_ids if position_ids.dim() == 3 else position_ids[None]
+        if attention_mask is not None:
+            pos = pos.masked_fill((attention_mask == 0).to(pos.device)[None], -1)
+        self.pos.copy_((pos.amax(-1).amax(0) + 1).expand_as(self.pos) if self.mrope else pos.amax(-1)[0] + 1)
+        self.steps = S
+
+    def _step_tables(self):
+        """(cos, sin) f32 [B, dk/2] of the next positions, rope_tables' arithmetic into buffers of the cache; then slot = k_hi, k_hi += 1,
+        pos += 1, all on the device."""
+        self._posf.copy_(self.pos)
+        if not self.mrope:
+            torch.mul(self._posf[:, None], self._inv_freq, out=self._ang)
+        else:
+            c0 = 0
+            for i, n in enumerate(self._section):
+                torch.mul(self._posf[i % 3][:, None], self._inv_freq[c0:c0 + n], out=self._ang[:, c0:c0 + n])
+                c0 += n
+        torch.cos(self._ang, out=self._cos)
+        torch.sin(self._ang, out=self._sin)
+        self.slot.copy_(self.k_hi)
+        self.k_hi.add_(1)
+        self.pos.add_(1)
+        return self._cos, self._sin
