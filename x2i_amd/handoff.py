@@ -350,6 +350,54 @@ class HipVision:
         self.remove()
 
 
+def find_vpm(model):
+    """The SigLIP vision tower of a MiniCPM-o model: `model.vpm`"""
+    v = getattr(model, "vpm", None)
+    if isinstance(v, nn.Module):
+        return v
+    raise RuntimeError("handoff: no vision tower (model.vpm) found in %s" % type(model).__name__)
+
+
+class HipSiglip:
+    """The vision tower behind `model.vpm` on the HIP path (x2i_amd/siglip.py: SiglipVisionTower, a bf16 copy of the tower's weights on its
+    device).  HipVision's interface: install() replaces the tower module's `forward` ON THE INSTANCE and remove() restores it; between the
+    two the surrounding model's get_vllm_embedding, its Resampler and its embedding scatter run as they always do and get the library's
+    output object from the HIP tower.  Also a context manager.  Independent of the kind of slab, and the same under generate()."""
+
+    def __init__(self, model):
+        from .siglip import SiglipVisionTower
+        self.vpm = find_vpm(model)
+        self.tower = SiglipVisionTower.from_hf(self.vpm)
+        self.calls = 0
+        self._installed = False
+
+    def _forward(self, pixel_values, patch_attention_mask=None, tgt_sizes=None, **kw):
+        self.calls += 1
+        return self.tower(pixel_values, patch_attention_mask=patch_attention_mask, tgt_sizes=tgt_sizes)
+
+    def install(self):
+        if not self._installed:
+            self._had = "forward" in self.vpm.__dict__
+            self._saved = self.vpm.__dict__.get("forward")
+            self.vpm.forward = self._forward
+            self._installed = True
+        return self
+
+    def remove(self):
+        if self._installed:
+            if self._had:
+                self.vpm.forward = self._saved
+            else:
+                del self.vpm.forward
+            self._installed = False
+
+    def __enter__(self):
+        return self.install()
+
+    def __exit__(self, *exc):
+        self.remove()
+
+
 def prefill_hidden_states(model, dtype=torch.bfloat16, **inputs):
     """Convenience wrapper: [B, C, S, H] conditioning tensor of `inputs` from one forward of `model`."""
     return HiddenStateSlab(find_decoder(model), dtype).prefill(model, **inputs)

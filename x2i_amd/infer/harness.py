@@ -72,8 +72,9 @@ def build_parser(family):
                    help="run the MLLM's decoder stack over the prompt on the HIP path (x2i_amd/qwen.py) instead of the library's forward; "
                         "prefill only, so not with --full_generate or --use_answer")
     p.add_argument("--hip_vision", action="store_true",
-                   help="run the MLLM's vision tower (Qwen2.5-VL's model.visual) on the HIP path (x2i_amd/qwen_vision.py) instead of the "
-                        "library's forward; independent of --hip_decoder")
+                   help="run the MLLM's vision tower on the HIP path instead of the library's forward: Qwen2.5-VL's model.visual "
+                        "(x2i_amd/qwen_vision.py) or MiniCPM-o's SigLIP model.vpm (x2i_amd/siglip.py); independent of --hip_decoder and of "
+                        "--full_generate")
     p.add_argument("--hip_generate", action="store_true",
                    help="run the MLLM's greedy 128-token generate() with the decoder stack on the HIP path over the prompt and over the "
                         "generated tokens (key/value cache, x2i_amd/qwen.py decode_step); serves --use_answer; Qwen2.5-VL only")
