@@ -156,7 +156,9 @@ int x2i_streamk_workspace_status(const void* workspace, int64_t workspace_bytes)
  * sat(epi * out_inv_scale) that is the next GEMM's A operand.  `args` is read as for x2i_gemm_bf16 with A / W pointing at e4m3
  * bytes and lda / ldw / K counted in elements (= bytes); ldc counts output elements.  Served shapes: K % 128 == 0, lda / ldw %
  * 16 == 0, N % 8 == 0 (N % 16 for out_fp8); anything else returns X2I_ERR_ALIGN / X2I_ERR_SHAPE -- callers keep such linears on
- * the bf16 entry point.  bf16 remains the default arithmetic of the path; fp8 is opt-in per model (x2i_amd: fp8= argument). */
+ * the bf16 entry point.  bf16 remains the default arithmetic of the path; fp8 is opt-in per model (x2i_amd: fp8= argument).
+ * The sum over k carries the accumulation error of v_mfma_scale_f32_16x16x128_f8f6f4, which is far above an f32 fma chain's: up to
+ * 9.3e-5 of sum_k |A8 W8| measured on MI355X, the same in every kernel form; the tests bound it by 2^-12 (tests/fp8_ref.py: U_ACC8). */
 typedef struct x2i_fp8_desc {
   const float* a_scale;          /* f32 [batch][M] per-row dequantisation scale of A (NULL: 1) */
   int64_t a_scale_batch_stride;

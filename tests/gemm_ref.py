@@ -114,17 +114,9 @@ def linear_f64(A, W, bias):
     return lin, mag
 
 
-def gemm_expect(A, W, bias=None, *, act=ACT_NONE, gate=None, res=None, act2=None, out_f32=False, bias2=None):
-    """Expected outputs of x2i_gemm_bf16 for the rows A [m, K] of one batch item: W [N, K], bias [N] (bf16 or None), gate [N] f32 or None,
-    res [m, N] bf16 or None, bias2 [N] f32 or None (x2i_gemm_args.bias2 of this item: added in front of the activation; its magnitude joins
-    the U_ACC term like the bias's).  Returns (want, bound, delta) float64 [m, N] for C (delta: the f32 part of the bound), and (want2, bound2, delta2) for
-    C2 = act2(v) when act2 is not None."""
-    lin, mag = linear_f64(A, W, bias)
-    if bias2 is not None:
-        lin += bias2.double()
-        mag += bias2.double().abs()
-    d = U_ACC * mag
-    del mag
+def epilogue_expect(lin, d, *, act=ACT_NONE, gate=None, res=None, act2=None, out_f32=False):
+    """The epilogue of x2i_gemm_bf16 from the linear part on: lin float64 [m, N] (biases included) and d, the bound on the kernel's f32 value
+    of it.  Returns what gemm_expect returns.  (The e4m3 GEMM's expectation, tests/fp8_ref.py, starts here with its own lin and d.)"""
     v = act_f64(lin, act)
     d = _act_bound(lin, v, d, act)
     if res is not None:                       # (the gate applies with a residual only)
@@ -139,6 +131,20 @@ def gemm_expect(A, W, bias=None, *, act=ACT_NONE, gate=None, res=None, act2=None
     v2 = act_f64(v, act2)
     d2 = _act_bound(v, v2, d, act2)
     return out, (v2, _round_bound(v2, d2, False), d2)
+
+
+def gemm_expect(A, W, bias=None, *, act=ACT_NONE, gate=None, res=None, act2=None, out_f32=False, bias2=None):
+    """Expected outputs of x2i_gemm_bf16 for the rows A [m, K] of one batch item: W [N, K], bias [N] (bf16 or None), gate [N] f32 or None,
+    res [m, N] bf16 or None, bias2 [N] f32 or None (x2i_gemm_args.bias2 of this item: added in front of the activation; its magnitude joins
+    the U_ACC term like the bias's).  Returns (want, bound, delta) float64 [m, N] for C (delta: the f32 part of the bound), and (want2, bound2, delta2) for
+    C2 = act2(v) when act2 is not None."""
+    lin, mag = linear_f64(A, W, bias)
+    if bias2 is not None:
+        lin += bias2.double()
+        mag += bias2.double().abs()
+    d = U_ACC * mag
+    del mag
+    return epilogue_expect(lin, d, act=act, gate=gate, res=res, act2=act2, out_f32=out_f32)
 
 
 def rope_rows(cos, sin, tok):
@@ -181,6 +187,11 @@ def qkv_expect(A, W, bias, norm_q, norm_k, c, s, *, H, q_scale=1.0, eps=1e-6):
     lin, mag = linear_f64(A, W, bias)
     d = U_ACC * mag
     del mag
+    return qkv_epilogue_expect(lin, d, norm_q, norm_k, c, s, H=H, q_scale=q_scale, eps=eps)
+
+
+def qkv_epilogue_expect(lin, d, norm_q, norm_k, c, s, *, H, q_scale=1.0, eps=1e-6):
+    """The fused QKV epilogue from the linear part on (lin, d as for epilogue_expect): what qkv_expect returns."""
     m, HD = lin.shape[0], H * 128
     want = torch.empty_like(lin)
     bound = torch.empty_like(lin)

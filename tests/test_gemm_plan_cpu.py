@@ -3,7 +3,8 @@ here, not part of the C ABI) runs the first two on made-up, never dereferenced a
 
 * The model's launches: the ten launches of a denoise step (x2i_amd/flux.py: D = 3072, H = 24, St = 512) in the four configurations and seven
   option variants of tests/test_gemm_fp64_gpu.py, against that module's DEFAULT_FORMS / ALT_FORMS -- tables measured on an MI355X.
-* The forms other GPU tests assert (test_gemm_w4_gpu, test_conv_w4_gpu, test_fp8_gpu), one row each.
+* The forms other GPU tests assert (test_gemm_w4_gpu, test_conv_w4_gpu, test_fp8_gpu), one row each, and every (shape, option, epilogue) of the
+  e4m3 table of tests/test_fp8_fp64_gpu.py with that module's geometry.
 * Batch independence of the two kinds of kernel that sum in another order than the rest -- the FX split and the persistent convolution
   kernels: whether they are chosen is the same for every batch 1..8, over a grid of shapes.
 * Plan sanity on every row, and the refusals' codes and messages stage by stage."""
@@ -13,6 +14,7 @@ import itertools
 import pytest
 
 from tests.test_conv_w4_gpu import CASES, CASES128
+from tests.test_fp8_fp64_gpu import A_ROWS as FP8_A_ROWS, EPILOGUES as FP8_EPILOGUES, GEMM_ROWS as FP8_ROWS, gemm_n as fp8_n
 from tests.test_gemm_fp64_gpu import ALT_FORMS, CONFIGS, DEFAULT_FORMS, LAUNCHES, ST
 from x2i_amd import _lib
 from x2i_amd._lib import ACT_GELU_TANH, ConvDesc, Fp8Desc, GemmArgs, QkvDesc
@@ -193,6 +195,35 @@ def test_forms_asserted_by_the_gpu_tests(lib, opt):
     opt("gemm_streamk", 1)
     opt("gemm_fp8_persist", 0)
     assert form_of(lib, gemm(lib, M, N, K), f=f) == 7256
+
+
+@pytest.mark.parametrize("row", list(FP8_ROWS))
+def test_e4m3_forms_asserted_by_the_fp64_gpu_tests(lib, opt, row):
+    """tests/test_fp8_fp64_gpu.py: one describe per (shape, option, epilogue) of its GEMM table, with that module's geometry (A rows behind an
+    offset in a [batch, 428, K] buffer, C at an offset into rows of ldc = N + 16), and its fused-QKV launches"""
+    M, N0, K, batch, name, value, want, _ = FP8_ROWS[row]
+    if name:
+        opt(name, value)
+    for epi, (scaled, act, out8, oinv, alpha, gated) in FP8_EPILOGUES.items():
+        N = fp8_n(N0, out8)
+        ldc = N + 16
+        c_bs = M * ldc + 64 if batch > 1 else 0
+        kw = dict(batch=batch, a_bs=FP8_A_ROWS * K, lda=K) if batch > 1 else {}
+        a = gemm(lib, M, N, K, c_bs=c_bs, ldc=ldc, act=act, gated=gated, **kw)
+        f = Fp8Desc(a_scale=ptr() if scaled else None, a_scale_batch_stride=M if batch > 1 else 0, w_scale=ptr() if scaled else None, alpha=alpha,
+                    out_fp8=int(out8), out_inv_scale=oinv)
+        assert form_of(lib, a, f=f) == want, (row, epi)
+
+
+@pytest.mark.parametrize("M,Hq,K,batch,want", [(300, 2, 256, 2, 7256), (300, 2, 384, 2, 8256), (2 * FP8_A_ROWS, 2, 256, 1, 7256),
+                                               (2 * FP8_A_ROWS, 2, 384, 1, 8256), (8000, 8, 2048, 1, 9256)])
+def test_e4m3_qkv_forms_asserted_by_the_fp64_gpu_tests(lib, M, Hq, K, batch, want):
+    S = M if M == 8000 else FP8_A_ROWS
+    qd = qkv_desc(S, FP8_A_ROWS - 300 if batch > 1 else 0, 300 if batch > 1 else S)
+    qd.H = Hq
+    f = Fp8Desc(a_scale=ptr(), a_scale_batch_stride=M if batch > 1 else 0, w_scale=ptr(), alpha=1.0, out_fp8=0, out_inv_scale=1.0)
+    kw = dict(batch=batch, a_bs=FP8_A_ROWS * K, lda=K) if batch > 1 else {}
+    assert form_of(lib, gemm(lib, M, 3 * Hq * 128, K, **kw), qd=qd, f=f) == want
 
 
 @pytest.mark.parametrize("case,new,old", [(c, 5256, 256) for c in CASES] + [(c, 5512, 128) for c in CASES128])
