@@ -361,8 +361,9 @@ def find_vpm(model):
 class HipSiglip:
     """The vision tower behind `model.vpm` on the HIP path (x2i_amd/siglip.py: SiglipVisionTower, a bf16 copy of the tower's weights on its
     device).  HipVision's interface: install() replaces the tower module's `forward` ON THE INSTANCE and remove() restores it; between the
-    two the surrounding model's get_vllm_embedding, its Resampler and its embedding scatter run as they always do and get the library's
-    output object from the HIP tower.  Also a context manager.  Independent of the kind of slab, and the same under generate()."""
+    two the surrounding model's get_vllm_embedding, its Resampler (the model's own, or HipResampler's when that is installed too) and its
+    embedding scatter run as they always do and get the library's output object from the HIP tower.  Also a context manager.  Independent
+    of the kind of slab, and the same under generate()."""
 
     def __init__(self, model):
         from .siglip import SiglipVisionTower
@@ -389,6 +390,54 @@ class HipSiglip:
                 self.vpm.forward = self._saved
             else:
                 del self.vpm.forward
+            self._installed = False
+
+    def __enter__(self):
+        return self.install()
+
+    def __exit__(self, *exc):
+        self.remove()
+
+
+def find_resampler(model):
+    """The perceiver of a MiniCPM-o model: `model.resampler`"""
+    r = getattr(model, "resampler", None)
+    if isinstance(r, nn.Module):
+        return r
+    raise RuntimeError("handoff: no resampler (model.resampler) found in %s" % type(model).__name__)
+
+
+class HipResampler:
+    """The perceiver behind `model.resampler` on the HIP path (x2i_amd/resampler.py: Resampler, a bf16 copy of the module's weights on its
+    device).  HipSiglip's interface: install() replaces the module's `forward` ON THE INSTANCE and remove() restores it; between the two
+    the surrounding model's get_vllm_embedding and its embedding scatter run as they always do and get a [B, NQ, D] tensor from the HIP
+    module.  Also a context manager.  Independent of HipSiglip: either, both or neither may be installed."""
+
+    def __init__(self, model):
+        from .resampler import Resampler
+        self.module = find_resampler(model)
+        self.resampler = Resampler.from_hf(self.module)
+        self.calls = 0
+        self._installed = False
+
+    def _forward(self, x, tgt_sizes=None, **kw):
+        self.calls += 1
+        return self.resampler(x, tgt_sizes=tgt_sizes)
+
+    def install(self):
+        if not self._installed:
+            self._had = "forward" in self.module.__dict__
+            self._saved = self.module.__dict__.get("forward")
+            self.module.forward = self._forward
+            self._installed = True
+        return self
+
+    def remove(self):
+        if self._installed:
+            if self._had:
+                self.module.forward = self._saved
+            else:
+                del self.module.forward
             self._installed = False
 
     def __enter__(self):

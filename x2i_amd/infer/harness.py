@@ -75,6 +75,10 @@ def build_parser(family):
                    help="run the MLLM's vision tower on the HIP path instead of the library's forward: Qwen2.5-VL's model.visual "
                         "(x2i_amd/qwen_vision.py) or MiniCPM-o's SigLIP model.vpm (x2i_amd/siglip.py); independent of --hip_decoder and of "
                         "--full_generate")
+    p.add_argument("--hip_resampler", action="store_true",
+                   help="run MiniCPM-o's Resampler (model.resampler, the perceiver behind the SigLIP tower) on the HIP path "
+                        "(x2i_amd/resampler.py) instead of the model's forward; independent of --hip_vision, --hip_decoder and --hip_generate; "
+                        "MiniCPM-o only")
     p.add_argument("--hip_generate", action="store_true",
                    help="run the MLLM's greedy 128-token generate() with the decoder stack on the HIP path over the prompt and over the "
                         "generated tokens (key/value cache, x2i_amd/qwen.py decode_step); serves --use_answer; Qwen2.5-VL only")

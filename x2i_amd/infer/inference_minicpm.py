@@ -25,7 +25,7 @@ class MiniCPMConditioner:
     pass of generate(max_new_tokens=1) (x2i_amd/handoff.py, row N2) -- no hidden-state tuple, no torch.stack copy, and no
     dependence on the reference's patched generate() returning `.hidden_states`.  full_generate: the reference's form."""
 
-    def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None, processor=None, hip_vision=False):
+    def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None, processor=None, hip_vision=False, hip_resampler=False):
         if model is None:
             from transformers import AutoModel, AutoProcessor, AutoTokenizer
             model = AutoModel.from_pretrained(path, trust_remote_code=True, torch_dtype=torch.bfloat16).eval().to(device)
@@ -38,11 +38,17 @@ class MiniCPMConditioner:
             from ..handoff import HiddenStateSlab, find_decoder
             self.slab = HiddenStateSlab(find_decoder(self.model))
         # hip_vision: the SigLIP tower behind model.vpm on the HIP path (x2i_amd/siglip.py), under the slab and under the reference's
-        # generate() alike: get_vllm_embedding still calls it, and the Resampler and the embedding scatter stay the model's own
+        # generate() alike: get_vllm_embedding still calls it, and the embedding scatter stays the model's own
         self.vision = None
         if hip_vision:
             from ..handoff import HipSiglip
             self.vision = HipSiglip(self.model).install()
+        # hip_resampler: the perceiver behind model.resampler on the HIP path (x2i_amd/resampler.py); without it the Resampler stays the
+        # model's own, with or without hip_vision
+        self.resampler = None
+        if hip_resampler:
+            from ..handoff import HipResampler
+            self.resampler = HipResampler(self.model).install()
 
     def hidden_states(self, inputs):
         """processor outputs -> [B, C, S, H]"""
@@ -95,7 +101,8 @@ def main(argv=None):
     torch.cuda.set_device(device)
     cond = SyntheticConditioner("minicpm", device) if args.synthetic else MiniCPMConditioner(args.minicpm_path, device,
                                                                                               prefill_only=not args.full_generate,
-                                                                                              hip_vision=args.hip_vision)
+                                                                                              hip_vision=args.hip_vision,
+                                                                                              hip_resampler=args.hip_resampler)
     Harness(args, "minicpm", cond, device).run_tasks(tasks(args))
 
 
