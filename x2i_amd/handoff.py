@@ -447,6 +447,86 @@ class HipResampler:
         self.remove()
 
 
+def find_apm(model):
+    """The Whisper audio encoder of a MiniCPM-o model: `model.apm`"""
+    a = getattr(model, "apm", None)
+    if isinstance(a, nn.Module):
+        return a
+    raise RuntimeError("handoff: no audio tower (model.apm) found in %s" % type(model).__name__)
+
+
+class HipAudio:
+    """The audio tower behind `model.apm`, with `model.audio_projection_layer` and `model.audio_avg_pooler`, on the HIP path
+    (x2i_amd/whisper.py: WhisperAudioTower, a bf16 copy of the modules' weights on their device).  The model's `apm` is never called as a
+    module for this -- get_audio_embedding builds the mask and picks hidden_states[-1] itself -- so install() replaces
+    `get_audio_embedding` ON THE INSTANCE and remove() restores it; the replacement takes (data, chunk_length=-1, dummy=True) and returns
+    the model's list (per prompt) of lists (per audio) of [n_b, E] tensors, [] for no audio.  What it does not serve goes to the original:
+    a model in training mode, or one whose audio_encoder_layer is not -1.  The embedding scatter (get_omni_embedding) and the streaming
+    path stay the model's own.  Also a context manager.  Independent of HipSiglip and HipResampler, and of the kind of slab."""
+
+    def __init__(self, model):
+        from .whisper import WhisperAudioTower
+        self.model = model
+        self.apm = find_apm(model)
+        proj = getattr(model, "audio_projection_layer", None)
+        if not isinstance(proj, nn.Module):
+            raise RuntimeError("handoff: no audio projector (model.audio_projection_layer) found in %s" % type(model).__name__)
+        cfg = getattr(model, "config", None)
+        step = getattr(cfg, "audio_pool_step", None)
+        if step is None:
+            pooler = getattr(model, "audio_avg_pooler", None)
+            k = getattr(pooler, "kernel_size", None)
+            step = k[0] if isinstance(k, (tuple, list)) else k
+        if step is None:
+            raise RuntimeError("handoff: no pooling step (model.config.audio_pool_step / model.audio_avg_pooler) found in %s" % type(model).__name__)
+        self.tower = WhisperAudioTower.from_hf(self.apm, proj, int(step))
+        self.calls = 0
+        self._installed = False
+
+    def _get_audio_embedding(self, data, chunk_length=-1, dummy=True):
+        model = self.model
+        if model.training or getattr(model, "audio_encoder_layer", -1) != -1:
+            return self._original(data, chunk_length=chunk_length, dummy=dummy)
+        mel = data.get("audio_features", [])
+        if len(mel) == 0:
+            return []
+        lens_raw = data.get("audio_feature_lens", [])
+        lens = [int(n) for group in lens_raw for n in (group.reshape(-1).tolist() if isinstance(group, torch.Tensor) else group)]
+        self.calls += 1
+        out, counts = self.tower(mel, feature_lens=lens, chunk_frames=int(chunk_length * 50) if chunk_length > 0 else 0)
+        final, idx = [], 0
+        for group in lens_raw:
+            mine = []
+            for _ in range(len(group)):
+                mine.append(out[idx, :counts[idx], :])
+                idx += 1
+            final.append(mine)
+        return final
+
+    def install(self):
+        if not self._installed:
+            self._had = "get_audio_embedding" in self.model.__dict__
+            self._saved = self.model.__dict__.get("get_audio_embedding")
+            self._original = self.model.get_audio_embedding
+            self.model.get_audio_embedding = self._get_audio_embedding
+            self._installed = True
+        return self
+
+    def remove(self):
+        if self._installed:
+            if self._had:
+                self.model.get_audio_embedding = self._saved
+            else:
+                del self.model.get_audio_embedding
+            self._installed = False
+
+    def __enter__(self):
+        return self.install()
+
+    def __exit__(self, *exc):
+        self.remove()
+
+
 def prefill_hidden_states(model, dtype=torch.bfloat16, **inputs):
     """Convenience wrapper: [B, C, S, H] conditioning tensor of `inputs` from one forward of `model`."""
     return HiddenStateSlab(find_decoder(model), dtype).prefill(model, **inputs)

@@ -79,6 +79,10 @@ def build_parser(family):
                    help="run MiniCPM-o's Resampler (model.resampler, the perceiver behind the SigLIP tower) on the HIP path "
                         "(x2i_amd/resampler.py) instead of the model's forward; independent of --hip_vision, --hip_decoder and --hip_generate; "
                         "MiniCPM-o only")
+    p.add_argument("--hip_audio", action="store_true",
+                   help="run MiniCPM-o's Whisper audio tower (model.apm with audio_projection_layer and audio_avg_pooler, what "
+                        "get_audio_embedding computes) on the HIP path (x2i_amd/whisper.py) instead of the model's own; independent of "
+                        "--hip_vision, --hip_resampler and --full_generate; MiniCPM-o only")
     p.add_argument("--hip_generate", action="store_true",
                    help="run the MLLM's greedy 128-token generate() with the decoder stack on the HIP path over the prompt and over the "
                         "generated tokens (key/value cache, x2i_amd/qwen.py decode_step); serves --use_answer; Qwen2.5-VL only")

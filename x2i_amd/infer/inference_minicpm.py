@@ -25,7 +25,8 @@ class MiniCPMConditioner:
     pass of generate(max_new_tokens=1) (x2i_amd/handoff.py, row N2) -- no hidden-state tuple, no torch.stack copy, and no
     dependence on the reference's patched generate() returning `.hidden_states`.  full_generate: the reference's form."""
 
-    def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None, processor=None, hip_vision=False, hip_resampler=False):
+    def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None, processor=None, hip_vision=False, hip_resampler=False,
+                 hip_audio=False):
         if model is None:
             from transformers import AutoModel, AutoProcessor, AutoTokenizer
             model = AutoModel.from_pretrained(path, trust_remote_code=True, torch_dtype=torch.bfloat16).eval().to(device)
@@ -49,6 +50,12 @@ class MiniCPMConditioner:
         if hip_resampler:
             from ..handoff import HipResampler
             self.resampler = HipResampler(self.model).install()
+        # hip_audio: the Whisper tower, the projector and the pooling behind get_audio_embedding on the HIP path (x2i_amd/whisper.py), under
+        # either kind of slab; the embedding scatter stays the model's own
+        self.audio = None
+        if hip_audio:
+            from ..handoff import HipAudio
+            self.audio = HipAudio(self.model).install()
 
     def hidden_states(self, inputs):
         """processor outputs -> [B, C, S, H]"""
@@ -102,7 +109,8 @@ def main(argv=None):
     cond = SyntheticConditioner("minicpm", device) if args.synthetic else MiniCPMConditioner(args.minicpm_path, device,
                                                                                               prefill_only=not args.full_generate,
                                                                                               hip_vision=args.hip_vision,
-                                                                                              hip_resampler=args.hip_resampler)
+                                                                                              hip_resampler=args.hip_resampler,
+                                                                                              hip_audio=args.hip_audio)
     Harness(args, "minicpm", cond, device).run_tasks(tasks(args))
 
 

@@ -19,8 +19,8 @@ touch the slab (input_layernorm reading it, the final norm writing it) are launc
 8 + B otherwise.
 
 Parameter names are the library's, so a decoder's state dict loads strictly; the q|k|v weights and biases and the gate|up weights are views
-into stacked storage (as T5Stack's are).  The audio towers and the embedding merge stay on PyTorch, and so do the vision towers but for
-Qwen2.5-VL's, which has a HIP path of its own (x2i_amd/qwen_vision.py): the stack takes `inputs_embeds` (or `input_ids`, a torch gather
+into stacked storage (as T5Stack's are).  The embedding merge stays on PyTorch; the towers in front of it have HIP paths of their own
+(x2i_amd/qwen_vision.py, siglip.py, resampler.py, and whisper.py for MiniCPM-o's audio tower) or stay on PyTorch: the stack takes `inputs_embeds` (or `input_ids`, a torch gather
 from embed_tokens).
 
 Decoding with a key/value cache (include/x2i_qwen_decode.h; the generated answer the reference conditions on under --use_answer) is three
