@@ -527,6 +527,65 @@ class HipAudio:
         self.remove()
 
 
+def find_extract_feature(model):
+    """What extract_feature of an InternVL2.5 chat model runs: (`model.vision_model`, `model.mlp1`), of a model that has the method"""
+    v, m = getattr(model, "vision_model", None), getattr(model, "mlp1", None)
+    if isinstance(v, nn.Module) and isinstance(m, nn.Module) and callable(getattr(model, "extract_feature", None)):
+        return v, m
+    raise RuntimeError("handoff: no extract_feature with model.vision_model and model.mlp1 found in %s" % type(model).__name__)
+
+
+class HipInternVision:
+    """What `extract_feature` of an InternVL2.5 chat model computes -- `model.vision_model` (InternViT), the class token dropped,
+    pixel_shuffle and `model.mlp1` -- on the HIP path (x2i_amd/internvit.py: InternVLVision over an InternVisionTower, a bf16 copy of the
+    modules' weights on their device).  The shuffle and mlp1 live in the chat model and not in vision_model, so install() replaces
+    `extract_feature` ON THE INSTANCE and remove() restores it; the replacement takes pixel_values [B, 3, 448, 448] and returns the
+    model's [B, num_image_token, H_llm].  select_layer, downsample_ratio and ps_version are read off the model.  A model in training mode
+    goes to the original.  With graph=True (the default here) every call after the second of a shape replays one captured graph.  The
+    embedding scatter and the language model stay the model's own.  HipAudio's interface; also a context manager.  Independent of the
+    kind of slab."""
+
+    def __init__(self, model, graph=True):
+        from .internvit import InternVisionTower, InternVLVision
+        self.model = model
+        vision_model, mlp1 = find_extract_feature(model)
+        cfg = getattr(model, "config", None)
+        pick = lambda name, default: getattr(model, name, getattr(cfg, name, default))
+        self.vision = InternVLVision(InternVisionTower.from_hf(vision_model), mlp1, downsample_ratio=pick("downsample_ratio", 0.5),
+                                     ps_version=pick("ps_version", "v2"), select_layer=pick("select_layer", -1), graph=graph)
+        self.calls = 0
+        self._installed = False
+
+    def _extract_feature(self, pixel_values):
+        if self.model.training:
+            return self._original(pixel_values)
+        self.calls += 1
+        return self.vision(pixel_values)
+
+    def install(self):
+        if not self._installed:
+            self._had = "extract_feature" in self.model.__dict__
+            self._saved = self.model.__dict__.get("extract_feature")
+            self._original = self.model.extract_feature
+            self.model.extract_feature = self._extract_feature
+            self._installed = True
+        return self
+
+    def remove(self):
+        if self._installed:
+            if self._had:
+                self.model.extract_feature = self._saved
+            else:
+                del self.model.extract_feature
+            self._installed = False
+
+    def __enter__(self):
+        return self.install()
+
+    def __exit__(self, *exc):
+        self.remove()
+
+
 def prefill_hidden_states(model, dtype=torch.bfloat16, **inputs):
     """Convenience wrapper: [B, C, S, H] conditioning tensor of `inputs` from one forward of `model`."""
     return HiddenStateSlab(find_decoder(model), dtype).prefill(model, **inputs)

@@ -73,7 +73,8 @@ def build_parser(family):
                         "prefill only, so not with --full_generate or --use_answer")
     p.add_argument("--hip_vision", action="store_true",
                    help="run the MLLM's vision tower on the HIP path instead of the library's forward: Qwen2.5-VL's model.visual "
-                        "(x2i_amd/qwen_vision.py) or MiniCPM-o's SigLIP model.vpm (x2i_amd/siglip.py); independent of --hip_decoder and of "
+                        "(x2i_amd/qwen_vision.py), MiniCPM-o's SigLIP model.vpm (x2i_amd/siglip.py) or InternVL2.5's extract_feature -- "
+                        "model.vision_model, pixel_shuffle and model.mlp1 (x2i_amd/internvit.py); independent of --hip_decoder and of "
                         "--full_generate")
     p.add_argument("--hip_resampler", action="store_true",
                    help="run MiniCPM-o's Resampler (model.resampler, the perceiver behind the SigLIP tower) on the HIP path "

@@ -14,7 +14,7 @@ class InternVLConditioner:
     (whose generate() returns token ids); full_generate expects the reference's locally modified modeling_internvl_chat.py, whose
     generate() is one forward returning every layer's hidden states (model_internvl/internvl/modeling_internvl_chat.py:314-363)."""
 
-    def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None):
+    def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None, hip_vision=False):
         if model is None:
             from transformers import AutoModel, AutoTokenizer
             model = AutoModel.from_pretrained(path, trust_remote_code=True, torch_dtype=torch.bfloat16).eval().to(device)
@@ -25,6 +25,12 @@ class InternVLConditioner:
         if prefill_only:
             from ..handoff import HiddenStateSlab, find_decoder
             self.slab = HiddenStateSlab(find_decoder(self.model))
+        # hip_vision: what extract_feature computes (vision_model, pixel_shuffle, mlp1) on the HIP path (x2i_amd/internvit.py), under the
+        # slab and under the reference's generate() alike: the chat model still calls extract_feature, and the scatter stays its own
+        self.vision = None
+        if hip_vision:
+            from ..handoff import HipInternVision
+            self.vision = HipInternVision(self.model).install()
 
     def hidden_states(self, pixel_values, input_ids, attention_mask):
         if self.slab is not None:
@@ -68,7 +74,8 @@ def main(argv=None):
     device = "cuda:%d" % int(__import__("os").environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(device)
     cond = SyntheticConditioner(kind, device) if args.synthetic else InternVLConditioner(args.internvl_path, device,
-                                                                                         prefill_only=not args.full_generate)
+                                                                                         prefill_only=not args.full_generate,
+                                                                                         hip_vision=args.hip_vision)
     Harness(args, kind, cond, device).run_tasks(tasks(args))
 
 
