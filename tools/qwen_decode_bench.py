@@ -12,7 +12,12 @@ Then, per x2i_qwen_decode_linear_bf16 shape of a step, the achieved weight bytes
 same run.  A step streams every weight once, 15 GB for the 7B, so each launch is measured over a ring of distinct weights of over 1 GB
 (nothing is served from the Infinity Cache), the whole ring captured in one graph and replayed (no launch gaps of the host in it).  The copy
 is torch's vectorised copy kernel over the same ring: it reads AND writes, so its rate counts both directions.
-Output: stdout and, with --log, a file (profiles/qwen_decode_bench.log)."""
+With --vocab real the models carry their real vocabularies (152064 x 3584 and 151936 x 2048: the lm_head then streams 1.09 / 0.62 GB per token
+on every side) and a fourth side joins the interleave: HipGenerate(hip_head=True), graph-replayed, the head kernels of
+include/x2i_qwen_head.h inside the captured step; its comparator is `hip graph`, the same loop with the torch head.  --only head times one
+x2i_qwen_head_logits_argmax_bf16 + x2i_qwen_head_select pair over a ring of distinct head weights, beside torch's lm_head call (bf16
+logits) and torch's copy over the same bytes.
+Output: stdout and, with --log, a file (profiles/qwen_decode_bench.log, profiles/qwen_head_bench.log)."""
 import argparse
 import os
 import statistics
@@ -23,12 +28,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from x2i_amd import qwen_decode_ops as qd  # noqa: E402
+from x2i_amd import qwen_head_ops as qh  # noqa: E402
 from x2i_amd.handoff import HipGenerate  # noqa: E402
 
 CONFIGS = {
     "7b": dict(hidden_size=3584, num_attention_heads=28, num_key_value_heads=4, intermediate_size=18944, num_hidden_layers=28, vocab_size=1024),
     "3b": dict(hidden_size=2048, num_attention_heads=16, num_key_value_heads=2, intermediate_size=11008, num_hidden_layers=36, vocab_size=1024),
 }
+REAL_VOCAB = {"7b": 152064, "3b": 151936}
 
 
 def library_model(c, seed=0):
@@ -69,7 +76,7 @@ def wall(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
-def bench_generate(say, name, c, batches, S, T, reps):
+def bench_generate(say, name, c, batches, S, T, reps, head=False):
     model = library_model(c)
     hg = HipGenerate(model, check_mask=False)
     for B in batches:
@@ -81,6 +88,8 @@ def bench_generate(say, name, c, batches, S, T, reps):
             "library": lambda n: model.generate(input_ids=ids, attention_mask=mask, max_new_tokens=n, min_new_tokens=n, do_sample=False, use_cache=True,
                                                 output_hidden_states=True, return_dict_in_generate=True),
         }
+        if head:
+            sides["hip head"] = lambda n: hg.generate(model, max_new_tokens=n, graph=True, hip_head=True, input_ids=ids, attention_mask=mask)
         for fn in sides.values():       # warm-up: every side once at both lengths
             fn(T)
             fn(1)
@@ -99,6 +108,10 @@ def bench_generate(say, name, c, batches, S, T, reps):
         say("%-3s B=%d                              : library / HIP eager %.2f x, library / HIP graph %.2f x; weights %.2f GB per token -> %.2f TB/s at the graph's rate"
             % (name, B, lib / statistics.median(per["hip eager"]), lib / statistics.median(per["hip graph"]), decoder_bytes(c) / 1e9,
                decoder_bytes(c) / (statistics.median(per["hip graph"]) * 1e-3) / 1e12))
+        if head:
+            h, g = statistics.median(per["hip head"]), statistics.median(per["hip graph"])
+            say("%-3s B=%d                              : hip head %.3f ms against hip graph (torch head) %.3f ms per token: %+.3f ms, %.3f x; "
+                "lm_head %.2f GB per token" % (name, B, h, g, h - g, g / h, c["vocab_size"] * c["hidden_size"] * 2 / 1e9))
     del hg, model
     torch.cuda.empty_cache()
 
@@ -158,6 +171,42 @@ def bench_linears(say, name, c, batches, reps):
         torch.cuda.empty_cache()
 
 
+def bench_head(say, name, c, batches, reps):
+    """one logits_argmax + select pair (no logits written, penalty 1.05 over a seen mask) per head weight of a ring, beside torch's lm_head"""
+    V, K = c["vocab_size"], c["hidden_size"]
+    nbytes = V * K * 2
+    ring = max(4, -(-(1 << 30) // nbytes))
+    W = torch.randn((ring, V, K), device="cuda", dtype=torch.bfloat16) * K ** -0.5
+    dst = torch.empty((V, K), device="cuda", dtype=torch.bfloat16)
+    t_copy = graph_ms(lambda: [dst.copy_(W[i]) for i in range(ring)], reps) / ring
+    say("%-3s lm_head       V=%-6d K=%-5d %6.1f MB: copy of the same bytes %.1f us = %.2f TB/s (read + write); the bytes alone at the guide's 6.3 TB/s: %.1f us"
+        % (name, V, K, nbytes / 1e6, t_copy * 1e3, 2 * nbytes / (t_copy * 1e-3) / 1e12, nbytes / 6.3e12 * 1e6))
+    del dst
+    for B in batches:
+        x = torch.randn((B, K), device="cuda").bfloat16()
+        ws = torch.empty((qh.workspace_floats(B, V),), device="cuda", dtype=torch.float32)
+        seen = (torch.rand((B, V), device="cuda") < 0.004).to(torch.uint8)       # about 600 ids: a 512-token prompt and its answer
+        step, token = torch.zeros((1,), device="cuda", dtype=torch.int32), torch.zeros((B,), device="cuda", dtype=torch.long)
+        seq, lengths = torch.zeros((B, 8 * ring), device="cuda", dtype=torch.long), torch.zeros((B,), device="cuda", dtype=torch.long)
+        done = torch.zeros((B,), device="cuda", dtype=torch.uint8)
+
+        def pair(i):
+            qh.logits_argmax(x, W[i], ws, seen=seen, penalty=1.05, step=step)
+            qh.select(ws, step, token, seq, lengths, done, 0, V, seen=seen)
+
+        def body():
+            step.zero_()
+            for i in range(ring):
+                pair(i)
+        t = graph_ms(body, reps) / ring
+        t_torch = graph_ms(lambda: [torch.nn.functional.linear(x, W[i]) for i in range(ring)], reps) / ring
+        say("%-3s lm_head       V=%-6d K=%-5d B=%d          : head kernels %.1f us = %.2f TB/s of weight; torch lm_head (bf16 logits, no penalty, no "
+            "argmax) %.1f us = %.2f TB/s; head / torch %.2f" % (name, V, K, B, t * 1e3, nbytes / (t * 1e-3) / 1e12, t_torch * 1e3,
+                                                                nbytes / (t_torch * 1e-3) / 1e12, t / t_torch))
+    del W
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="7b,3b")
@@ -165,7 +214,9 @@ def main():
     ap.add_argument("--prompt", type=int, default=512)
     ap.add_argument("--tokens", type=int, default=128)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--only", choices=("all", "generate", "linears"), default="all")
+    ap.add_argument("--only", choices=("all", "generate", "linears", "head"), default="all")
+    ap.add_argument("--vocab", choices=("small", "real"), default="small",
+                    help="real: the models' own vocabularies, and the hip_head side in the generate table")
     ap.add_argument("--log", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -177,14 +228,19 @@ def main():
         lines.append(s)
 
     batches = [int(b) for b in a.batches.split(",")]
-    say("qwen_decode_bench: %s, torch %s, prompt %d, %d tokens, %d reps, sides interleaved" % (torch.cuda.get_device_name(0), torch.__version__, a.prompt,
-                                                                                                a.tokens, a.reps))
+    say("qwen_decode_bench: %s, torch %s, prompt %d, %d tokens, %d reps, sides interleaved, vocabulary %s"
+        % (torch.cuda.get_device_name(0), torch.__version__, a.prompt, a.tokens, a.reps, a.vocab))
+    real = a.vocab == "real"
     for name in a.configs.split(","):
+        c = dict(CONFIGS[name], vocab_size=REAL_VOCAB[name]) if real else CONFIGS[name]
         if a.only in ("all", "generate"):
-            bench_generate(say, name, CONFIGS[name], batches, a.prompt, a.tokens, a.reps)
+            bench_generate(say, name, c, batches, a.prompt, a.tokens, a.reps, head=real)
         if a.only in ("all", "linears"):
             with torch.no_grad():
-                bench_linears(say, name, CONFIGS[name], batches, 10)
+                bench_linears(say, name, c, batches, 10)
+        if a.only == "head" or (a.only == "all" and real):
+            with torch.no_grad():
+                bench_head(say, name, dict(CONFIGS[name], vocab_size=REAL_VOCAB[name]), batches, 10)
     if a.log:
         os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
         with open(a.log, "w") as fh:

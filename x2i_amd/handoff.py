@@ -143,6 +143,36 @@ class HipPrefill:
         return slab
 
 
+def head_plan(processors):
+    """What HipGenerate(hip_head=True) makes of a list of `transformers` logits processors: -> the repetition penalty that the head kernel
+    applies (1.0: none).  Needs no GPU.  Accepted, in any order: RepetitionPenaltyLogitsProcessor without prompt_ignore_length (at most one;
+    its penalty is taken), and TemperatureLogitsWarper (temperature > 0), TopKLogitsWarper, TopPLogitsWarper -- monotone maps that keep the top
+    element, so they cannot move an argmax and are dropped (what Qwen2.5-VL's generation_config brings).  Anything else, a subclass included,
+    raises ValueError naming the class: there is no silent fallback to the torch processors."""
+    from transformers.generation.logits_process import (RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper,
+                                                        TopPLogitsWarper)
+    penalty = None
+    for p in processors or []:
+        name = type(p).__name__
+        if type(p) is RepetitionPenaltyLogitsProcessor:
+            if p.prompt_ignore_length:
+                raise ValueError("handoff.HipGenerate: hip_head cannot fuse %s with prompt_ignore_length=%r (the kernel penalises every id of "
+                                 "the sequence); run without --hip_head" % (name, p.prompt_ignore_length))
+            if penalty is not None:
+                raise ValueError("handoff.HipGenerate: hip_head fuses one %s, and the list holds two; run without --hip_head" % name)
+            penalty = float(p.penalty)
+        elif type(p) is TemperatureLogitsWarper:
+            if not p.temperature > 0:
+                raise ValueError("handoff.HipGenerate: hip_head cannot drop %s with temperature=%r (not a monotone map); run without "
+                                 "--hip_head" % (name, p.temperature))
+        elif type(p) in (TopKLogitsWarper, TopPLogitsWarper):
+            pass
+        else:
+            raise ValueError("handoff.HipGenerate: hip_head cannot fuse the logits processor %s (it fuses RepetitionPenaltyLogitsProcessor and "
+                             "drops TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper); run without --hip_head" % name)
+    return 1.0 if penalty is None else penalty
+
+
 class GenerateResult:
     """What HipGenerate.generate returns: prompt bf16 [B, C, S, H] (the prompt pass, HipPrefill's slab), answer bf16 [B, C, T - 1, H] (the
     decode passes: column t is the pass whose input is generated token t; the pass of the last token never runs, the HF convention),
@@ -162,15 +192,22 @@ class HipGenerate:
     optional `transformers` logits processors (torch), argmax.  With graph=True the gather, the step and the lm_head are captured ONCE in a
     torch.cuda.graph (one stream, no parallel branches) and replayed; the processors and the argmax follow each replay as torch ops.
     Finished samples are tracked on the device and the host looks once every `check_every` steps.  The cache and the graph captured on it
-    stay resident between calls and serve every later call of the same batch size and rounded capacity (prompt + new tokens)."""
+    stay resident between calls and serve every later call of the same batch size and rounded capacity (prompt + new tokens).
+    With hip_head=True (off by default; per call generate(hip_head=...)) the step's tail is on the HIP path too (x2i_amd/qwen_head_ops.py):
+    the lm_head, the repetition penalty and a per-workgroup argmax in one launch, the choice of the token with the end-token bookkeeping in
+    a second, both inside the captured step, so a generated token is one graph replay and no torch op; token 0 goes through the same two
+    kernels on each sample's last valid prompt row.  head_plan decides which processor lists fuse; any other raises.  A token is then the
+    argmax of f32-accumulated logits that were never rounded to bf16: where the top two logits lie within one bf16 ulp the torch head ties
+    them and takes the lower index, so the two paths can pick different tokens there."""
 
-    def __init__(self, model, check_mask=True):
+    def __init__(self, model, check_mask=True, hip_head=False):
         from .qwen import Qwen2DecoderStack
         self.decoder = find_decoder(model)
         self.stack = Qwen2DecoderStack.from_hf(self.decoder)
         self.n_layers = len(self.decoder.layers)
         self.C = self.n_layers + 1
         self.check_mask = check_mask
+        self.hip_head = hip_head
         self.slab = self._cache = None
         self._state = {}
 
@@ -203,10 +240,11 @@ class HipGenerate:
 
     @torch.no_grad()
     def generate(self, model, max_new_tokens=128, eos_token_id=None, pad_token_id=None, logits_processor=None, graph=True, check_every=16,
-                 generation_config=None, **inputs):
+                 generation_config=None, hip_head=None, **inputs):
         """-> GenerateResult.  inputs: the model's forward arguments of the prompt (input_ids required; attention_mask, pixel_values, ...).
         eos_token_id: an id, a list of ids or None (never stop early); pad_token_id: what follows a sample's end token (default: the first
-        end token, else 0).  logits_processor: a list of callables (input_ids [B, len], scores f32 [B, V]) -> scores."""
+        end token, else 0).  logits_processor: a list of callables (input_ids [B, len], scores f32 [B, V]) -> scores.  hip_head: None takes
+        the constructor's; True needs a list that head_plan accepts."""
         self.refuse_sampling(generation_config if generation_config is not None else getattr(model, "generation_config", None))
         if max_new_tokens < 1:
             raise ValueError("handoff.HipGenerate: max_new_tokens must be at least 1")
@@ -216,7 +254,19 @@ class HipGenerate:
         eos = [] if eos_token_id is None else ([int(eos_token_id)] if not isinstance(eos_token_id, (list, tuple)) else [int(e) for e in eos_token_id])
         pad = int(pad_token_id) if pad_token_id is not None else (eos[0] if eos else 0)
         processors = list(logits_processor or [])
+        hip_head = self.hip_head if hip_head is None else hip_head
         head = model.get_output_embeddings()
+        if hip_head:       # every refusal comes before anything runs
+            import inspect
+            penalty = head_plan(processors)
+            if len(eos) > 8:
+                raise ValueError("handoff.HipGenerate: hip_head takes at most 8 end tokens (got %d)" % len(eos))
+            if getattr(head, "bias", None) is not None or head.weight.dtype != torch.bfloat16 or not head.weight.is_contiguous():
+                raise ValueError("handoff.HipGenerate: hip_head needs a contiguous bf16 lm_head weight and no bias")
+            if not 0 <= pad < head.weight.shape[0]:
+                raise ValueError("handoff.HipGenerate: hip_head needs a pad token inside the vocabulary (got %d)" % pad)
+            if "logits_to_keep" in inspect.signature(model.forward).parameters and "logits_to_keep" not in inputs:
+                inputs = dict(inputs, logits_to_keep=1)       # the model's own logits are not used: one position, not all S
         self.slab = self._cache = None
         self._new_tokens = max_new_tokens
         had = "forward" in self.decoder.__dict__
@@ -237,6 +287,8 @@ class HipGenerate:
         T = max_new_tokens
         rows = torch.arange(B, device=dev)
         last = (cache.k_hi - 1).long()                                   # the last valid token of each sample, under either padding
+        if hip_head:
+            return self._generate_hip_head(prompt, cache, ids, head.weight, penalty, eos, pad, T, rows, last, graph, check_every)
         sequences = torch.full((B, S + T), pad, device=dev, dtype=torch.long)
         sequences[:, :S] = ids
         answer = torch.empty((B, C, max(T - 1, 0), H), device=dev, dtype=torch.bfloat16)
@@ -299,6 +351,76 @@ class HipGenerate:
         n = int(lengths.max()) if eos_t is not None else T                # (tokens after every sample's end are dropped: one host read)
         n = max(n, 1)
         return GenerateResult(prompt, answer[:, :, :n - 1], sequences[:, :S + n], lengths)
+
+    def _generate_hip_head(self, prompt, cache, ids, W, penalty, eos, pad, T, rows, last, graph, check_every):
+        """generate()'s loop with the head kernels: every word of the loop's state lives in buffers that stay with the cache, so that the
+        captured step (gather, decode_step, the copy into the answer at the device counter's column, both head kernels) replays."""
+        from . import qwen_head_ops as HO
+        dev = prompt.device
+        B, C, S, H = prompt.shape
+        V = W.shape[0]
+        st = self._state
+        hkey = (W.data_ptr(), V, penalty, pad, tuple(eos))         # what a captured step holds by value
+        if st.get("hkey") != hkey or st["h_answer"].shape[2] < T - 1:
+            st.pop("hgraph", None)
+            st["hkey"] = hkey
+            st["h_token"] = torch.zeros((B,), device=dev, dtype=torch.long)
+            st["h_out"] = torch.empty((B, C, H), device=dev, dtype=torch.bfloat16)
+            st["h_answer"] = torch.empty((B, C, max(T - 1, 1), H), device=dev, dtype=torch.bfloat16)
+            st["h_seq"] = torch.empty((B, st["key"][1]), device=dev, dtype=torch.long)
+            st["h_seen"] = torch.empty((B, V), device=dev, dtype=torch.uint8)
+            st["h_ws"] = torch.empty((HO.workspace_floats(B, V),), device=dev, dtype=torch.float32)
+            st["h_step"] = torch.zeros((1,), device=dev, dtype=torch.int32)
+            st["h_base"] = torch.zeros((1,), device=dev, dtype=torch.long)
+            st["h_done"] = torch.zeros((B,), device=dev, dtype=torch.uint8)
+            st["h_len"] = torch.zeros((B,), device=dev, dtype=torch.long)
+            st["h_eos"] = torch.tensor(eos, device=dev, dtype=torch.long) if eos else None
+        token, step_out, abuf, seq, seen, ws = st["h_token"], st["h_out"], st["h_answer"], st["h_seq"], st["h_seen"], st["h_ws"]
+        step, base, done, lengths, eos_t = st["h_step"], st["h_base"], st["h_done"], st["h_len"], st["h_eos"]
+        seq.fill_(pad)
+        seq[:, :S] = ids
+        seen.zero_().scatter_(1, ids.long(), 1)                    # every id of input_ids, pad ids included (the library's processor)
+        step.fill_(S)                                              # the column of token 0
+        base.fill_(S + 1)                                          # the pass of token t - 1 runs with the counter at S + t: answer column t - 1
+        done.zero_()
+        lengths.zero_()
+
+        def pick(x):
+            HO.logits_argmax(x, W, ws, seen=seen, penalty=penalty, step=step)
+            HO.select(ws, step, token, seq, lengths, done, pad, V, eos=eos_t, seen=seen)
+
+        def one_step():
+            self.stack.decode_step(cache, input_ids=token, out=step_out)
+            abuf.index_copy_(2, step.long() - base, step_out.unsqueeze(2))
+            pick(step_out[:, -1])
+
+        pick(prompt[:, -1][rows, last].contiguous())               # token 0: the same two kernels on each sample's last valid row
+        t = 1
+        while t < T:
+            if check_every and t % check_every == 0 and eos_t is not None and bool(done.all()):      # the one host read per check_every steps
+                break
+            if not graph:
+                one_step()
+            elif "hgraph" not in st and not st.get("hwarm"):
+                side = torch.cuda.Stream()                         # the warm-up a capture needs
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    one_step()
+                torch.cuda.current_stream().wait_stream(side)
+                st["hwarm"] = True
+            else:
+                if "hgraph" not in st:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        one_step()
+                    cache.steps -= 1                               # (a capture runs nothing: the replay below is this step)
+                    st["hgraph"] = g
+                st["hgraph"].replay()
+                cache.steps += 1
+            t += 1
+        n = int(lengths.max()) if eos_t is not None else T                # (tokens after every sample's end are dropped: one host read)
+        n = max(n, 1)
+        return GenerateResult(prompt, abuf[:, :, :n - 1].clone(), seq[:, :S + n].clone(), lengths.clone())
 
 
 def find_visual(model):

@@ -87,6 +87,12 @@ def build_parser(family):
     p.add_argument("--hip_generate", action="store_true",
                    help="run the MLLM's greedy 128-token generate() with the decoder stack on the HIP path over the prompt and over the "
                         "generated tokens (key/value cache, x2i_amd/qwen.py decode_step); serves --use_answer; Qwen2.5-VL only")
+    p.add_argument("--hip_head", action="store_true",
+                   help="with --hip_generate: choose every token on the HIP path too (x2i_amd/qwen_head_ops.py) -- the lm_head, the repetition "
+                        "penalty and the argmax inside the captured step, no [B, V] logits written; the temperature, top-k and top-p warpers of "
+                        "the generation_config cannot move an argmax and are dropped, any other logits processor is refused by name.  A token is "
+                        "the argmax of f32 logits that are not rounded to bf16, so where the top two logits lie within one bf16 ulp it can "
+                        "differ from the torch head's; Qwen2.5-VL only")
     p.add_argument("--decode", action="store_true", help="with --synthetic: also run the (random-weight) VAE decoder and save images")
     return p
 

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Interactive multi-turn Qwen2.5-VL -> image loop on the HIP path.  Counterpart of infer/inference_multi_turn.py: the
 chat history grows each turn, the model answers with max_new_tokens=64, and the conditioning is the prompt-pass hidden
-states concatenated along S with the generated-token hidden states (:132-141); 4 steps, 1024x1024, manual_seed(0)."""
+states concatenated along S with the generated-token hidden states (:132-141); 4 steps, 1024x1024, manual_seed(0).
+With --hip_generate a turn is one handoff.HipGenerate.generate call (the decoder stack on the HIP path over the prompt and the answer),
+with --hip_head its tokens are chosen on the HIP path too."""
 import time
 
 import torch
@@ -10,12 +12,23 @@ from .harness import Harness, SyntheticConditioner, build_parser, stack_hidden_s
 
 
 class MultiTurnConditioner:
-    def __init__(self, path, device):
-        from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
-        self.model = Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
-        self.processor = AutoProcessor.from_pretrained(path)
+    """model / processor: hand in loaded ones (a test's tiny model and stub processor) and `path` is not read."""
+
+    def __init__(self, path, device, hip_generate=False, hip_head=False, model=None, processor=None):
+        if model is None or processor is None:
+            from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
+            model = model if model is not None else Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
+            processor = processor if processor is not None else AutoProcessor.from_pretrained(path)
+        self.model, self.processor = model, processor
         self.device = device
         self.history = []
+        self.generate = None
+        if hip_head and not hip_generate:
+            raise ValueError("--hip_head chooses the tokens of --hip_generate's loop: not without --hip_generate")
+        if hip_generate:
+            from ..handoff import HipGenerate
+            HipGenerate.refuse_sampling(self.model.generation_config)
+            self.generate = HipGenerate(self.model, hip_head=hip_head)
 
     @torch.no_grad()
     def __call__(self, images=None, text_prompt=None, **_):
@@ -30,6 +43,16 @@ class MultiTurnConditioner:
         prompt = self.processor.apply_chat_template(self.history, tokenize=False, add_generation_prompt=True)
         all_ims = [c["image"] for m in self.history if m["role"] == "user" for c in m["content"] if c["type"] == "image"]
         inputs = self.processor(text=[prompt], images=all_ims or None, return_tensors="pt").to(self.device)
+        if self.generate is not None:
+            gc = self.model.generation_config
+            S = inputs["input_ids"].shape[1]
+            out = self.generate.generate(self.model, max_new_tokens=64, eos_token_id=gc.eos_token_id, pad_token_id=gc.pad_token_id,
+                                         logits_processor=self.model._get_logits_processor(gc, input_ids_seq_length=S, device=self.device), **inputs)
+            answer = self.processor.batch_decode(out.sequences[:, S:], skip_special_tokens=True)[0]
+            self.history.append({"role": "assistant", "content": [{"type": "text", "text": answer}]})
+            if out.answer.shape[2] > 0:
+                return torch.cat([out.prompt, out.answer], dim=2), answer
+            return out.prompt, answer
         out = self.model.generate(**inputs, max_new_tokens=64, output_hidden_states=True, return_dict_in_generate=True)
         answer = self.processor.batch_decode(out.sequences[:, inputs.input_ids.shape[1]:], skip_special_tokens=True)[0]
         self.history.append({"role": "assistant", "content": [{"type": "text", "text": answer}]})
@@ -67,7 +90,7 @@ def main(argv=None):
     torch.cuda.set_device(device)
     if args.synthetic:
         return synthetic_turns(args, kind, device)
-    cond = MultiTurnConditioner(args.qwen_path, device)
+    cond = MultiTurnConditioner(args.qwen_path, device, hip_generate=args.hip_generate, hip_head=args.hip_head)
     h = Harness(args, kind, lambda **kw: cond(**kw)[0], device)
     turn = 0
     while True:

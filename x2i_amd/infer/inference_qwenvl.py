@@ -14,7 +14,7 @@ class QwenVLConditioner:
     """Qwen2_5_VLForConditionalGeneration prompt pass; inputs padded to 512 tokens, images resized to 128x128, videos at
     1 fps / 128*128 pixels, generate(max_new_tokens=128, output_hidden_states=True) -- infer/inference_qwenvl.py:136-180."""
 
-    def __init__(self, path, device, use_answer=False, prefill_only=True, hip_decoder=False, hip_vision=False, hip_generate=False):
+    def __init__(self, path, device, use_answer=False, prefill_only=True, hip_decoder=False, hip_vision=False, hip_generate=False, hip_head=False):
         from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
         self.model = Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
         self.processor = AutoProcessor.from_pretrained(path)
@@ -27,12 +27,14 @@ class QwenVLConditioner:
         # hip_generate: the whole greedy generate() with the decoder stack on the HIP path (handoff.HipGenerate): the generated tokens' states
         # under --use_answer, the prompt's otherwise
         self.generate = None
+        if hip_head and not hip_generate:
+            raise ValueError("--hip_head chooses the tokens of --hip_generate's loop: not without --hip_generate")
         if hip_generate:
             if hip_decoder:
                 raise ValueError("--hip_generate runs the prompt pass on the HIP path itself: not together with --hip_decoder")
             from ..handoff import HipGenerate
             HipGenerate.refuse_sampling(self.model.generation_config)
-            self.generate = HipGenerate(self.model)
+            self.generate = HipGenerate(self.model, hip_head=hip_head)
         elif prefill_only and not use_answer:
             from ..handoff import HiddenStateSlab, HipPrefill, find_decoder
             # hip_decoder: the same one forward with the decoder stack itself on the HIP path (x2i_amd/qwen.py)
@@ -106,7 +108,7 @@ def main(argv=None):
     torch.cuda.set_device(device)
     cond = SyntheticConditioner(kind, device) if args.synthetic else QwenVLConditioner(args.qwen_path, device, args.use_answer, prefill_only=not args.full_generate,
                                                                                             hip_decoder=args.hip_decoder, hip_vision=args.hip_vision,
-                                                                                            hip_generate=args.hip_generate)
+                                                                                            hip_generate=args.hip_generate, hip_head=args.hip_head)
     Harness(args, kind, cond, device).run_tasks(tasks(args))
 
 
