@@ -258,6 +258,25 @@ def test_c_abi_argument_validation_returns_codes_without_a_gpu():
     assert lib.x2i_rope_table_f32(fake, 8, 16, 55, 56, 10000.0, fake, fake, None) < 0  # odd axis width
     assert lib.x2i_timestep_sinusoid(fake, fake, 1, 255, 0, None) < 0
     assert lib.x2i_conv_stem_bf16(None, None, None, None, 1, 8, 8, 64, None) < 0
+    # the projector's layer fusion: both conv entry points and the pack refuse H % 8, C = 0, a [C, S, H] slab of 2 GB and misaligned pointers
+    err = lib.x2i_last_error
+    off8, off4, off2 = C.c_void_p(0x1008), C.c_void_p(0x1004), C.c_void_p(0x1002)
+    for conv in (lib.x2i_proj_conv5x5_bf16, lib.x2i_proj_conv5x5_packed_bf16):
+        assert conv(fake, fake, None, fake, 1, 3, 4, 12, None) < 0 and b"H=12" in err()
+        assert conv(fake, fake, None, fake, 1, 0, 4, 16, None) < 0
+        assert conv(fake, fake, None, fake, 1, 64, 4096, 4096, None) < 0 and b"2 GB" in err()
+        assert conv(fake, fake, None, fake, 1, 1, 65024, 16384, None) < 0 and b"2 GB" in err()          # 0x7f000000 bytes: the first size refused
+        assert conv(off8, fake, None, fake, 1, 3, 4, 16, None) < 0 and b"aligned" in err()
+        assert conv(None, fake, None, fake, 1, 3, 4, 16, None) < 0 and b"null" in err()
+        assert conv(fake, fake, None, None, 1, 3, 4, 16, None) < 0 and b"null" in err()
+    assert lib.x2i_proj_conv5x5_bf16(fake, fake, None, fake, 1, 65, 4, 16, None) < 0 and b"C=65" in err()
+    assert lib.x2i_proj_conv5x5_bf16(fake, fake, None, off2, 1, 3, 4, 16, None) < 0 and b"aligned" in err()          # y: 4 bytes
+    assert lib.x2i_proj_conv5x5_packed_bf16(fake, fake, None, off4, 1, 3, 4, 16, None) < 0 and b"aligned" in err()   # y: 8 bytes
+    assert lib.x2i_proj_conv5x5_packed_bf16(fake, off8, None, fake, 1, 3, 4, 16, None) < 0 and b"aligned" in err()   # table: 16 bytes
+    assert lib.x2i_proj_conv5x5_pack(fake, fake, 0, None) < 0 and b"C=0" in err()
+    assert lib.x2i_proj_conv5x5_pack(fake, off8, 3, None) < 0 and b"aligned" in err()
+    assert lib.x2i_proj_conv5x5_pack(None, fake, 3, None) < 0 and b"null" in err()
+    assert lib.x2i_proj_layer_mean_bf16(fake, None, fake, 1, 2, 12, None) < 0 and b"multiple of 8" in err()
     assert lib.x2i_abi_version() >= 1
 
 
