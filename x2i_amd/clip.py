@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import clip_ops, ops, t5_ops
+from ._packed import WB, PackedModule, config_fields, config_object
 
 _FIELDS = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12,
                max_position_embeddings=77, hidden_act="quick_gelu", layer_norm_eps=1e-5, eos_token_id=49407)
@@ -48,27 +49,6 @@ class CLIPTextOutput(tuple):
         return self[1]
 
 
-class _WB(nn.Module):
-    def __init__(self, weight, bias=None):
-        super().__init__()
-        as_param = lambda t: t if isinstance(t, nn.Parameter) else nn.Parameter(t, requires_grad=False)
-        self.weight = as_param(weight)
-        if bias is not None:
-            self.bias = as_param(bias)
-
-
-def _config_fields(config, kw):
-    f = dict(_FIELDS)
-    if config is not None:
-        for k in f:
-            f[k] = getattr(config, k, f[k])
-    unknown = set(kw) - set(f)
-    if unknown:
-        raise TypeError("CLIPTextModel: unknown configuration fields %s" % sorted(unknown))
-    f.update(kw)
-    return f
-
-
 def _canonical_keys(state_dict):
     """The module's own (4.x, `text_model.`-prefixed) names for a state dict in either spelling; the 4.x buffer `embeddings.position_ids`
     (persistent in old checkpoints, arange(max_position_embeddings) by construction) is not a parameter and is dropped."""
@@ -83,13 +63,13 @@ def _canonical_keys(state_dict):
     return out
 
 
-class CLIPTextModel(nn.Module):
+class CLIPTextModel(PackedModule):
     """Drop-in for transformers.CLIPTextModel as the reference calls it: `model(input_ids, output_hidden_states=False)` ->
     `.pooler_output` bf16 [B, hidden], `.last_hidden_state` bf16 [B, S, hidden]."""
 
     def __init__(self, config=None, device="cuda", dtype=torch.bfloat16, **kw):
-        super().__init__()
-        f = _config_fields(config, kw)
+        super().__init__(device)
+        f = config_fields(_FIELDS, config, kw, "CLIPTextModel")
         if f["hidden_act"] != "quick_gelu":
             raise ValueError("x2i_amd CLIPTextModel: hidden_act=%r is not built (quick_gelu only)" % (f["hidden_act"],))
         D, H, F = f["hidden_size"], f["num_attention_heads"], f["intermediate_size"]
@@ -99,92 +79,54 @@ class CLIPTextModel(nn.Module):
             raise ValueError("x2i_amd CLIPTextModel: intermediate_size must be a multiple of 8")
         if dtype != torch.bfloat16:
             raise ValueError("x2i_amd: the HIP path computes in bf16 (fp32 statistics/accumulation)")
-        self.config = type("CLIPTextConfig", (), dict(f))()
-        dev = torch.device(device)
-        self._fused = {}
-        self._views = []
-
-        def param(*shape):
-            return nn.Parameter(torch.empty(shape, device=dev, dtype=dtype), requires_grad=False)
-
-        def view(name, r0, r1):
-            p = nn.Parameter(self._fused[name][r0:r1], requires_grad=False)
-            self._views.append((p, name, slice(r0, r1)))
-            return p
-
+        self.config = config_object("CLIPTextConfig", f)
+        param = self._param
+        view = lambda name, r0, r1: self._view(name, slice(r0, r1))
         tm = nn.Module()
         emb = nn.Module()
-        emb.add_module("token_embedding", _WB(param(f["vocab_size"], D)))
-        emb.add_module("position_embedding", _WB(param(f["max_position_embeddings"], D)))
+        emb.add_module("token_embedding", WB(param(f["vocab_size"], D)))
+        emb.add_module("position_embedding", WB(param(f["max_position_embeddings"], D)))
         tm.add_module("embeddings", emb)
         layers = []
         for i in range(f["num_hidden_layers"]):
-            self._fused["%d.qkv.w" % i] = torch.empty((3 * D, D), device=dev, dtype=dtype)
-            self._fused["%d.qkv.b" % i] = torch.empty((3 * D,), device=dev, dtype=dtype)
+            self._store("%d.qkv.w" % i, 3 * D, D)
+            self._store("%d.qkv.b" % i, 3 * D)
             att = nn.Module()
             for j, nm in enumerate("qkv"):
-                att.add_module(nm + "_proj", _WB(view("%d.qkv.w" % i, j * D, (j + 1) * D), view("%d.qkv.b" % i, j * D, (j + 1) * D)))
-            att.add_module("out_proj", _WB(param(D, D), param(D)))
+                att.add_module(nm + "_proj", WB(view("%d.qkv.w" % i, j * D, (j + 1) * D), view("%d.qkv.b" % i, j * D, (j + 1) * D)))
+            att.add_module("out_proj", WB(param(D, D), param(D)))
             mlp = nn.Module()
-            mlp.add_module("fc1", _WB(param(F, D), param(F)))
-            mlp.add_module("fc2", _WB(param(D, F), param(D)))
+            mlp.add_module("fc1", WB(param(F, D), param(F)))
+            mlp.add_module("fc2", WB(param(D, F), param(D)))
             layer = nn.Module()
             layer.add_module("self_attn", att)
-            layer.add_module("layer_norm1", _WB(param(D), param(D)))
+            layer.add_module("layer_norm1", WB(param(D), param(D)))
             layer.add_module("mlp", mlp)
-            layer.add_module("layer_norm2", _WB(param(D), param(D)))
+            layer.add_module("layer_norm2", WB(param(D), param(D)))
             layers.append(layer)
         enc = nn.Module()
         enc.add_module("layers", nn.ModuleList(layers))
         tm.add_module("encoder", enc)
-        tm.add_module("final_layer_norm", _WB(param(D), param(D)))
+        tm.add_module("final_layer_norm", WB(param(D), param(D)))
         self.text_model = tm
-        self._ws = {}
 
-    # ------------------------------------------------------------------ nn.Module plumbing
-    @property
-    def dtype(self):
-        return torch.bfloat16
+    _canonical_keys = staticmethod(_canonical_keys)     # load_state_dict takes either spelling of the library's keys (with or without `text_model.`)
 
-    @property
-    def device(self):
-        return self.text_model.final_layer_norm.weight.device
-
-    def _apply(self, fn, recurse=True):
-        # the stacked q|k|v parameters are views: move the storage, re-point the views, then the ordinary parameters
-        for k in list(self._fused):
-            new = fn(self._fused[k])
-            if new.dtype != torch.bfloat16:
-                raise ValueError("x2i_amd CLIPTextModel is bf16-only")
-            self._fused[k] = new
-        for p, name, sl in self._views:
-            p.data = self._fused[name][sl]
-        self._ws = {}
-        return super()._apply(fn, recurse)
-
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        """Either spelling of the library's keys (with or without `text_model.`); strict about everything else."""
-        if assign:
-            raise ValueError("x2i_amd CLIPTextModel: assign=True would detach the stacked q|k|v views")
-        return super().load_state_dict(_canonical_keys(state_dict), strict=strict)
-
-    @torch.no_grad()
     def init_random_(self, seed=0):
         """Random weights in place on the device (tools and smoke runs; there are no checkpoints offline): linears N(0, 1 / fan_in), norm
         weights 1 + 0.1 N(0, 1), biases 0.1 N(0, 1), the token table N(0, 0.02^2) and the position table N(0, 0.01^2) as the library draws them."""
-        gen = torch.Generator(device=self.device).manual_seed(seed)
-        for n, p in self.named_parameters():
-            r = torch.randn(p.shape, device=p.device, generator=gen)
+        def rule(n, p, r):
             if n.endswith("token_embedding.weight"):
-                p.copy_(0.02 * r)
-            elif n.endswith("position_embedding.weight"):
-                p.copy_(0.01 * r)
-            elif p.dim() == 2:
-                p.copy_(r * p.shape[1] ** -0.5)
-            elif "layer_norm" in n and n.endswith(".weight"):
-                p.copy_(1.0 + 0.1 * r)
-            else:
-                p.copy_(0.1 * r)
+                return 0.02 * r
+            if n.endswith("position_embedding.weight"):
+                return 0.01 * r
+            if p.dim() == 2:
+                return r * p.shape[1] ** -0.5
+            if "layer_norm" in n and n.endswith(".weight"):
+                return 1.0 + 0.1 * r
+            return 0.1 * r
+
+        self._init_random(seed, rule)
         return self
 
     def _workspace(self, B, S):

@@ -39,7 +39,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import internvit_ops, ops, siglip_ops, t5_ops, vit_ops
-from .qwen import _WB
+from ._packed import WB, PackedModule, config_fields, config_object
 
 _FIELDS = dict(hidden_size=1024, num_attention_heads=16, num_hidden_layers=24, intermediate_size=4096, image_size=448, patch_size=14,
                layer_norm_eps=1e-6, hidden_act="gelu", norm_type="layer_norm", qk_normalization=False, qkv_bias=True, num_channels=3)
@@ -57,21 +57,17 @@ class InternVisionPlan:
     """Everything of a call that depends on (B, gh, gw) alone (InternVisionTower.plan)"""
 
 
-class InternVisionTower(nn.Module):
+class InternVisionTower(PackedModule):
     """Drop-in for `model.vision_model`.  forward(pixel_values [B, 3, gh*P, gw*P]) -> BaseModelOutputWithPooling(last_hidden_state bf16
     [B, 1 + gh*gw, hidden], pooler_output = its class row); select_layer picks the reference's hidden_states[select_layer] instead.
     Eval only."""
 
+    _eval_only = True
+    _copies = "_ls"
+
     def __init__(self, config=None, device="cuda", dtype=torch.bfloat16, **kw):
-        super().__init__()
-        f = dict(_FIELDS)
-        if config is not None:
-            for k in f:
-                f[k] = getattr(config, k, f[k])
-        unknown = set(kw) - set(f)
-        if unknown:
-            raise TypeError("InternVisionTower: unknown configuration fields %s" % sorted(unknown))
-        f.update(kw)
+        super().__init__(device)
+        f = config_fields(_FIELDS, config, kw, "InternVisionTower")
         if dtype != torch.bfloat16:
             raise ValueError("x2i_amd: the HIP path computes in bf16 (fp32 statistics/accumulation); dtype=%r is not built" % (dtype,))
         if f["hidden_act"] != "gelu":
@@ -86,37 +82,32 @@ class InternVisionTower(nn.Module):
         if f["num_channels"] != 3 or not 1 <= P <= 32 or f["image_size"] // P < 1:
             raise ValueError("x2i_amd InternVisionTower: need 3 channels, patch_size in 1..32 and image_size >= patch_size")
         f["head_dim"] = D // H
-        self.config = type("InternVisionTowerConfig", (), dict(f))()
+        self.config = config_object("InternVisionTowerConfig", f)
         self.side = side = f["image_size"] // P         # patches per side of the position table
         self.patch_dim = Kpe = 3 * P * P
         self.Kp = Kp = internvit_ops.pad64(Kpe)
         self.rms = f["norm_type"] == "rms_norm"
-        dev = torch.device(device)
-        self._pe = torch.zeros((D, Kp), device=dev, dtype=dtype)
+        self._store("pe", D, Kp, zero=True)
         self._ls = None
-        self._plans = {}
         self._pos = {}
-
-        def param(*shape):
-            return nn.Parameter(torch.empty(shape, device=dev, dtype=dtype), requires_grad=False)
-
-        norm = lambda: _WB(param(D), None if self.rms else param(D))
+        param = self._param
+        norm = lambda: WB(param(D), None if self.rms else param(D))
         emb = nn.Module()
         emb.class_embedding = param(1, 1, D)
-        emb.add_module("patch_embedding", _WB(nn.Parameter(self._pe[:, :Kpe].view(D, 3, P, P), requires_grad=False), param(D)))
+        emb.add_module("patch_embedding", WB(self._view("pe", (slice(None), slice(0, Kpe)), (D, 3, P, P)), param(D)))
         emb.position_embedding = param(1, 1 + side * side, D)
         self.embeddings = emb
         layers = []
         for _ in range(NL):
             att = nn.Module()
-            att.add_module("qkv", _WB(param(3 * D, D), param(3 * D) if f["qkv_bias"] else None))
+            att.add_module("qkv", WB(param(3 * D, D), param(3 * D) if f["qkv_bias"] else None))
             if f["qk_normalization"]:
-                att.add_module("q_norm", _WB(param(D)))
-                att.add_module("k_norm", _WB(param(D)))
-            att.add_module("proj", _WB(param(D, D), param(D)))
+                att.add_module("q_norm", WB(param(D)))
+                att.add_module("k_norm", WB(param(D)))
+            att.add_module("proj", WB(param(D, D), param(D)))
             mlp = nn.Module()
-            mlp.add_module("fc1", _WB(param(F_, D), param(F_)))
-            mlp.add_module("fc2", _WB(param(D, F_), param(D)))
+            mlp.add_module("fc1", WB(param(F_, D), param(F_)))
+            mlp.add_module("fc2", WB(param(D, F_), param(D)))
             layer = nn.Module()
             layer.add_module("attn", att)
             layer.add_module("mlp", mlp)
@@ -129,40 +120,14 @@ class InternVisionTower(nn.Module):
         self.encoder.add_module("layers", nn.ModuleList(layers))
         self.eval()
 
-    # ------------------------------------------------------------------ nn.Module plumbing
     @property
-    def dtype(self):
-        return torch.bfloat16
+    def _pe(self):
+        """The patch embedding's [hidden, Kp] matrix, of which the Conv2d weight is a view"""
+        return self._fused["pe"]
 
-    @property
-    def device(self):
-        return self.embeddings.class_embedding.device
-
-    def train(self, mode=True):
-        if mode:
-            raise ValueError("x2i_amd InternVisionTower is eval-only")
-        return super().train(False)
-
-    def _apply(self, fn, recurse=True):
-        # the Conv2d weight is a view: move the storage, re-point the view, then the ordinary parameters; the f32 copies are made again
-        new = fn(self._pe)
-        if new.dtype != torch.bfloat16:
-            raise ValueError("x2i_amd InternVisionTower is bf16-only")
-        self._pe = new
-        c = self.config
-        self.embeddings.patch_embedding.weight.data = new[:, :self.patch_dim].view(c.hidden_size, 3, c.patch_size, c.patch_size)
-        self._plans, self._pos = {}, {}
-        out = super()._apply(fn, recurse)
-        if self._ls is not None:
-            self.pack_()
-        return out
-
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        if assign:
-            raise ValueError("x2i_amd InternVisionTower: assign=True would detach the padded view")
-        out = super().load_state_dict(state_dict, strict=strict)
-        self.pack_()
-        return out
+    def _moved(self, fn):
+        super()._moved(fn)
+        self._pos = {}
 
     @torch.no_grad()
     def pack_(self):
@@ -181,23 +146,19 @@ class InternVisionTower(nn.Module):
         m.load_state_dict({k: v.detach().to(device=device, dtype=torch.bfloat16) for k, v in vision_model.state_dict().items()}, strict=True)
         return m
 
-    @torch.no_grad()
     def init_random_(self, seed=0):
         """Random weights in place (tools; there are no checkpoints offline): matrices N(0, 1 / fan_in), the class token and the position
         table N(0, 0.02^2), biases 0.1 N(0, 1), norm weights 1 + 0.1 N(0, 1), ls1 / ls2 0.1 (1 + 0.5 N(0, 1))"""
-        gen = torch.Generator(device=self.device).manual_seed(seed)
-        for n, p in self.named_parameters():
-            r = torch.randn(p.shape, device=p.device, generator=gen)
+        def rule(n, p, r):
             if n.endswith("position_embedding") or n.endswith("class_embedding"):
-                p.copy_(0.02 * r)
-            elif n.endswith(".ls1") or n.endswith(".ls2"):
-                p.copy_(0.1 * (1.0 + 0.5 * r))
-            elif "norm" in n and n.endswith(".weight"):
-                p.copy_(1.0 + 0.1 * r)
-            elif p.dim() == 1:
-                p.copy_(0.1 * r)
-            else:
-                p.copy_(r * (p.numel() // p.shape[0]) ** -0.5)
+                return 0.02 * r
+            if n.endswith(".ls1") or n.endswith(".ls2"):
+                return 0.1 * (1.0 + 0.5 * r)
+            if "norm" in n and n.endswith(".weight"):
+                return 1.0 + 0.1 * r
+            return 0.1 * r if p.dim() == 1 else r * (p.numel() // p.shape[0]) ** -0.5
+
+        self._init_random(seed, rule)
         return self.pack_()
 
     # ------------------------------------------------------------------ the host work of a call
@@ -236,14 +197,6 @@ class InternVisionTower(nn.Module):
             p.ws = dict(PX=torch.empty((B * p.L, self.Kp), **bf), X=torch.empty((B, S, D), **bf), NRM=torch.empty((M, D), **bf),
                         QKV=torch.empty((M, 3 * D), **bf), Q=torch.zeros((B, H, Spad, dk), **bf), K=torch.zeros((B, H, Spad, dk), **bf),
                         VT=torch.zeros((B, H, dk, Spad), **bf), ATT=torch.empty((M, D), **bf), HH=torch.empty((M, F_), **bf))
-        return p
-
-    def _plan_for(self, B, gh, gw):
-        key = (B, gh, gw)
-        p = self._plans.get(key)
-        if p is None:
-            p = self.plan(B, gh, gw)
-            self._plans = {key: p}      # keep one shape resident
         return p
 
     def _check_pixels(self, pixel_values):
@@ -325,7 +278,7 @@ class InternVLVisionPlan:
     buffers and, with graph=True, the captured graph and its stream-K workspace"""
 
 
-class InternVLVision(nn.Module):
+class InternVLVision(PackedModule):
     """Stands in for the chat model's extract_feature: forward(pixel_values [B, 3, g*P, g*P]) -> bf16 [B, (g/2)^2, H_llm].
     tower: an InternVisionTower; mlp1: the chat model's `mlp1` (LayerNorm(4 hidden), Linear, GELU, Linear; copied in bf16 to the tower's
     device) or the LLM's width (an int: parameters left uninitialised, see init_random_).  The parameter names are the chat model's
@@ -336,10 +289,12 @@ class InternVLVision(nn.Module):
     stream-K workspace of its own attached to every GEMM (ops.streamk_scope), and later calls copy the pixels in and replay.  The returned
     tensor is a copy of the result buffer."""
 
+    _eval_only = True
+
     def __init__(self, tower, mlp1, downsample_ratio=0.5, ps_version="v2", select_layer=-1, graph=False):
-        super().__init__()
         if not isinstance(tower, InternVisionTower):
             raise TypeError("InternVLVision: tower must be an InternVisionTower")
+        super().__init__(tower.device)
         if float(downsample_ratio) != 0.5:
             raise ValueError("x2i_amd InternVLVision: downsample_ratio=%r is not built (0.5 only)" % (downsample_ratio,))
         if ps_version not in ("v1", "v2"):
@@ -360,46 +315,31 @@ class InternVLVision(nn.Module):
         if Hl <= 0 or Hl % 8:
             raise ValueError("x2i_amd InternVLVision: the LLM width must be a positive multiple of 8 (got %r)" % (Hl,))
         self.llm_hidden_size, self.ln_eps = Hl, float(eps)
-        param = lambda *shape: nn.Parameter(torch.empty(shape, device=dev, dtype=torch.bfloat16), requires_grad=False)
+        param = self._param
         m = nn.Module()
-        m.add_module("0", _WB(param(4 * D), param(4 * D)))
-        m.add_module("1", _WB(param(Hl, 4 * D), param(Hl)))
-        m.add_module("3", _WB(param(Hl, Hl), param(Hl)))
+        m.add_module("0", WB(param(4 * D), param(4 * D)))
+        m.add_module("1", WB(param(Hl, 4 * D), param(Hl)))
+        m.add_module("3", WB(param(Hl, Hl), param(Hl)))
         self.mlp1 = m
         if src is not None:
             m.load_state_dict(src, strict=True)
-        self._plans = {}
         self.eval()
 
     @property
     def device(self):
         return self.vision_model.device
 
-    def train(self, mode=True):
-        if mode:
-            raise ValueError("x2i_amd InternVLVision is eval-only")
-        return super().train(False)
-
-    def _apply(self, fn, recurse=True):
+    def pack_(self):
+        """The tower's copies again; the plans (their graphs captured the tower's old copies) are dropped"""
         self._plans = {}
-        return super()._apply(fn, recurse)
-
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        if assign:
-            raise ValueError("x2i_amd InternVLVision: assign=True would detach the tower's padded view")
-        self._plans = {}
-        out = super().load_state_dict(state_dict, strict=strict)
         self.vision_model.pack_()
-        return out
+        return self
 
-    @torch.no_grad()
     def init_random_(self, seed=0):
         """Random weights in place, the tower's included (tools): InternVisionTower.init_random_'s rules"""
         self.vision_model.init_random_(seed)
-        gen = torch.Generator(device=self.device).manual_seed(seed + 1)
-        for n, p in self.mlp1.named_parameters():
-            r = torch.randn(p.shape, device=p.device, generator=gen)
-            p.copy_(1.0 + 0.1 * r if n == "0.weight" else (0.1 * r if p.dim() == 1 else r * p.shape[1] ** -0.5))
+        self._init_random(seed + 1, lambda n, p, r: 1.0 + 0.1 * r if n == "0.weight" else (0.1 * r if p.dim() == 1 else r * p.shape[1] ** -0.5),
+                          root=self.mlp1)
         self._plans = {}
         return self
 

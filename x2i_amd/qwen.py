@@ -36,6 +36,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, qwen_ops, t5_ops
+from ._packed import WB, PackedModule, config_fields, config_object
 
 _FIELDS = dict(hidden_size=3584, num_attention_heads=28, num_key_value_heads=4, intermediate_size=18944, num_hidden_layers=28, rms_norm_eps=1e-6,
                vocab_size=152064, hidden_act="silu", head_dim=None, rope_theta=1000000.0, rope_type="default", mrope_section=None,
@@ -97,15 +98,6 @@ def mask_state(attention_mask):
     return tuple(bool(v) for v in torch.stack((ok, (cnt == S).all())).tolist())
 
 
-class _WB(nn.Module):
-    def __init__(self, weight, bias=None):
-        super().__init__()
-        as_param = lambda t: t if isinstance(t, nn.Parameter) else nn.Parameter(t, requires_grad=False)
-        self.weight = as_param(weight)
-        if bias is not None:
-            self.bias = as_param(bias)
-
-
 def _rope_fields(config):
     """rope_theta / rope_type / mrope_section of a library config: `rope_parameters` (5.x) or `rope_theta` + `rope_scaling` (4.x, remote code)"""
     rp = getattr(config, "rope_parameters", None) or getattr(config, "rope_scaling", None) or {}
@@ -119,27 +111,14 @@ def _rope_fields(config):
     return out
 
 
-def _config_fields(config, kw):
-    f = dict(_FIELDS)
-    if config is not None:
-        for k in f:
-            f[k] = getattr(config, k, f[k])
-        f.update(_rope_fields(config))
-    unknown = set(kw) - set(f)
-    if unknown:
-        raise TypeError("Qwen2DecoderStack: unknown configuration fields %s" % sorted(unknown))
-    f.update(kw)
-    return f
-
-
-class Qwen2DecoderStack(nn.Module):
+class Qwen2DecoderStack(PackedModule):
     """Prefill-only drop-in for transformers' Qwen2Model / Qwen2_5_VLTextModel (the module handoff.find_decoder finds).
     forward(...) -> the hidden-state slab bf16 [B, num_layers + 1, S, H].  Decoding with a key/value cache is new_cache / prefill /
     decode_step, below; forward itself keeps none."""
 
     def __init__(self, config=None, embed_tokens=None, device="cuda", dtype=torch.bfloat16, **kw):
-        super().__init__()
-        f = _config_fields(config, kw)
+        super().__init__(device)
+        f = config_fields(_FIELDS, config, kw, "Qwen2DecoderStack", extra=_rope_fields)
         if dtype != torch.bfloat16:
             raise ValueError("x2i_amd: the HIP path computes in bf16 (fp32 statistics/accumulation)")
         if f["hidden_act"] != "silu":
@@ -161,64 +140,32 @@ class Qwen2DecoderStack(nn.Module):
         if f["mrope_section"] is not None and sum(f["mrope_section"]) != dk // 2:
             raise ValueError("x2i_amd Qwen2DecoderStack: mrope_section %r does not sum to head_dim / 2 = %d" % (f["mrope_section"], dk // 2))
         f["head_dim"] = dk
-        self.config = type("Qwen2DecoderStackConfig", (), dict(f))()
+        self.config = config_object("Qwen2DecoderStackConfig", f)
         nq, nkv = Hq * dk, Hkv * dk
-        dev = torch.device(device)
-        self._fused = {}
-        self._views = []
-
-        def param(*shape):
-            return nn.Parameter(torch.empty(shape, device=dev, dtype=dtype), requires_grad=False)
-
-        def view(name, r0, r1):
-            p = nn.Parameter(self._fused[name][r0:r1], requires_grad=False)
-            self._views.append((p, name, slice(r0, r1)))
-            return p
-
-        self.embed_tokens = _WB(embed_tokens if embed_tokens is not None else param(f["vocab_size"], D))
+        param = self._param
+        view = lambda name, r0, r1: self._view(name, slice(r0, r1))
+        self.embed_tokens = WB(embed_tokens if embed_tokens is not None else param(f["vocab_size"], D))
         layers = []
         for i in range(f["num_hidden_layers"]):
-            self._fused["%d.qkv.w" % i] = torch.empty((nq + 2 * nkv, D), device=dev, dtype=dtype)
-            self._fused["%d.qkv.b" % i] = torch.empty((nq + 2 * nkv,), device=dev, dtype=dtype)
-            self._fused["%d.gu" % i] = torch.empty((2 * F, D), device=dev, dtype=dtype)
+            self._store("%d.qkv.w" % i, nq + 2 * nkv, D)
+            self._store("%d.qkv.b" % i, nq + 2 * nkv)
+            self._store("%d.gu" % i, 2 * F, D)
             att = nn.Module()
             for nm, r0, r1 in (("q_proj", 0, nq), ("k_proj", nq, nq + nkv), ("v_proj", nq + nkv, nq + 2 * nkv)):
-                att.add_module(nm, _WB(view("%d.qkv.w" % i, r0, r1), view("%d.qkv.b" % i, r0, r1)))
-            att.add_module("o_proj", _WB(param(D, nq)))
+                att.add_module(nm, WB(view("%d.qkv.w" % i, r0, r1), view("%d.qkv.b" % i, r0, r1)))
+            att.add_module("o_proj", WB(param(D, nq)))
             mlp = nn.Module()
-            mlp.add_module("gate_proj", _WB(view("%d.gu" % i, 0, F)))
-            mlp.add_module("up_proj", _WB(view("%d.gu" % i, F, 2 * F)))
-            mlp.add_module("down_proj", _WB(param(D, F)))
+            mlp.add_module("gate_proj", WB(view("%d.gu" % i, 0, F)))
+            mlp.add_module("up_proj", WB(view("%d.gu" % i, F, 2 * F)))
+            mlp.add_module("down_proj", WB(param(D, F)))
             layer = nn.Module()
             layer.add_module("self_attn", att)
             layer.add_module("mlp", mlp)
-            layer.add_module("input_layernorm", _WB(param(D)))
-            layer.add_module("post_attention_layernorm", _WB(param(D)))
+            layer.add_module("input_layernorm", WB(param(D)))
+            layer.add_module("post_attention_layernorm", WB(param(D)))
             layers.append(layer)
         self.layers = nn.ModuleList(layers)
-        self.norm = _WB(param(D))
-        self._ws = {}
-
-    # ------------------------------------------------------------------ nn.Module plumbing
-    @property
-    def dtype(self):
-        return torch.bfloat16
-
-    @property
-    def device(self):
-        return self.norm.weight.device
-
-    def _apply(self, fn, recurse=True):
-        # the stacked q|k|v and gate|up parameters are views: move the storage, re-point the views, then the ordinary parameters
-        for k in list(self._fused):
-            new = fn(self._fused[k])
-            if new.dtype != torch.bfloat16:
-                raise ValueError("x2i_amd Qwen2DecoderStack is bf16-only")
-            self._fused[k] = new
-        for p, name, sl in self._views:
-            p.data = self._fused[name][sl]
-        self._ws = {}
-        return super()._apply(fn, recurse)
+        self.norm = WB(param(D))
 
     @classmethod
     def from_hf(cls, decoder, device=None):
@@ -232,21 +179,17 @@ class Qwen2DecoderStack(nn.Module):
         m.load_state_dict(sd, strict=True)
         return m
 
-    @torch.no_grad()
     def init_random_(self, seed=0):
         """Random weights in place on the device (tools and smoke runs; there are no checkpoints offline): linears N(0, 1 / fan_in), biases
         0.1 N(0, 1), norms 1 + 0.1 N(0, 1), token table N(0, 1)."""
-        gen = torch.Generator(device=self.device).manual_seed(seed)
-        for n, p in self.named_parameters():
-            r = torch.randn(p.shape, device=p.device, generator=gen)
+        def rule(n, p, r):
             if n.endswith("norm.weight") or n.endswith("layernorm.weight"):
-                p.copy_(1.0 + 0.1 * r)
-            elif p.dim() == 1:
-                p.copy_(0.1 * r)
-            elif n.startswith("embed_tokens"):
-                p.copy_(r)
-            else:
-                p.copy_(r * p.shape[1] ** -0.5)
+                return 1.0 + 0.1 * r
+            if p.dim() == 1:
+                return 0.1 * r
+            return r if n.startswith("embed_tokens") else r * p.shape[1] ** -0.5
+
+        self._init_random(seed, rule)
         return self
 
     # ------------------------------------------------------------------ workspace

@@ -33,7 +33,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, qwen_ops, t5_ops, vit_ops
-from .qwen import _WB
+from ._packed import WB, PackedModule, config_fields, config_object
 
 _FIELDS = dict(depth=32, hidden_size=1280, hidden_act="silu", intermediate_size=3420, num_heads=16, in_channels=3, patch_size=14,
                spatial_merge_size=2, temporal_patch_size=2, window_size=112, out_hidden_size=3584, fullatt_block_indexes=(7, 15, 23, 31))
@@ -93,19 +93,12 @@ class VisionPlan:
     """Everything of a call that depends on grid_thw alone (Qwen2_5VisionTower.plan)"""
 
 
-class Qwen2_5VisionTower(nn.Module):
+class Qwen2_5VisionTower(PackedModule):
     """Drop-in for transformers' Qwen2_5_VisionTransformerPretrainedModel.  forward(pixel_rows, grid_thw) -> BaseModelOutputWithPooling."""
 
     def __init__(self, config=None, device="cuda", dtype=torch.bfloat16, **kw):
-        super().__init__()
-        f = dict(_FIELDS)
-        if config is not None:
-            for k in f:
-                f[k] = getattr(config, k, f[k])
-        unknown = set(kw) - set(f)
-        if unknown:
-            raise TypeError("Qwen2_5VisionTower: unknown configuration fields %s" % sorted(unknown))
-        f.update(kw)
+        super().__init__(device)
+        f = config_fields(_FIELDS, config, kw, "Qwen2_5VisionTower")
         if dtype != torch.bfloat16:
             raise ValueError("x2i_amd: the HIP path computes in bf16 (fp32 statistics/accumulation)")
         if f["hidden_act"] != "silu":
@@ -119,76 +112,41 @@ class Qwen2_5VisionTower(nn.Module):
             raise ValueError("x2i_amd Qwen2_5VisionTower: window_size must hold at least one merge unit")
         f["fullatt_block_indexes"] = tuple(f["fullatt_block_indexes"])
         f["head_dim"] = D // H
-        self.config = type("Qwen2_5VisionTowerConfig", (), dict(f))()
+        self.config = config_object("Qwen2_5VisionTowerConfig", f)
         self.spatial_merge_size = f["spatial_merge_size"]          # (the surrounding model reads it)
         self.spatial_merge_unit = unit = f["spatial_merge_size"] ** 2
         self.patch_dim = Kpe = f["in_channels"] * f["temporal_patch_size"] * f["patch_size"] ** 2
         self.Fp, self.Kp = Fp, Kp = vit_ops.pad64(F), vit_ops.pad64(Kpe)
-        dev = torch.device(device)
-        self._fused = {}
-        self._views = []
-
-        def param(*shape):
-            return nn.Parameter(torch.empty(shape, device=dev, dtype=dtype), requires_grad=False)
-
-        def view(name, index, shape=None):
-            t = self._fused[name][index]
-            p = nn.Parameter(t if shape is None else t.view(shape), requires_grad=False)
-            self._views.append((p, name, index, shape))
-            return p
-
+        param, view = self._param, self._view
         cols = lambda n: (slice(None), slice(0, n))
-        self._fused["pe"] = torch.zeros((D, Kp), device=dev, dtype=dtype)
+        self._store("pe", D, Kp, zero=True)
         self.patch_embed = nn.Module()
-        self.patch_embed.add_module("proj", _WB(view("pe", cols(Kpe), (D, f["in_channels"], f["temporal_patch_size"], f["patch_size"], f["patch_size"]))))
+        self.patch_embed.add_module("proj", WB(view("pe", cols(Kpe), (D, f["in_channels"], f["temporal_patch_size"], f["patch_size"], f["patch_size"]))))
         blocks = []
         for i in range(L):
-            self._fused["%d.gu.w" % i] = torch.zeros((2 * Fp, D), device=dev, dtype=dtype)
-            self._fused["%d.gu.b" % i] = torch.zeros((2 * Fp,), device=dev, dtype=dtype)
-            self._fused["%d.down" % i] = torch.zeros((D, Fp), device=dev, dtype=dtype)
+            self._store("%d.gu.w" % i, 2 * Fp, D, zero=True)
+            self._store("%d.gu.b" % i, 2 * Fp, zero=True)
+            self._store("%d.down" % i, D, Fp, zero=True)
             att = nn.Module()
-            att.add_module("qkv", _WB(param(3 * D, D), param(3 * D)))
-            att.add_module("proj", _WB(param(D, D), param(D)))
+            att.add_module("qkv", WB(param(3 * D, D), param(3 * D)))
+            att.add_module("proj", WB(param(D, D), param(D)))
             mlp = nn.Module()
-            mlp.add_module("gate_proj", _WB(view("%d.gu.w" % i, slice(0, F)), view("%d.gu.b" % i, slice(0, F))))
-            mlp.add_module("up_proj", _WB(view("%d.gu.w" % i, slice(Fp, Fp + F)), view("%d.gu.b" % i, slice(Fp, Fp + F))))
-            mlp.add_module("down_proj", _WB(view("%d.down" % i, cols(F)), param(D)))
+            mlp.add_module("gate_proj", WB(view("%d.gu.w" % i, slice(0, F)), view("%d.gu.b" % i, slice(0, F))))
+            mlp.add_module("up_proj", WB(view("%d.gu.w" % i, slice(Fp, Fp + F)), view("%d.gu.b" % i, slice(Fp, Fp + F))))
+            mlp.add_module("down_proj", WB(view("%d.down" % i, cols(F)), param(D)))
             blk = nn.Module()
-            blk.add_module("norm1", _WB(param(D)))
-            blk.add_module("norm2", _WB(param(D)))
+            blk.add_module("norm1", WB(param(D)))
+            blk.add_module("norm2", WB(param(D)))
             blk.add_module("attn", att)
             blk.add_module("mlp", mlp)
             blocks.append(blk)
         self.blocks = nn.ModuleList(blocks)
         self.merger = nn.Module()
-        self.merger.add_module("ln_q", _WB(param(D)))
+        self.merger.add_module("ln_q", WB(param(D)))
         mm = nn.Module()
-        mm.add_module("0", _WB(param(unit * D, unit * D), param(unit * D)))
-        mm.add_module("2", _WB(param(f["out_hidden_size"], unit * D), param(f["out_hidden_size"])))
+        mm.add_module("0", WB(param(unit * D, unit * D), param(unit * D)))
+        mm.add_module("2", WB(param(f["out_hidden_size"], unit * D), param(f["out_hidden_size"])))
         self.merger.add_module("mlp", mm)
-        self._plans = {}
-
-    # ------------------------------------------------------------------ nn.Module plumbing
-    @property
-    def dtype(self):
-        return torch.bfloat16
-
-    @property
-    def device(self):
-        return self.merger.ln_q.weight.device
-
-    def _apply(self, fn, recurse=True):
-        # the padded parameters are views: move the storage, re-point the views, then the ordinary parameters
-        for k in list(self._fused):
-            new = fn(self._fused[k])
-            if new.dtype != torch.bfloat16:
-                raise ValueError("x2i_amd Qwen2_5VisionTower is bf16-only")
-            self._fused[k] = new
-        for p, name, index, shape in self._views:
-            t = self._fused[name][index]
-            p.data = t if shape is None else t.view(shape)
-        self._plans = {}
-        return super()._apply(fn, recurse)
 
     @classmethod
     def from_hf(cls, visual, device=None):
@@ -199,18 +157,14 @@ class Qwen2_5VisionTower(nn.Module):
         m.load_state_dict({k: v.detach().to(device=device, dtype=torch.bfloat16) for k, v in visual.state_dict().items()}, strict=True)
         return m
 
-    @torch.no_grad()
     def init_random_(self, seed=0):
         """Random weights in place (tools; there are no checkpoints offline): matrices N(0, 1 / fan_in), biases 0.1 N(0, 1), norms 1 + 0.1 N(0, 1)"""
-        gen = torch.Generator(device=self.device).manual_seed(seed)
-        for n, p in self.named_parameters():
-            r = torch.randn(p.shape, device=p.device, generator=gen)
+        def rule(n, p, r):
             if "norm" in n or "ln_q" in n:
-                p.copy_(1.0 + 0.1 * r)
-            elif p.dim() == 1:
-                p.copy_(0.1 * r)
-            else:
-                p.copy_(r * (p.numel() // p.shape[0]) ** -0.5)
+                return 1.0 + 0.1 * r
+            return 0.1 * r if p.dim() == 1 else r * (p.numel() // p.shape[0]) ** -0.5
+
+        self._init_random(seed, rule)
         return self
 
     # ------------------------------------------------------------------ plan
@@ -258,14 +212,6 @@ class Qwen2_5VisionTower(nn.Module):
                         M2=torch.empty((S // unit, c.out_hidden_size), **bf))
         return p
 
-    def _plan_for(self, grid_thw):
-        grid = tuple(tuple(int(v) for v in g) for g in grid_thw.tolist())     # the one host read
-        p = self._plans.get(grid)
-        if p is None:
-            p = self.plan(grid)
-            self._plans = {grid: p}     # keep one grid resident
-        return p
-
     # ------------------------------------------------------------------ forward
     def _block(self, i, plan, x, out):
         """block i on the rows x [S, hidden] (window order) -> out (which may be x): nine launches"""
@@ -294,7 +240,7 @@ class Qwen2_5VisionTower(nn.Module):
         if plan is None:
             if grid_thw is None:
                 raise ValueError("Qwen2_5VisionTower: pass grid_thw or a plan")
-            plan = self._plan_for(grid_thw)
+            plan = self._plan_for(tuple(tuple(int(v) for v in g) for g in grid_thw.tolist()))     # the one host read
         c = self.config
         D, L, unit = c.hidden_size, len(self.blocks), self.spatial_merge_unit
         S = plan.S

@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, resampler_ops
-from .qwen import _WB
+from ._packed import WB, PackedModule
 
 MAX_SIDE = 70          # the reference's max_size: the table is built once for 70 x 70 and never grown
 CHUNK = 16             # frames per pass over the workspaces
@@ -64,11 +64,13 @@ class ResamplerPlan:
     """Everything of a call that depends on (tgt_sizes, L) alone (Resampler.plan)"""
 
 
-class Resampler(nn.Module):
+class Resampler(PackedModule):
     """Drop-in for MiniCPM-o's `model.resampler`.  forward(x [B, L, kv_dim], tgt_sizes [B, 2]) -> bf16 [B, NQ, embed_dim]."""
 
+    _copies = "_projT"
+
     def __init__(self, num_queries=64, embed_dim=3584, num_heads=None, kv_dim=1152, eps=1e-6, device="cuda", dtype=torch.bfloat16):
-        super().__init__()
+        super().__init__(device)
         if dtype != torch.bfloat16:
             raise ValueError("x2i_amd: the HIP path computes in bf16 (fp32 statistics/accumulation)")
         num_heads = embed_dim // DK if num_heads is None else num_heads
@@ -82,51 +84,30 @@ class Resampler(nn.Module):
                              "(an Identity kv_proj is not built; got %r)" % (kv_dim,))
         self.num_queries, self.embed_dim, self.num_heads, self.kv_dim, self.eps = num_queries, embed_dim, num_heads, kv_dim, eps
         self.max_size = (MAX_SIDE, MAX_SIDE)
-        dev, D = torch.device(device), embed_dim
-
-        def param(*shape):
-            return nn.Parameter(torch.empty(shape, device=dev, dtype=dtype), requires_grad=False)
-
+        dev, D, param = torch.device(device), embed_dim, self._param
         self.query = param(num_queries, D)
-        self.kv_proj = _WB(param(D, kv_dim))
+        self.kv_proj = WB(param(D, kv_dim))
         self.attn = nn.Module()
         self.attn.in_proj_weight = param(3 * D, D)
         self.attn.in_proj_bias = param(3 * D)
-        self.attn.add_module("out_proj", _WB(param(D, D), param(D)))
-        self.ln_q = _WB(param(D), param(D))
-        self.ln_kv = _WB(param(D), param(D))
-        self.ln_post = _WB(param(D), param(D))
+        self.attn.add_module("out_proj", WB(param(D, D), param(D)))
+        self.ln_q = WB(param(D), param(D))
+        self.ln_kv = WB(param(D), param(D))
+        self.ln_post = WB(param(D), param(D))
         self.proj = param(D, D)
         # not parameters: the reference keeps its table in a non-persistent buffer, so a state dict does not carry it
         self._pos = sincos_table(D).to(torch.bfloat16).reshape(MAX_SIDE * MAX_SIDE, D).to(dev)
         self._projT = None
         self._Q = None
-        self._plans = {}
-
-    # ------------------------------------------------------------------ nn.Module plumbing
-    @property
-    def dtype(self):
-        return torch.bfloat16
 
     @property
     def device(self):
         return self.query.device
 
-    def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)
-        if self.query.dtype != torch.bfloat16:
-            raise ValueError("x2i_amd Resampler is bf16-only")
-        self._pos = fn(self._pos)
-        self._plans = {}
+    def _moved(self, fn):
+        super()._moved(fn)
+        self._pos = self._bf16(fn(self._pos))     # no storage is fused here: the table is what refuses another dtype, before a parameter moves
         self._Q = None
-        if self._projT is not None:
-            self.pack_()
-        return out
-
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        out = super().load_state_dict(state_dict, strict=strict, assign=assign)
-        self.pack_()
-        return out
 
     @torch.no_grad()
     def pack_(self):
@@ -145,23 +126,19 @@ class Resampler(nn.Module):
         m.load_state_dict({k: v.detach().to(device=device, dtype=torch.bfloat16) for k, v in module.state_dict().items()}, strict=True)
         return m
 
-    @torch.no_grad()
     def init_random_(self, seed=0):
         """Random weights in place (tools; there are no checkpoints offline): matrices N(0, 1 / fan_in), the queries N(0, 1), biases
         0.1 N(0, 1), norm weights 1 + 0.1 N(0, 1)"""
-        gen = torch.Generator(device=self.device).manual_seed(seed)
-        for n, p in self.named_parameters():
-            r = torch.randn(p.shape, device=p.device, generator=gen)
+        def rule(n, p, r):
             if n.startswith("ln_") and n.endswith(".weight"):
-                p.copy_(1.0 + 0.1 * r)
-            elif n == "query":
-                p.copy_(r)
-            elif p.dim() == 1:
-                p.copy_(0.1 * r)
-            elif n == "proj":
-                p.copy_(r * p.shape[0] ** -0.5)
-            else:
-                p.copy_(r * p.shape[1] ** -0.5)
+                return 1.0 + 0.1 * r
+            if n == "query":
+                return r
+            if p.dim() == 1:
+                return 0.1 * r
+            return r * p.shape[0 if n == "proj" else 1] ** -0.5
+
+        self._init_random(seed, rule)
         return self.pack_()
 
     # ------------------------------------------------------------------ the cached queries
@@ -204,14 +181,6 @@ class Resampler(nn.Module):
             p.ws = dict(X0=torch.empty((M, D), **bf), XV=torch.empty((M, D), **bf), XK=torch.empty((M, D), **bf), KV=torch.empty((M, 2 * D), **bf),
                         K=torch.zeros((Bc, H, Lpad, DK), **bf), VT=torch.zeros((Bc, H, DK, Lpad), **bf), ATT=torch.empty((Bc * NQ, D), **bf),
                         Y=torch.empty((Bc * NQ, D), **bf), Z=torch.empty((Bc * NQ, D), **bf))
-        return p
-
-    def _plan_for(self, sizes, L):
-        key = (sizes, L)
-        p = self._plans.get(key)
-        if p is None:
-            p = self.plan(sizes, L)
-            self._plans = {key: p}      # keep one shape resident
         return p
 
     # ------------------------------------------------------------------ forward

@@ -39,7 +39,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, siglip_ops, vit_ops
-from .qwen import _WB
+from ._packed import WB, PackedModule, config_fields, config_object
 
 _FIELDS = dict(hidden_size=1152, num_attention_heads=16, num_hidden_layers=27, intermediate_size=4304, image_size=980, patch_size=14,
                layer_norm_eps=1e-6, hidden_act="gelu_pytorch_tanh", num_channels=3)
@@ -71,20 +71,15 @@ class SiglipPlan:
     """Everything of a call that depends on (tgt_sizes, L) alone (SiglipVisionTower.plan)"""
 
 
-class SiglipVisionTower(nn.Module):
+class SiglipVisionTower(PackedModule):
     """Drop-in for the SigLIP tower behind MiniCPM-o's `model.vpm`.  forward(pixel_values, patch_attention_mask, tgt_sizes) ->
     BaseModelOutputWithPooling(last_hidden_state bf16 [B, L, hidden], pooler_output None)."""
 
+    _copies = "_packed"
+
     def __init__(self, config=None, device="cuda", dtype=torch.bfloat16, **kw):
-        super().__init__()
-        f = dict(_FIELDS)
-        if config is not None:
-            for k in f:
-                f[k] = getattr(config, k, f[k])
-        unknown = set(kw) - set(f)
-        if unknown:
-            raise TypeError("SiglipVisionTower: unknown configuration fields %s" % sorted(unknown))
-        f.update(kw)
+        super().__init__(device)
+        f = config_fields(_FIELDS, config, kw, "SiglipVisionTower")
         if dtype != torch.bfloat16:
             raise ValueError("x2i_amd: the HIP path computes in bf16 (fp32 statistics/accumulation)")
         if f["hidden_act"] != "gelu_pytorch_tanh":
@@ -98,83 +93,38 @@ class SiglipVisionTower(nn.Module):
         if f["num_channels"] != 3 or not 1 <= P <= 32 or f["image_size"] // P < 1:
             raise ValueError("x2i_amd SiglipVisionTower: need 3 channels, patch_size in 1..32 and image_size >= patch_size")
         f["head_dim"] = dk = D // H
-        self.config = type("SiglipVisionTowerConfig", (), dict(f))()
+        self.config = config_object("SiglipVisionTowerConfig", f)
         self.side = side = f["image_size"] // P         # patches per side of the position table
         self.patch_dim = Kpe = 3 * P * P
         self.dkp = padded_head_width(dk)
         self.Fp, self.Kp = Fp, Kp = siglip_ops.pad64(F), siglip_ops.pad64(Kpe)
-        dev = torch.device(device)
-        self._fused = {}
-        self._views = []
         self._packed = None
-        self._plans = {}
-
-        def param(*shape):
-            return nn.Parameter(torch.empty(shape, device=dev, dtype=dtype), requires_grad=False)
-
-        def view(name, index, shape=None):
-            t = self._fused[name][index]
-            p = nn.Parameter(t if shape is None else t.view(shape), requires_grad=False)
-            self._views.append((p, name, index, shape))
-            return p
-
+        param, view = self._param, self._view
         cols = lambda n: (slice(None), slice(0, n))
-        self._fused["pe"] = torch.zeros((D, Kp), device=dev, dtype=dtype)
+        self._store("pe", D, Kp, zero=True)
         self.embeddings = nn.Module()
-        self.embeddings.add_module("patch_embedding", _WB(view("pe", cols(Kpe), (D, 3, P, P)), param(D)))
-        self.embeddings.add_module("position_embedding", _WB(param(side * side, D)))
+        self.embeddings.add_module("patch_embedding", WB(view("pe", cols(Kpe), (D, 3, P, P)), param(D)))
+        self.embeddings.add_module("position_embedding", WB(param(side * side, D)))
         layers = []
         for i in range(NL):
-            self._fused["%d.fc1.w" % i] = torch.zeros((Fp, D), device=dev, dtype=dtype)
-            self._fused["%d.fc1.b" % i] = torch.zeros((Fp,), device=dev, dtype=dtype)
-            self._fused["%d.fc2" % i] = torch.zeros((D, Fp), device=dev, dtype=dtype)
+            self._store("%d.fc1.w" % i, Fp, D, zero=True)
+            self._store("%d.fc1.b" % i, Fp, zero=True)
+            self._store("%d.fc2" % i, D, Fp, zero=True)
             att = nn.Module()
             for nm in ("q_proj", "k_proj", "v_proj", "out_proj"):
-                att.add_module(nm, _WB(param(D, D), param(D)))
+                att.add_module(nm, WB(param(D, D), param(D)))
             mlp = nn.Module()
-            mlp.add_module("fc1", _WB(view("%d.fc1.w" % i, slice(0, F)), view("%d.fc1.b" % i, slice(0, F))))
-            mlp.add_module("fc2", _WB(view("%d.fc2" % i, cols(F)), param(D)))
+            mlp.add_module("fc1", WB(view("%d.fc1.w" % i, slice(0, F)), view("%d.fc1.b" % i, slice(0, F))))
+            mlp.add_module("fc2", WB(view("%d.fc2" % i, cols(F)), param(D)))
             layer = nn.Module()
             layer.add_module("self_attn", att)
-            layer.add_module("layer_norm1", _WB(param(D), param(D)))
+            layer.add_module("layer_norm1", WB(param(D), param(D)))
             layer.add_module("mlp", mlp)
-            layer.add_module("layer_norm2", _WB(param(D), param(D)))
+            layer.add_module("layer_norm2", WB(param(D), param(D)))
             layers.append(layer)
         self.encoder = nn.Module()
         self.encoder.add_module("layers", nn.ModuleList(layers))
-        self.post_layernorm = _WB(param(D), param(D))
-
-    # ------------------------------------------------------------------ nn.Module plumbing
-    @property
-    def dtype(self):
-        return torch.bfloat16
-
-    @property
-    def device(self):
-        return self.post_layernorm.weight.device
-
-    def _apply(self, fn, recurse=True):
-        # the padded parameters are views: move the storage, re-point the views, then the ordinary parameters; the head-padded copies are made again
-        for k in list(self._fused):
-            new = fn(self._fused[k])
-            if new.dtype != torch.bfloat16:
-                raise ValueError("x2i_amd SiglipVisionTower is bf16-only")
-            self._fused[k] = new
-        for p, name, index, shape in self._views:
-            t = self._fused[name][index]
-            p.data = t if shape is None else t.view(shape)
-        self._plans = {}
-        out = super()._apply(fn, recurse)
-        if self._packed is not None:
-            self.pack_()
-        return out
-
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        if assign:
-            raise ValueError("x2i_amd SiglipVisionTower: assign=True would detach the padded views")
-        out = super().load_state_dict(state_dict, strict=strict)
-        self.pack_()
-        return out
+        self.post_layernorm = WB(param(D), param(D))
 
     @torch.no_grad()
     def pack_(self):
@@ -204,21 +154,17 @@ class SiglipVisionTower(nn.Module):
         m.load_state_dict({k: v.detach().to(device=device, dtype=torch.bfloat16) for k, v in vpm.state_dict().items()}, strict=True)
         return m
 
-    @torch.no_grad()
     def init_random_(self, seed=0):
         """Random weights in place (tools; there are no checkpoints offline): matrices N(0, 1 / fan_in), the position table N(0, 0.02^2),
         biases 0.1 N(0, 1), norm weights 1 + 0.1 N(0, 1)"""
-        gen = torch.Generator(device=self.device).manual_seed(seed)
-        for n, p in self.named_parameters():
-            r = torch.randn(p.shape, device=p.device, generator=gen)
+        def rule(n, p, r):
             if n.endswith("position_embedding.weight"):
-                p.copy_(0.02 * r)
-            elif "norm" in n and n.endswith(".weight"):
-                p.copy_(1.0 + 0.1 * r)
-            elif p.dim() == 1:
-                p.copy_(0.1 * r)
-            else:
-                p.copy_(r * (p.numel() // p.shape[0]) ** -0.5)
+                return 0.02 * r
+            if "norm" in n and n.endswith(".weight"):
+                return 1.0 + 0.1 * r
+            return 0.1 * r if p.dim() == 1 else r * (p.numel() // p.shape[0]) ** -0.5
+
+        self._init_random(seed, rule)
         return self.pack_()
 
     # ------------------------------------------------------------------ plan
@@ -256,14 +202,6 @@ class SiglipVisionTower(nn.Module):
             p.ws = dict(PX=torch.empty((M, self.Kp), **bf), X=torch.empty((M, D), **bf), NRM=torch.empty((M, D), **bf),
                         QKV=torch.empty((M, 3 * H * dkp), **bf), Q=torch.zeros((B, H, Spad, dks), **bf), K=torch.zeros((B, H, Spad, dks), **bf),
                         VT=torch.zeros((B, H, dks, Spad), **bf), ATT=torch.empty((M, H * dkp), **bf), HH=torch.empty((M, self.Fp), **bf))
-        return p
-
-    def _plan_for(self, sizes, L):
-        key = (len(sizes), L, sizes)
-        p = self._plans.get(key)
-        if p is None:
-            p = self.plan(sizes, L)
-            self._plans = {key: p}      # keep one shape resident
         return p
 
     # ------------------------------------------------------------------ forward

@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, t5_ops
+from ._packed import WB, PackedModule, config_fields, config_object
 
 _FIELDS = dict(d_model=512, d_kv=64, num_heads=8, d_ff=2048, num_layers=6, layer_norm_epsilon=1e-6, relative_attention_num_buckets=32,
                relative_attention_max_distance=128, feed_forward_proj="gated-gelu", dense_act_fn="gelu_new", vocab_size=32128, is_decoder=False)
@@ -64,30 +65,12 @@ class T5Output(tuple):
         return self[0]
 
 
-class _W(nn.Module):
-    def __init__(self, weight):
-        super().__init__()
-        self.weight = weight if isinstance(weight, nn.Parameter) else nn.Parameter(weight, requires_grad=False)
-
-
-def _config_fields(config, kw):
-    f = dict(_FIELDS)
-    if config is not None:
-        for k in f:
-            f[k] = getattr(config, k, f[k])
-    unknown = set(kw) - set(f)
-    if unknown:
-        raise TypeError("T5Stack: unknown configuration fields %s" % sorted(unknown))
-    f.update(kw)
-    return f
-
-
-class T5Stack(nn.Module):
+class T5Stack(PackedModule):
     """Encoder-only drop-in for transformers.models.t5.modeling_t5.T5Stack (gated-GELU feed-forward, relative attention bias in block 0)."""
 
     def __init__(self, config=None, embed_tokens=None, device="cuda", dtype=torch.bfloat16, **kw):
-        super().__init__()
-        f = _config_fields(config, kw)
+        super().__init__(device)
+        f = config_fields(_FIELDS, config, kw, "T5Stack")
         if f["is_decoder"]:
             raise ValueError("x2i_amd T5Stack: only the encoder is built (is_decoder=True)")
         if f["feed_forward_proj"] not in ("gated-gelu",):
@@ -102,88 +85,58 @@ class T5Stack(nn.Module):
             raise ValueError("x2i_amd T5Stack: relative_attention_max_distance must be in 1..2047 and relative_attention_num_buckets >= 4")
         if dtype != torch.bfloat16:
             raise ValueError("x2i_amd: the HIP path computes in bf16 (fp32 statistics/accumulation)")
-        self.config = type("T5StackConfig", (), dict(f))()
+        self.config = config_object("T5StackConfig", f)
         D, dk, H, F = f["d_model"], f["d_kv"], f["num_heads"], f["d_ff"]
         inner = H * dk
-        dev = torch.device(device)
-        self._fused = {}
-        self._views = []
-
-        def param(*shape):
-            return nn.Parameter(torch.empty(shape, device=dev, dtype=dtype), requires_grad=False)
-
-        def view(name, r0, r1):
-            p = nn.Parameter(self._fused[name][r0:r1], requires_grad=False)
-            self._views.append((p, name, slice(r0, r1)))
-            return _W(p)
-
-        self.embed_tokens = _W(embed_tokens if embed_tokens is not None else param(f["vocab_size"], D))
+        param = self._param
+        view = lambda name, r0, r1: WB(self._view(name, slice(r0, r1)))
+        self.embed_tokens = WB(embed_tokens if embed_tokens is not None else param(f["vocab_size"], D))
         blocks = []
         for i in range(f["num_layers"]):
-            self._fused["%d.qkv" % i] = torch.empty((3 * inner, D), device=dev, dtype=dtype)
-            self._fused["%d.wi" % i] = torch.empty((2 * F, D), device=dev, dtype=dtype)
+            self._store("%d.qkv" % i, 3 * inner, D)
+            self._store("%d.wi" % i, 2 * F, D)
             att = nn.Module()
             for j, nm in enumerate("qkv"):
                 att.add_module(nm, view("%d.qkv" % i, j * inner, (j + 1) * inner))
-            att.add_module("o", _W(param(D, inner)))
+            att.add_module("o", WB(param(D, inner)))
             if i == 0:
-                att.add_module("relative_attention_bias", _W(param(f["relative_attention_num_buckets"], H)))
+                att.add_module("relative_attention_bias", WB(param(f["relative_attention_num_buckets"], H)))
             l0 = nn.Module()
             l0.add_module("SelfAttention", att)
-            l0.add_module("layer_norm", _W(param(D)))
+            l0.add_module("layer_norm", WB(param(D)))
             ff = nn.Module()
             ff.add_module("wi_0", view("%d.wi" % i, 0, F))
             ff.add_module("wi_1", view("%d.wi" % i, F, 2 * F))
-            ff.add_module("wo", _W(param(D, F)))
+            ff.add_module("wo", WB(param(D, F)))
             l1 = nn.Module()
             l1.add_module("DenseReluDense", ff)
-            l1.add_module("layer_norm", _W(param(D)))
+            l1.add_module("layer_norm", WB(param(D)))
             blk = nn.Module()
             blk.add_module("layer", nn.ModuleList([l0, l1]))
             blocks.append(blk)
         self.block = nn.ModuleList(blocks)
-        self.final_layer_norm = _W(param(D))
+        self.final_layer_norm = WB(param(D))
         R = f["relative_attention_max_distance"]
         # the bucket of every key offset -R..R, evaluated once on the CPU (where the float64 references evaluate the library's expression too)
         self._buckets_cpu = relative_position_bucket(torch.arange(-R, R + 1, dtype=torch.long), f["relative_attention_num_buckets"], R)
         self._buckets = None
         self._table = None
-        self._ws = {}
 
-    # ------------------------------------------------------------------ nn.Module plumbing
-    @property
-    def dtype(self):
-        return torch.bfloat16
+    def _moved(self, fn):
+        super()._moved(fn)
+        self._table, self._buckets = None, None
 
-    @property
-    def device(self):
-        return self.final_layer_norm.weight.device
-
-    def _apply(self, fn, recurse=True):
-        # the stacked q|k|v and wi_0|wi_1 parameters are views: move the storage, re-point the views, then the ordinary parameters
-        for k in list(self._fused):
-            new = fn(self._fused[k])
-            if new.dtype != torch.bfloat16:
-                raise ValueError("x2i_amd T5Stack is bf16-only")
-            self._fused[k] = new
-        for p, name, sl in self._views:
-            p.data = self._fused[name][sl]
-        self._ws, self._table, self._buckets = {}, None, None
-        return super()._apply(fn, recurse)
-
-    @torch.no_grad()
     def init_random_(self, seed=0):
         """Random weights in place on the device (tools and smoke runs; there are no checkpoints offline), at the library's scales: linears
         N(0, 1 / fan_in), q a further d_kv^-1/2 (the scores carry no softmax scale), norms 1 + 0.1 N(0, 1), token table and bias N(0, 1)."""
-        gen = torch.Generator(device=self.device).manual_seed(seed)
-        for n, p in self.named_parameters():
-            r = torch.randn(p.shape, device=p.device, generator=gen)
+        def rule(n, p, r):
             if p.dim() == 1:
-                p.copy_(1.0 + 0.1 * r)
-            elif n.endswith("relative_attention_bias.weight") or n.startswith("embed_tokens"):
-                p.copy_(r)
-            else:
-                p.copy_(r * (p.shape[1] ** -0.5 * (self.config.d_kv ** -0.5 if n.endswith("SelfAttention.q.weight") else 1.0)))
+                return 1.0 + 0.1 * r
+            if n.endswith("relative_attention_bias.weight") or n.startswith("embed_tokens"):
+                return r
+            return r * (p.shape[1] ** -0.5 * (self.config.d_kv ** -0.5 if n.endswith("SelfAttention.q.weight") else 1.0))
+
+        self._init_random(seed, rule)
         return self
 
     # ------------------------------------------------------------------ bias table and workspace
@@ -255,8 +208,8 @@ class T5EncoderModel(nn.Module):
 
     def __init__(self, config=None, device="cuda", dtype=torch.bfloat16, **kw):
         super().__init__()
-        f = _config_fields(config, kw)
-        self.shared = _W(torch.empty((f["vocab_size"], f["d_model"]), device=torch.device(device), dtype=dtype))
+        f = config_fields(_FIELDS, config, kw, "T5Stack")
+        self.shared = WB(torch.empty((f["vocab_size"], f["d_model"]), device=torch.device(device), dtype=dtype))
         self.encoder = T5Stack(config, embed_tokens=self.shared.weight, device=device, dtype=dtype, **kw)   # tied, as the library ties them
         self.config = self.encoder.config
 

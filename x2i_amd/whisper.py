@@ -43,7 +43,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, siglip_ops, vit_ops, whisper_ops
-from .qwen import _WB
+from ._packed import WB, PackedModule, config_fields, config_object
 
 _FIELDS = dict(d_model=1024, encoder_attention_heads=16, encoder_ffn_dim=4096, encoder_layers=24, max_source_positions=1500, num_mel_bins=80,
                activation_function="gelu", embed_dim=3584, pool_step=2, layer_norm_eps=1e-5)
@@ -73,20 +73,16 @@ class WhisperPlan:
     """Everything of a call that depends on (feature_lens, T, chunk_frames) alone (WhisperAudioTower.plan)"""
 
 
-class WhisperAudioTower(nn.Module):
+class WhisperAudioTower(PackedModule):
     """Drop-in for get_audio_embedding's tensor work.  forward(mel [B, 80, T], feature_lens) -> (bf16 [B, n_max, E], [n_b]): sample b's
     audio embedding is rows < n_b of out[b].  Eval only."""
 
+    _eval_only = True
+    _copies = "_conv2"
+
     def __init__(self, config=None, device="cuda", dtype=torch.bfloat16, **kw):
-        super().__init__()
-        f = dict(_FIELDS)
-        if config is not None:
-            for k in f:
-                f[k] = getattr(config, k, f[k])
-        unknown = set(kw) - set(f)
-        if unknown:
-            raise TypeError("WhisperAudioTower: unknown configuration fields %s" % sorted(unknown))
-        f.update(kw)
+        super().__init__(device)
+        f = config_fields(_FIELDS, config, kw, "WhisperAudioTower")
         if dtype != torch.bfloat16:
             raise ValueError("x2i_amd: the HIP path computes in bf16 (fp32 statistics/accumulation)")
         if f["activation_function"] != "gelu":
@@ -100,88 +96,38 @@ class WhisperAudioTower(nn.Module):
         if not 1 <= k <= 8:
             raise ValueError("x2i_amd WhisperAudioTower: pool_step must be in 1..8 (got %r)" % (k,))
         f["head_dim"] = 64
-        self.config = type("WhisperAudioTowerConfig", (), dict(f))()
+        self.config = config_object("WhisperAudioTowerConfig", f)
         self.Kp = Kp = siglip_ops.pad64(3 * Cin)
-        dev = torch.device(device)
-        self._fused = {}
-        self._views = []
         self._conv2 = None
-        self._plans = {}
-
-        def param(*shape):
-            return nn.Parameter(torch.empty(shape, device=dev, dtype=dtype), requires_grad=False)
-
-        def view(name, index, shape=None):
-            t = self._fused[name][index]
-            p = nn.Parameter(t if shape is None else t.view(shape), requires_grad=False)
-            self._views.append((p, name, index, shape))
-            return p
-
-        self._fused["c1"] = torch.zeros((D, Kp), device=dev, dtype=dtype)
+        param, view = self._param, self._view
+        self._store("c1", D, Kp, zero=True)
         apm = nn.Module()
-        apm.add_module("conv1", _WB(view("c1", (slice(None), slice(0, 3 * Cin)), (D, Cin, 3)), param(D)))
-        apm.add_module("conv2", _WB(param(D, D, 3), param(D)))
-        apm.add_module("embed_positions", _WB(param(NP, D)))
+        apm.add_module("conv1", WB(view("c1", (slice(None), slice(0, 3 * Cin)), (D, Cin, 3)), param(D)))
+        apm.add_module("conv2", WB(param(D, D, 3), param(D)))
+        apm.add_module("embed_positions", WB(param(NP, D)))
         layers = []
         for i in range(NL):
-            self._fused["%d.qkv.w" % i] = torch.zeros((3 * D, D), device=dev, dtype=dtype)
-            self._fused["%d.qkv.b" % i] = torch.zeros((3 * D,), device=dev, dtype=dtype)
+            self._store("%d.qkv.w" % i, 3 * D, D, zero=True)
+            self._store("%d.qkv.b" % i, 3 * D, zero=True)
             att = nn.Module()
             for j, nm in enumerate(("q_proj", "k_proj", "v_proj")):
                 rows = slice(j * D, (j + 1) * D)
-                att.add_module(nm, _WB(view("%d.qkv.w" % i, rows), None if nm == "k_proj" else view("%d.qkv.b" % i, rows)))
-            att.add_module("out_proj", _WB(param(D, D), param(D)))
+                att.add_module(nm, WB(view("%d.qkv.w" % i, rows), None if nm == "k_proj" else view("%d.qkv.b" % i, rows)))
+            att.add_module("out_proj", WB(param(D, D), param(D)))
             layer = nn.Module()
             layer.add_module("self_attn", att)
-            layer.add_module("self_attn_layer_norm", _WB(param(D), param(D)))
-            layer.add_module("fc1", _WB(param(F, D), param(F)))
-            layer.add_module("fc2", _WB(param(D, F), param(D)))
-            layer.add_module("final_layer_norm", _WB(param(D), param(D)))
+            layer.add_module("self_attn_layer_norm", WB(param(D), param(D)))
+            layer.add_module("fc1", WB(param(F, D), param(F)))
+            layer.add_module("fc2", WB(param(D, F), param(D)))
+            layer.add_module("final_layer_norm", WB(param(D), param(D)))
             layers.append(layer)
         apm.add_module("layers", nn.ModuleList(layers))
-        apm.add_module("layer_norm", _WB(param(D), param(D)))
+        apm.add_module("layer_norm", WB(param(D), param(D)))
         self.apm = apm
         self.audio_projection_layer = nn.Module()
-        self.audio_projection_layer.add_module("linear1", _WB(param(E, D), param(E)))
-        self.audio_projection_layer.add_module("linear2", _WB(param(E, E), param(E)))
+        self.audio_projection_layer.add_module("linear1", WB(param(E, D), param(E)))
+        self.audio_projection_layer.add_module("linear2", WB(param(E, E), param(E)))
         self.eval()
-
-    # ------------------------------------------------------------------ nn.Module plumbing
-    @property
-    def dtype(self):
-        return torch.bfloat16
-
-    @property
-    def device(self):
-        return self.apm.layer_norm.weight.device
-
-    def train(self, mode=True):
-        if mode:
-            raise ValueError("x2i_amd WhisperAudioTower is eval-only")
-        return super().train(False)
-
-    def _apply(self, fn, recurse=True):
-        # the packed parameters are views: move the storage, re-point the views, then the ordinary parameters; the permuted copy is made again
-        for k in list(self._fused):
-            new = fn(self._fused[k])
-            if new.dtype != torch.bfloat16:
-                raise ValueError("x2i_amd WhisperAudioTower is bf16-only")
-            self._fused[k] = new
-        for p, name, index, shape in self._views:
-            t = self._fused[name][index]
-            p.data = t if shape is None else t.view(shape)
-        self._plans = {}
-        out = super()._apply(fn, recurse)
-        if self._conv2 is not None:
-            self.pack_()
-        return out
-
-    def load_state_dict(self, state_dict, strict=True, assign=False):
-        if assign:
-            raise ValueError("x2i_amd WhisperAudioTower: assign=True would detach the packed views")
-        out = super().load_state_dict(state_dict, strict=strict)
-        self.pack_()
-        return out
 
     @torch.no_grad()
     def pack_(self):
@@ -203,21 +149,17 @@ class WhisperAudioTower(nn.Module):
         m.load_state_dict({k: v.detach().to(device=device, dtype=torch.bfloat16) for k, v in sd.items()}, strict=True)
         return m
 
-    @torch.no_grad()
     def init_random_(self, seed=0):
         """Random weights in place (tools; there are no checkpoints offline): matrices and convolutions N(0, 1 / fan_in), the position
         table N(0, 0.02^2), biases 0.1 N(0, 1), norm weights 1 + 0.1 N(0, 1)"""
-        gen = torch.Generator(device=self.device).manual_seed(seed)
-        for n, p in self.named_parameters():
-            r = torch.randn(p.shape, device=p.device, generator=gen)
+        def rule(n, p, r):
             if n.endswith("embed_positions.weight"):
-                p.copy_(0.02 * r)
-            elif "norm" in n and n.endswith(".weight"):
-                p.copy_(1.0 + 0.1 * r)
-            elif p.dim() == 1:
-                p.copy_(0.1 * r)
-            else:
-                p.copy_(r * (p.numel() // p.shape[0]) ** -0.5)
+                return 0.02 * r
+            if "norm" in n and n.endswith(".weight"):
+                return 1.0 + 0.1 * r
+            return 0.1 * r if p.dim() == 1 else r * (p.numel() // p.shape[0]) ** -0.5
+
+        self._init_random(seed, rule)
         return self.pack_()
 
     # ------------------------------------------------------------------ plan
@@ -258,14 +200,6 @@ class WhisperAudioTower(nn.Module):
                         NRM=torch.empty((M, D), **bf), QKV=torch.empty((M, 3 * D), **bf), Q=torch.zeros((B, H, Spad, 64), **bf),
                         K=torch.zeros((B, H, Spad, 64), **bf), VT=torch.zeros((B, H, 64, Spad), **bf), ATT=torch.empty((M, D), **bf),
                         HH=torch.empty((M, F), **bf), P1=torch.empty((M, E), **bf), PL=torch.empty((B * max(p.n_max, 1), E), **bf))
-        return p
-
-    def _plan_for(self, lens, T, C):
-        key = (lens, T, C)
-        p = self._plans.get(key)
-        if p is None:
-            p = self.plan(lens, T, C)
-            self._plans = {key: p}      # keep one shape resident
         return p
 
     # ------------------------------------------------------------------ forward
