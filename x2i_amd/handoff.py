@@ -708,6 +708,198 @@ class HipInternVision:
         self.remove()
 
 
+def generate_positions(attention_mask, pad_position=0):
+    """The position ids the library's generate() derives from a 0/1 [B, S] mask for the prompt pass: the count of valid tokens before each
+    row, and pad_position in the padding -- 0 in `transformers` 5.x (_prepare_position_ids_for_generation), 1 in 4.x; the rows of the
+    padding are in the slab the projector reads, so the value is the library's and not a free choice.  None without a mask (the stack's
+    arange)."""
+    if attention_mask is None:
+        return None
+    return (attention_mask.long().cumsum(-1) - 1).masked_fill_(attention_mask == 0, pad_position)
+
+
+class _PromptHandoff:
+    """What the two prompt hand-offs share: the decoder stack on the HIP path called DIRECTLY -- not through the surrounding causal LM, so no
+    lm_head runs on the prompt -- and HipAudio's interface around it: install() replaces `generate` ON THE INSTANCE by one prompt pass and
+    remove() restores it; also a context manager, which restores on exceptions too."""
+
+    def _find(self, model, lm_name):
+        from .qwen import Qwen2DecoderStack
+        lm = getattr(model, lm_name, None)
+        if not isinstance(lm, nn.Module):
+            raise RuntimeError("handoff: no language model (model.%s) found in %s" % (lm_name, type(model).__name__))
+        if model.training:
+            raise ValueError("handoff.%s: the model is in training mode (its dummy-feature branches are not built); call .eval() first"
+                             % type(self).__name__)
+        self.model = model
+        self.decoder = find_decoder(lm)
+        self.stack = Qwen2DecoderStack.from_hf(self.decoder)
+        self.n_layers = len(self.decoder.layers)
+        self.C = self.n_layers + 1
+        self.calls = 0
+        self._installed = False
+
+    def install(self):
+        if not self._installed:
+            self._had = "generate" in self.model.__dict__
+            self._saved = self.model.__dict__.get("generate")
+            self.model.generate = self._generate
+            self._installed = True
+        return self
+
+    def remove(self):
+        if self._installed:
+            if self._had:
+                self.model.generate = self._saved
+            else:
+                del self.model.generate
+            self._installed = False
+
+    def __enter__(self):
+        return self.install()
+
+    def __exit__(self, *exc):
+        self.remove()
+
+
+class HipInternVLPrompt(_PromptHandoff):
+    """The prompt pass of an InternVL2.5 chat model (Qwen2 language model) with the embedding merge and the decoder stack on the HIP path:
+    prompt(input_ids, attention_mask, pixel_values) -> the [B, C, S, H] slab.  The features come from `model.extract_feature(pixel_values)`
+    -- the model's own, or HipInternVision's when that is installed -- the rows of `img_context_token_id` are ranked on the device
+    (merge.MergePlan.from_placeholder: the row order of the model's `input_embeds[selected] = vit_embeds.reshape(-1, C)`), and ONE launch
+    writes token rows and feature rows into entry 0 of the slab the stack then runs on.  Without pixels the ids run alone.  Positions are
+    the library generate()'s (generate_positions).  check=True costs one host read after the merge launch and raises ValueError when the
+    prompt's context tokens and the feature rows differ in number (the model's own assert) or an id lies outside the table.
+    install() makes `model.generate(pixel_values=, input_ids=, attention_mask=)` return the per-layer tuple of that slab (views, no copy):
+    the contract of the reference's modified generate()."""
+
+    def __init__(self, model, check_mask=True, check=True, img_context_token_id=None):
+        if not callable(getattr(model, "extract_feature", None)):
+            raise RuntimeError("handoff: no extract_feature found in %s" % type(model).__name__)
+        self._find(model, "language_model")
+        self.check_mask, self.check = check_mask, check
+        self.img_context_token_id = img_context_token_id
+
+    @torch.no_grad()
+    def prompt(self, input_ids, attention_mask=None, pixel_values=None, visual_features=None, position_ids=None):
+        from .merge import MergePlan
+        plan = None
+        if pixel_values is not None or visual_features is not None:
+            token = self.img_context_token_id if self.img_context_token_id is not None else getattr(self.model, "img_context_token_id", None)
+            if token is None:
+                raise ValueError("handoff.HipInternVLPrompt: pixels were given and img_context_token_id is not set (on the model or here)")
+            feats = visual_features if visual_features is not None else self.model.extract_feature(pixel_values)
+            plan = MergePlan.from_placeholder(input_ids, token, check=self.check).set_features(vision=feats.to(torch.bfloat16))
+        slab = self.stack(input_ids=input_ids, attention_mask=attention_mask, merge=plan, check_mask=self.check_mask,
+                          position_ids=position_ids if position_ids is not None else generate_positions(attention_mask))
+        self.calls += 1
+        return slab
+
+    def _generate(self, pixel_values=None, input_ids=None, attention_mask=None, visual_features=None, **kw):
+        if input_ids is None:
+            raise ValueError("handoff.HipInternVLPrompt: generate() needs input_ids")
+        return tuple(self.prompt(input_ids, attention_mask, pixel_values, visual_features).unbind(1))
+
+
+class HipMiniCPMPrompt(_PromptHandoff):
+    """The prompt pass of a MiniCPM-o model with the embedding merge and the decoder stack on the HIP path: prompt(**processor outputs) ->
+    the [B, C, S, H] slab.  It does the work of get_vllm_embedding up to the scatter -- every image flattened to patch rows and padded to
+    one batch, the patch mask and the target sizes, `model.vpm` in chunks of config.vision_batch_size and `model.resampler`, each whichever
+    implementation is installed (the model's own, HipSiglip's, HipResampler's) -- takes the audio rows from `model.get_audio_embedding`
+    (the model's own or HipAudio's), and then ONE launch writes token rows (times llm.config.scale_emb where the field exists), vision
+    rows and audio rows into entry 0 of the slab the stack runs on (merge.MergePlan.from_bounds).  All bounds and target sizes of a call
+    cross to the host in ONE read (none when they are on the CPU); the model's own path reads two ends per image bound.  Both forms of
+    config.chunk_input are served: True lays a sample's concatenated audio rows over its bounds in order, False pairs audio i with bound
+    i and raises the model's ValueError on a length mismatch.  A sample's bounds and its feature rows must agree in number (ValueError,
+    before any launch).  install() makes `model.generate(**inputs)` return an object whose `hidden_states[0]` is the per-layer tuple of
+    that slab: what the reference stacks."""
+
+    def __init__(self, model, check_mask=True, check=True):
+        for name in ("vpm", "resampler"):
+            if not isinstance(getattr(model, name, None), nn.Module):
+                raise RuntimeError("handoff: no model.%s found in %s" % (name, type(model).__name__))
+        self._find(model, "llm")
+        self.check_mask, self.check = check_mask, check
+        self.scale = float(getattr(model.llm.config, "scale_emb", 1.0))
+
+    def _vision_rows(self, pixel_values_list, tgt_sizes, dtype, device):
+        """-> (bf16 [images, queries, H] or None, images per sample); tgt_sizes: host lists (merge.host_ints)"""
+        import numpy as np
+        flat, img_cnt = [], []
+        for pixel_values in pixel_values_list:
+            img_cnt.append(len(pixel_values))
+            flat.extend(i.flatten(end_dim=1).permute(1, 0) for i in pixel_values)
+        if not flat:
+            return None, img_cnt
+        sizes = [row for t in tgt_sizes if isinstance(t, list) and t for row in (t if isinstance(t[0], list) else [t])]
+        if len(sizes) != len(flat):
+            raise ValueError("handoff.HipMiniCPMPrompt: %d images and %d target sizes" % (len(flat), len(sizes)))
+        patches = [int(h) * int(w) for h, w in sizes]
+        x = torch.nn.utils.rnn.pad_sequence(flat, batch_first=True, padding_value=0.0)
+        n, L, _ = x.shape
+        x = x.permute(0, 2, 1).reshape(n, 3, -1, L).to(device=device, dtype=dtype)
+        mask = np.zeros((n, 1, max(patches)), dtype=bool)
+        for i, p in enumerate(patches):
+            mask[i, 0, :p] = True
+        mask = torch.from_numpy(mask).to(device)
+        tgt = torch.tensor(sizes, dtype=torch.int32, device=device)
+        step = int(self.model.config.vision_batch_size)
+        hs = [self.model.vpm(x[i:i + step], patch_attention_mask=mask[i:i + step], tgt_sizes=tgt[i:i + step]).last_hidden_state
+              for i in range(0, n, step)]
+        return self.model.resampler(hs[0] if len(hs) == 1 else torch.cat(hs, dim=0), tgt).to(torch.bfloat16), img_cnt
+
+    @torch.no_grad()
+    def prompt(self, input_ids, pixel_values=None, tgt_sizes=None, image_bound=None, audio_features=(), audio_feature_lens=None,
+               audio_bounds=None, attention_mask=None, position_ids=None, **ignored):
+        from .merge import MergePlan, host_ints
+        model, cfg = self.model, self.model.config
+        B, S = input_ids.shape
+        w = self.stack.embed_tokens.weight
+        image_bound, audio_bounds, tgt_sizes = host_ints(image_bound, audio_bounds, tgt_sizes)        # the one host read
+        image_bound = [list(b) for b in (image_bound or [])]
+        vision, img_cnt = self._vision_rows(pixel_values if pixel_values is not None else [[]] * B, tgt_sizes or [], w.dtype, w.device)
+        vision_rows = [n * (vision.shape[1] if vision is not None else 0) for n in img_cnt]
+        audio, audio_rows = None, None
+        if getattr(cfg, "init_audio", True) and audio_features is not None and len(audio_features) > 0:
+            embs = model.get_audio_embedding(dict(audio_features=audio_features, audio_feature_lens=audio_feature_lens),
+                                             chunk_length=getattr(cfg, "audio_chunk_length", -1))
+            if len(embs) != B:
+                raise ValueError("handoff.HipMiniCPMPrompt: audio embeddings for %d prompts, a batch of %d" % (len(embs), B))
+            audio_bounds = [list(b) for b in (audio_bounds or [])] + [[]] * (B - len(audio_bounds or []))
+            if not getattr(cfg, "chunk_input", False):
+                for i in range(B):
+                    for e, (s0, s1) in zip(embs[i], audio_bounds[i]):
+                        if e.shape[0] != s1 - s0:
+                            raise ValueError("Shape mismatch: Trying to assign embeddings of shape %s to input indices of length %d"
+                                             % (tuple(e.shape), s1 - s0))
+                    audio_bounds[i] = audio_bounds[i][:len(embs[i])]
+                    embs[i] = embs[i][:len(audio_bounds[i])]
+            else:
+                audio_bounds = [b if embs[i] else [] for i, b in enumerate(audio_bounds)]      # (the model skips a sample without audio rows)
+            audio_rows = [sum(int(e.shape[0]) for e in embs[i]) for i in range(B)]
+            rows = [e for sample in embs for e in sample]
+            if rows:
+                audio = (rows[0] if len(rows) == 1 else torch.cat(rows, dim=0)).to(device=w.device, dtype=torch.bfloat16)
+        else:
+            audio_bounds = None
+        plan = MergePlan.from_bounds(B, S, image_bound, audio_bounds, device=w.device, check=self.check, vision_rows=vision_rows,
+                                     audio_rows=audio_rows).set_features(vision=vision, audio=audio)
+        slab = self.stack(input_ids=input_ids, attention_mask=attention_mask, merge=plan, embed_scale=self.scale, check_mask=self.check_mask,
+                          position_ids=position_ids if position_ids is not None else generate_positions(attention_mask))
+        self.calls += 1
+        return slab
+
+    def _generate(self, input_ids=None, stream=False, vision_hidden_states=None, **inputs):
+        if input_ids is None:
+            raise ValueError("handoff.HipMiniCPMPrompt: generate() needs input_ids")
+        if stream or vision_hidden_states is not None:
+            raise ValueError("handoff.HipMiniCPMPrompt: stream=True and precomputed vision_hidden_states are not built; remove() the hand-off")
+        for k in ("tokenizer", "max_new_tokens", "decode_text", "spk_bounds"):
+            inputs.pop(k, None)
+        from types import SimpleNamespace
+        return SimpleNamespace(hidden_states=(tuple(self.prompt(input_ids, **inputs).unbind(1)),), sequences=None)
+
+
 def prefill_hidden_states(model, dtype=torch.bfloat16, **inputs):
     """Convenience wrapper: [B, C, S, H] conditioning tensor of `inputs` from one forward of `model`."""
     return HiddenStateSlab(find_decoder(model), dtype).prefill(model, **inputs)

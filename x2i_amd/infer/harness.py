@@ -70,7 +70,10 @@ def build_parser(family):
                    help="run the MLLM's 128-token generate() as the reference does instead of the single prefill forward")
     p.add_argument("--hip_decoder", action="store_true",
                    help="run the MLLM's decoder stack over the prompt on the HIP path (x2i_amd/qwen.py) instead of the library's forward; "
-                        "prefill only, so not with --full_generate or --use_answer")
+                        "prefill only, so not with --full_generate or --use_answer.  Qwen2.5-VL: inside the library's model forward "
+                        "(handoff.HipPrefill).  MiniCPM-o and InternVL2.5: the stack is called directly, with the token lookup and the merge of "
+                        "the vision / audio rows in one launch that writes layer 0's input (x2i_amd/merge.py, handoff.HipMiniCPMPrompt / "
+                        "HipInternVLPrompt), and no lm_head runs on the prompt; independent of --hip_vision, --hip_resampler and --hip_audio")
     p.add_argument("--hip_vision", action="store_true",
                    help="run the MLLM's vision tower on the HIP path instead of the library's forward: Qwen2.5-VL's model.visual "
                         "(x2i_amd/qwen_vision.py), MiniCPM-o's SigLIP model.vpm (x2i_amd/siglip.py) or InternVL2.5's extract_feature -- "

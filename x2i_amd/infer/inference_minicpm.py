@@ -26,7 +26,9 @@ class MiniCPMConditioner:
     dependence on the reference's patched generate() returning `.hidden_states`.  full_generate: the reference's form."""
 
     def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None, processor=None, hip_vision=False, hip_resampler=False,
-                 hip_audio=False):
+                 hip_audio=False, hip_decoder=False, use_answer=False):
+        if hip_decoder and not (prefill_only and not use_answer):     # (refused before a checkpoint is read)
+            raise ValueError("--hip_decoder serves the prompt pass only: not with --full_generate or --use_answer")
         if model is None:
             from transformers import AutoModel, AutoProcessor, AutoTokenizer
             model = AutoModel.from_pretrained(path, trust_remote_code=True, torch_dtype=torch.bfloat16).eval().to(device)
@@ -34,8 +36,13 @@ class MiniCPMConditioner:
             processor = AutoProcessor.from_pretrained(path, trust_remote_code=True)
         self.model, self.tokenizer, self.processor = model, tokenizer, processor
         self.device = device
-        self.slab = None
-        if prefill_only:
+        self.slab = self.prompt = None
+        if hip_decoder:
+            # hip_decoder: the embedding merge and the decoder stack of the prompt pass on the HIP path (handoff.HipMiniCPMPrompt): the towers
+            # below -- the model's own or their HIP forms -- feed ONE merge launch that writes layer 0's input, and no lm_head runs
+            from ..handoff import HipMiniCPMPrompt
+            self.prompt = HipMiniCPMPrompt(self.model)
+        elif prefill_only:
             from ..handoff import HiddenStateSlab, find_decoder
             self.slab = HiddenStateSlab(find_decoder(self.model))
         # hip_vision: the SigLIP tower behind model.vpm on the HIP path (x2i_amd/siglip.py), under the slab and under the reference's
@@ -59,6 +66,8 @@ class MiniCPMConditioner:
 
     def hidden_states(self, inputs):
         """processor outputs -> [B, C, S, H]"""
+        if self.prompt is not None:
+            return self.prompt.prompt(**inputs)
         run = lambda: self.model.generate(**inputs, tokenizer=self.tokenizer, max_new_tokens=1, decode_text=False)  # noqa: E731
         if self.slab is not None:
             return self.slab.capture(run)
@@ -110,7 +119,9 @@ def main(argv=None):
                                                                                               prefill_only=not args.full_generate,
                                                                                               hip_vision=args.hip_vision,
                                                                                               hip_resampler=args.hip_resampler,
-                                                                                              hip_audio=args.hip_audio)
+                                                                                              hip_audio=args.hip_audio,
+                                                                                              hip_decoder=args.hip_decoder,
+                                                                                              use_answer=args.use_answer)
     Harness(args, "minicpm", cond, device).run_tasks(tasks(args))
 
 

@@ -19,9 +19,10 @@ touch the slab (input_layernorm reading it, the final norm writing it) are launc
 8 + B otherwise.
 
 Parameter names are the library's, so a decoder's state dict loads strictly; the q|k|v weights and biases and the gate|up weights are views
-into stacked storage (as T5Stack's are).  The embedding merge stays on PyTorch; the towers in front of it have HIP paths of their own
-(x2i_amd/qwen_vision.py, siglip.py, resampler.py, and whisper.py for MiniCPM-o's audio tower) or stay on PyTorch: the stack takes `inputs_embeds` (or `input_ids`, a torch gather
-from embed_tokens).
+into stacked storage (as T5Stack's are).  The towers in front of the stack have HIP paths of their own (x2i_amd/qwen_vision.py, siglip.py,
+resampler.py, whisper.py, internvit.py) or stay on PyTorch.  The stack takes `inputs_embeds`, or `input_ids` with an optional `merge=` plan
+(x2i_amd/merge.py): the token lookup and the embedding merge of MiniCPM-o and InternVL are one launch of include/x2i_merge.h that writes
+entry 0 of the slab.  (Qwen2.5-VL's masked_scatter sits inside the library's model forward and reaches the stack as inputs_embeds.)
 
 Decoding with a key/value cache (include/x2i_qwen_decode.h; the generated answer the reference conditions on under --use_answer) is three
 more methods: new_cache(B, capacity), prefill(cache, ...) -- forward's slab bit for bit, written through the cache's per-layer K / V^T with
@@ -35,7 +36,7 @@ forward itself stays prefill only.
 import torch
 import torch.nn as nn
 
-from . import ops, qwen_ops, t5_ops
+from . import merge_ops, ops, qwen_ops, t5_ops
 from ._packed import WB, PackedModule, config_fields, config_object
 
 _FIELDS = dict(hidden_size=3584, num_attention_heads=28, num_key_value_heads=4, intermediate_size=18944, num_hidden_layers=28, rms_norm_eps=1e-6,
@@ -206,30 +207,37 @@ class Qwen2DecoderStack(PackedModule):
         ws = dict(Spad=Spad, X1=torch.empty((B * S, D), **bf), X2=torch.empty((B * S, D), **bf), NRM=torch.empty((B * S, D), **bf),
                   QKV=torch.empty((B * S, nq + 2 * nkv), **bf), Q=torch.zeros((B, Hq, Spad, dk), **bf), K=torch.zeros((B, Hkv, Spad, dk), **bf),
                   VT=torch.zeros((B, Hkv, dk, Spad), **bf), ATT=torch.empty((B * S, nq), **bf), HH=torch.empty((B * S, 2 * F), **bf),
-                  G=torch.empty((B * S, F), **bf), arange=torch.arange(S, device=dev)[None].expand(B, S), rope={})
+                  G=torch.empty((B * S, F), **bf), arange=torch.arange(S, device=dev)[None].expand(B, S), rope={},
+                  merge_err=torch.zeros((1,), device=dev, dtype=torch.int32))   # set by a plain input_ids pass that met an id outside the table
         self._ws = {(B, S): ws}  # keep one shape resident
         return ws
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, inputs_embeds=None, input_ids=None, attention_mask=None, position_ids=None, check_mask=True, use_cache=None,
-                past_key_values=None, **unused):
+                past_key_values=None, merge=None, embed_scale=1.0, **unused):
         """-> bf16 [B, C, S, H], C = num_layers + 1: entry i < L is the INPUT of layer i, the last entry the final norm's output (the HF
         `hidden_states` convention).  attention_mask: None or 0/1 [B, S] whose valid keys are one contiguous run per sample (left, right or
         two-sided padding); check_mask=True verifies that with one host read (ValueError otherwise), False skips the check (graph capture).
         position_ids: None (arange(S), as the library's forward), [B, S], or [3, B, S] / [4, B, S] for M-RoPE (of four, the first -- the text
         positions the library builds its mask from -- is dropped).  After the first call at a (B, S) a forward allocates the slab and the two
         RoPE tables and nothing else (with a mask: the two range vectors and their torch temporaries too).  Rows before a left-padded
-        sample's first valid token hold finite values that the library does not define."""
+        sample's first valid token hold finite values that the library does not define.
+        input_ids are looked up by the merge kernel (include/x2i_merge.h), which writes slab[:, 0] directly; merge: a merge.MergePlan for
+        the same [B, S], whose feature rows (vision, audio) the same ONE launch puts in the places the prompt reserves for them -- there
+        is no inputs_embeds tensor and no copy; embed_scale: see _prompt_pass."""
         if use_cache or past_key_values is not None:
             raise ValueError("x2i_amd Qwen2DecoderStack: prefill only; use_cache=True and past_key_values are not built")
-        return self._prompt_pass(None, inputs_embeds, input_ids, attention_mask, position_ids, check_mask)
+        return self._prompt_pass(None, inputs_embeds, input_ids, attention_mask, position_ids, check_mask, merge, embed_scale)
 
-    def _prompt_pass(self, cache, inputs_embeds, input_ids, attention_mask, position_ids, check_mask):
+    def _prompt_pass(self, cache, inputs_embeds, input_ids, attention_mask, position_ids, check_mask, merge=None, embed_scale=1.0):
         """forward's launches; with a cache (prefill) rope_split and the attention run with Spad = cap on the cache's own per-layer K / V^T, and
-        the cache's ranges and next positions are set: the same kernels on the same values, so the slab is bit-identical."""
+        the cache's ranges and next positions are set: the same kernels on the same values, so the slab is bit-identical.
+        embed_scale: what the token rows (not the feature rows) are multiplied by, one f32 multiply and one rounding (MiniCPM's scale_emb)."""
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("Qwen2DecoderStack: pass exactly one of input_ids and inputs_embeds")
+        if merge is not None and input_ids is None:
+            raise ValueError("Qwen2DecoderStack: merge= goes with input_ids (with inputs_embeds the merge has been done)")
         c = self.config
         D, dk, Hq, Hkv, F, eps, L = c.hidden_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads, c.intermediate_size, c.rms_norm_eps, len(self.layers)
         nq, C = Hq * dk, len(self.layers) + 1
@@ -268,8 +276,11 @@ class Qwen2DecoderStack(PackedModule):
         if input_ids is not None:
             if input_ids.device != dev:
                 raise ops._lib.X2IError("x2i_amd: input_ids must live on the model's device (got %s)" % input_ids.device)
-            for b in range(B):
-                torch.index_select(self.embed_tokens.weight, 0, input_ids[b], out=slab[b, 0])   # the token lookup is a torch gather
+            # the token lookup and the embedding merge are ONE launch that writes entry 0 (without a plan: every row a table row)
+            if merge is not None:
+                merge.launch(slab[:, 0], input_ids, self.embed_tokens.weight, embed_scale)
+            else:
+                merge_ops.embed_merge(slab[:, 0], ws["merge_err"], ids=input_ids.contiguous(), table=self.embed_tokens.weight, scale=embed_scale)
         else:
             ops._req(inputs_embeds, torch.bfloat16, "inputs_embeds")
             slab[:, 0].copy_(inputs_embeds)
@@ -303,14 +314,14 @@ class Qwen2DecoderStack(PackedModule):
         return Qwen2DecodeCache(self, B, capacity)
 
     @torch.no_grad()
-    def prefill(self, cache, inputs_embeds=None, input_ids=None, attention_mask=None, position_ids=None, check_mask=True, **unused):
+    def prefill(self, cache, inputs_embeds=None, input_ids=None, attention_mask=None, position_ids=None, check_mask=True, merge=None, embed_scale=1.0, **unused):
         """forward's arguments and forward's slab [B, C, S, H], bit for bit: the same launches, but rope_split and the attention run with
         Spad = cap on the cache's own per-layer K / V^T.  Sets the cache's key ranges (from the mask) and every sample's next position: one
         more than the largest position id of its valid tokens over all axes -- for plain Qwen2 the count of valid tokens, for Qwen2.5-VL what
         the library's rope_deltas yields.  Refuses S + 1 > cap."""
         if not isinstance(cache, Qwen2DecodeCache) or cache.owner() is not self:
             raise ValueError("x2i_amd Qwen2DecoderStack.prefill: the cache must come from this stack's new_cache()")
-        return self._prompt_pass(cache, inputs_embeds, input_ids, attention_mask, position_ids, check_mask)
+        return self._prompt_pass(cache, inputs_embeds, input_ids, attention_mask, position_ids, check_mask, merge, embed_scale)
 
     @torch.no_grad()
     def decode_step(self, cache, inputs_embeds=None, input_ids=None, out=None):
