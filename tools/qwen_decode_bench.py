@@ -17,6 +17,11 @@ on every side) and a fourth side joins the interleave: HipGenerate(hip_head=True
 include/x2i_qwen_head.h inside the captured step; its comparator is `hip graph`, the same loop with the torch head.  --only head times one
 x2i_qwen_head_logits_argmax_bf16 + x2i_qwen_head_select pair over a ring of distinct head weights, beside torch's lm_head call (bf16
 logits) and torch's copy over the same bytes.
+With --w8 the e4m3 weight-only decode steps join (include/x2i_qwen_decode_w8.h, Qwen2DecoderStack.pack_w8): per layer shape a `decode_linear_w8`
+line beside each `decode_linear` line -- the two rings captured in a graph each and replayed alternately in the same run, us, TB/s of the
+(halved) weight bytes, the ratio to the bf16 kernel and min .. max over the reps of both -- and in the generate table a `hip w8` side
+(HipGenerate(w8=True), graph-replayed, torch head) next to `hip graph`, with `hip head + w8` under --vocab real
+(profiles/qwen_decode_w8_bench.log).
 Output: stdout and, with --log, a file (profiles/qwen_decode_bench.log, profiles/qwen_head_bench.log)."""
 import argparse
 import os
@@ -27,7 +32,9 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from x2i_amd import ops  # noqa: E402
 from x2i_amd import qwen_decode_ops as qd  # noqa: E402
+from x2i_amd import qwen_decode_w8_ops as qd8  # noqa: E402
 from x2i_amd import qwen_head_ops as qh  # noqa: E402
 from x2i_amd.handoff import HipGenerate  # noqa: E402
 
@@ -76,7 +83,7 @@ def wall(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
-def bench_generate(say, name, c, batches, S, T, reps, head=False):
+def bench_generate(say, name, c, batches, S, T, reps, head=False, w8=False):
     model = library_model(c)
     hg = HipGenerate(model, check_mask=False)
     for B in batches:
@@ -90,6 +97,11 @@ def bench_generate(say, name, c, batches, S, T, reps, head=False):
         }
         if head:
             sides["hip head"] = lambda n: hg.generate(model, max_new_tokens=n, graph=True, hip_head=True, input_ids=ids, attention_mask=mask)
+        if w8:
+            sides["hip w8"] = lambda n: hg.generate(model, max_new_tokens=n, graph=True, w8=True, input_ids=ids, attention_mask=mask)
+            if head:
+                sides["hip head + w8"] = lambda n: hg.generate(model, max_new_tokens=n, graph=True, hip_head=True, w8=True, input_ids=ids,
+                                                               attention_mask=mask)
         for fn in sides.values():       # warm-up: every side once at both lengths
             fn(T)
             fn(1)
@@ -102,7 +114,7 @@ def bench_generate(say, name, c, batches, S, T, reps, head=False):
                 per[k].append((tT - t1) / (T - 1))
                 one[k].append(t1)
         for k in sides:
-            say("%-3s B=%d prompt %d, %d tokens, %-9s: %.3f ms per token (min %.3f .. max %.3f, %d reps); prompt pass + first token %.1f ms"
+            say("%-3s B=%d prompt %d, %d tokens, %-13s: %.3f ms per token (min %.3f .. max %.3f, %d reps); prompt pass + first token %.1f ms"
                 % (name, B, S, T, k, statistics.median(per[k]), min(per[k]), max(per[k]), reps, statistics.median(one[k])))
         lib = statistics.median(per["library"])
         say("%-3s B=%d                              : library / HIP eager %.2f x, library / HIP graph %.2f x; weights %.2f GB per token -> %.2f TB/s at the graph's rate"
@@ -112,6 +124,13 @@ def bench_generate(say, name, c, batches, S, T, reps, head=False):
             h, g = statistics.median(per["hip head"]), statistics.median(per["hip graph"])
             say("%-3s B=%d                              : hip head %.3f ms against hip graph (torch head) %.3f ms per token: %+.3f ms, %.3f x; "
                 "lm_head %.2f GB per token" % (name, B, h, g, h - g, g / h, c["vocab_size"] * c["hidden_size"] * 2 / 1e9))
+        if w8:
+            for a, b in (("hip w8", "hip graph"),) + ((("hip head + w8", "hip head"),) if head else ()):
+                ta, tb = statistics.median(per[a]), statistics.median(per[b])
+                say("%-3s B=%d                              : %s %.3f ms against %s %.3f ms per token: %+.3f ms, %.3f x (min .. max of the two: "
+                    "%.3f .. %.3f, %.3f .. %.3f); decoder weights %.2f -> %.2f GB per token"
+                    % (name, B, a, ta, b, tb, ta - tb, tb / ta, min(per[a]), max(per[a]), min(per[b]), max(per[b]), decoder_bytes(c) / 1e9,
+                       decoder_bytes(c) / 2e9))
     del hg, model
     torch.cuda.empty_cache()
 
@@ -145,7 +164,33 @@ def graph_ms(body, reps):
     return statistics.median(ms)
 
 
-def bench_linears(say, name, c, batches, reps):
+def graph_ms_interleaved(bodies, reps):
+    """per body the list of ms of one replay, the bodies captured in a graph each and replayed in turn (a, b, a, b, ...)"""
+    graphs = []
+    for body in bodies:
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            body()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            body()
+        g.replay()
+        graphs.append(g)
+    ms = [[] for _ in bodies]
+    for _ in range(reps):
+        for i, g in enumerate(graphs):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            g.replay()
+            t1.record()
+            torch.cuda.synchronize()
+            ms[i].append(t0.elapsed_time(t1))
+    return ms
+
+
+def bench_linears(say, name, c, batches, reps, w8=False):
     D, F = c["hidden_size"], c["intermediate_size"]
     dk = D // c["num_attention_heads"]
     nq, nkv = c["num_attention_heads"] * dk, c["num_key_value_heads"] * dk
@@ -159,15 +204,32 @@ def bench_linears(say, name, c, batches, reps):
         t_copy = graph_ms(lambda: [dst.copy_(W[i]) for i in range(ring)], reps) / ring
         say("%-3s %-13s N=%-5d K=%-5d %6.1f MB: copy of the same bytes %.1f us = %.2f TB/s (read + write)"
             % (name, label, N, K, nbytes / 1e6, t_copy * 1e3, 2 * nbytes / (t_copy * 1e-3) / 1e12))
+        if w8:      # the same ring, quantised as pack_w8() quantises a layer's weight: distinct memory per entry, half the bytes
+            q = [ops.quantize_rows_fp8(W[i]) for i in range(ring)]
+            W8, S8 = torch.stack([t[0].view(torch.uint8) for t in q]), torch.stack([t[1] for t in q])
+            del q
         for B in batches:
             x = torch.randn((B, K), device="cuda").bfloat16()
             res = None if gate or label.startswith("qkv") else torch.randn((B, N), device="cuda").bfloat16()
             bias = torch.randn((rows,), device="cuda").bfloat16() if label.startswith("qkv") else None
             out = torch.empty((B, N), device="cuda", dtype=torch.bfloat16)
+            if w8:
+                ms16, ms8 = graph_ms_interleaved([lambda: [qd.linear(x, W[i], bias, res, out=out, gate=gate) for i in range(ring)],
+                                                  lambda: [qd8.linear_w8(x, W8[i], S8[i], bias, res, out=out, gate=gate) for i in range(ring)]], reps)
+                us16, us8 = [t / ring * 1e3 for t in ms16], [t / ring * 1e3 for t in ms8]
+                m16, m8 = statistics.median(us16), statistics.median(us8)
+                say("%-3s %-13s N=%-5d K=%-5d B=%d          : decode_linear    %.1f us (min %.1f .. max %.1f) = %.2f TB/s of weight (%.2f of the copy's time)"
+                    % (name, label, N, K, B, m16, min(us16), max(us16), nbytes / (m16 * 1e-6) / 1e12, m16 * 1e-3 / t_copy))
+                verdict = "faster by more than the spread" if max(us8) < min(us16) else ("NOT faster" if m8 >= m16 else "faster, within the spread")
+                say("%-3s %-13s N=%-5d K=%-5d B=%d          : decode_linear_w8 %.1f us (min %.1f .. max %.1f) = %.2f TB/s of weight (%.1f MB); bf16 / w8 "
+                    "%.2f x: %s" % (name, label, N, K, B, m8, min(us8), max(us8), nbytes / 2 / (m8 * 1e-6) / 1e12, nbytes / 2e6, m16 / m8, verdict))
+                continue
             t = graph_ms(lambda: [qd.linear(x, W[i], bias, res, out=out, gate=gate) for i in range(ring)], reps) / ring
             say("%-3s %-13s N=%-5d K=%-5d B=%d          : decode_linear %.1f us = %.2f TB/s of weight (%.2f of the copy's time)"
                 % (name, label, N, K, B, t * 1e3, nbytes / (t * 1e-3) / 1e12, t / t_copy))
         del W, dst
+        if w8:
+            del W8, S8
         torch.cuda.empty_cache()
 
 
@@ -217,6 +279,7 @@ def main():
     ap.add_argument("--only", choices=("all", "generate", "linears", "head"), default="all")
     ap.add_argument("--vocab", choices=("small", "real"), default="small",
                     help="real: the models' own vocabularies, and the hip_head side in the generate table")
+    ap.add_argument("--w8", action="store_true", help="add the e4m3 weight-only sides: decode_linear_w8 per shape, hip w8 (and hip head + w8) per generate")
     ap.add_argument("--log", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -234,10 +297,10 @@ def main():
     for name in a.configs.split(","):
         c = dict(CONFIGS[name], vocab_size=REAL_VOCAB[name]) if real else CONFIGS[name]
         if a.only in ("all", "generate"):
-            bench_generate(say, name, c, batches, a.prompt, a.tokens, a.reps, head=real)
+            bench_generate(say, name, c, batches, a.prompt, a.tokens, a.reps, head=real, w8=a.w8)
         if a.only in ("all", "linears"):
             with torch.no_grad():
-                bench_linears(say, name, c, batches, 10)
+                bench_linears(say, name, c, batches, 10, w8=a.w8)
         if a.only == "head" or (a.only == "all" and real):
             with torch.no_grad():
                 bench_head(say, name, dict(CONFIGS[name], vocab_size=REAL_VOCAB[name]), batches, 10)

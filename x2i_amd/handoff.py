@@ -198,9 +198,13 @@ class HipGenerate:
     a second, both inside the captured step, so a generated token is one graph replay and no torch op; token 0 goes through the same two
     kernels on each sample's last valid prompt row.  head_plan decides which processor lists fuse; any other raises.  A token is then the
     argmax of f32-accumulated logits that were never rounded to bf16: where the top two logits lie within one bf16 ulp the torch head ties
-    them and takes the lower index, so the two paths can pick different tokens there."""
+    them and takes the lower index, so the two paths can pick different tokens there.
+    With w8=True (off by default; per call generate(w8=...)) the four linears of every layer of a decode step read e4m3 weights with one
+    f32 scale per output row (Qwen2DecoderStack.pack_w8, made once at first use and kept beside the bf16 weights, which the prompt pass
+    still runs on): half the weight bytes per token.  The lm_head stays bf16 under either head.  The captured steps hold their weights by
+    pointer, so the graphs are kept per value of w8."""
 
-    def __init__(self, model, check_mask=True, hip_head=False):
+    def __init__(self, model, check_mask=True, hip_head=False, w8=False):
         from .qwen import Qwen2DecoderStack
         self.decoder = find_decoder(model)
         self.stack = Qwen2DecoderStack.from_hf(self.decoder)
@@ -208,6 +212,7 @@ class HipGenerate:
         self.C = self.n_layers + 1
         self.check_mask = check_mask
         self.hip_head = hip_head
+        self.w8 = w8
         self.slab = self._cache = None
         self._state = {}
 
@@ -240,11 +245,12 @@ class HipGenerate:
 
     @torch.no_grad()
     def generate(self, model, max_new_tokens=128, eos_token_id=None, pad_token_id=None, logits_processor=None, graph=True, check_every=16,
-                 generation_config=None, hip_head=None, **inputs):
+                 generation_config=None, hip_head=None, w8=None, **inputs):
         """-> GenerateResult.  inputs: the model's forward arguments of the prompt (input_ids required; attention_mask, pixel_values, ...).
         eos_token_id: an id, a list of ids or None (never stop early); pad_token_id: what follows a sample's end token (default: the first
         end token, else 0).  logits_processor: a list of callables (input_ids [B, len], scores f32 [B, V]) -> scores.  hip_head: None takes
-        the constructor's; True needs a list that head_plan accepts."""
+        the constructor's; True needs a list that head_plan accepts.  w8: None takes the constructor's; True runs the decode steps on the
+        stack's e4m3 weights (packed at first use)."""
         self.refuse_sampling(generation_config if generation_config is not None else getattr(model, "generation_config", None))
         if max_new_tokens < 1:
             raise ValueError("handoff.HipGenerate: max_new_tokens must be at least 1")
@@ -255,6 +261,7 @@ class HipGenerate:
         pad = int(pad_token_id) if pad_token_id is not None else (eos[0] if eos else 0)
         processors = list(logits_processor or [])
         hip_head = self.hip_head if hip_head is None else hip_head
+        w8 = bool(self.w8 if w8 is None else w8)
         head = model.get_output_embeddings()
         if hip_head:       # every refusal comes before anything runs
             import inspect
@@ -267,6 +274,8 @@ class HipGenerate:
                 raise ValueError("handoff.HipGenerate: hip_head needs a pad token inside the vocabulary (got %d)" % pad)
             if "logits_to_keep" in inspect.signature(model.forward).parameters and "logits_to_keep" not in inputs:
                 inputs = dict(inputs, logits_to_keep=1)       # the model's own logits are not used: one position, not all S
+        if w8 and self.stack._w8 is None:
+            self.stack.pack_w8()
         self.slab = self._cache = None
         self._new_tokens = max_new_tokens
         had = "forward" in self.decoder.__dict__
@@ -288,7 +297,7 @@ class HipGenerate:
         rows = torch.arange(B, device=dev)
         last = (cache.k_hi - 1).long()                                   # the last valid token of each sample, under either padding
         if hip_head:
-            return self._generate_hip_head(prompt, cache, ids, head.weight, penalty, eos, pad, T, rows, last, graph, check_every)
+            return self._generate_hip_head(prompt, cache, ids, head.weight, penalty, eos, pad, T, rows, last, graph, check_every, w8)
         sequences = torch.full((B, S + T), pad, device=dev, dtype=torch.long)
         sequences[:, :S] = ids
         answer = torch.empty((B, C, max(T - 1, 0), H), device=dev, dtype=torch.bfloat16)
@@ -316,35 +325,39 @@ class HipGenerate:
         if st.get("head") is not head:      # (a graph holds the lm_head it was captured with)
             st.pop("graph", None)
             st["head"] = head
+        graphs = st.setdefault("graph", {})     # w8 -> (graph, logits): a captured step holds its weights by pointer
+        if graphs and st.get("w8_pack") is not self.stack._w8:       # ... and a new pack is new pointers
+            graphs.pop(True, None)
+        st["w8_pack"] = self.stack._w8
         t = 1
         while t < T:
             if check_every and t % check_every == 0 and eos_t is not None and bool(done.all()):      # the one host read per check_every steps
                 break
             if not graph:
                 cache_out = answer[:, :, t - 1]
-                self.stack.decode_step(cache, input_ids=token, out=cache_out)
+                self.stack.decode_step(cache, input_ids=token, out=cache_out, w8=w8)
                 logits = head(cache_out[:, -1])
             else:
-                if "graph" not in st and not st.get("warm"):
+                if w8 not in graphs and w8 not in st.setdefault("warm", set()):
                     # the very first step runs eagerly on a side stream (the warm-up a capture needs); the next one is the capture
                     side = torch.cuda.Stream()
                     side.wait_stream(torch.cuda.current_stream())
                     with torch.cuda.stream(side):
-                        self.stack.decode_step(cache, input_ids=token, out=step_out)
+                        self.stack.decode_step(cache, input_ids=token, out=step_out, w8=w8)
                         logits = head(step_out[:, -1])
                     torch.cuda.current_stream().wait_stream(side)
-                    st["warm"] = True
+                    st["warm"].add(w8)
                 else:
-                    if "graph" not in st:
+                    if w8 not in graphs:
                         g = torch.cuda.CUDAGraph()
                         with torch.cuda.graph(g):
-                            self.stack.decode_step(cache, input_ids=token, out=step_out)
-                            st["logits"] = head(step_out[:, -1])
+                            self.stack.decode_step(cache, input_ids=token, out=step_out, w8=w8)
+                            captured = head(step_out[:, -1])
                         cache.steps -= 1                 # (a capture runs nothing: the replay below is this step)
-                        st["graph"] = g
-                    st["graph"].replay()
+                        graphs[w8] = (g, captured)
+                    graphs[w8][0].replay()
                     cache.steps += 1
-                    logits = st["logits"]
+                    logits = graphs[w8][1]
                 answer[:, :, t - 1].copy_(step_out)
             pick(t, logits.float())
             t += 1
@@ -352,7 +365,7 @@ class HipGenerate:
         n = max(n, 1)
         return GenerateResult(prompt, answer[:, :, :n - 1], sequences[:, :S + n], lengths)
 
-    def _generate_hip_head(self, prompt, cache, ids, W, penalty, eos, pad, T, rows, last, graph, check_every):
+    def _generate_hip_head(self, prompt, cache, ids, W, penalty, eos, pad, T, rows, last, graph, check_every, w8=False):
         """generate()'s loop with the head kernels: every word of the loop's state lives in buffers that stay with the cache, so that the
         captured step (gather, decode_step, the copy into the answer at the device counter's column, both head kernels) replays."""
         from . import qwen_head_ops as HO
@@ -375,6 +388,10 @@ class HipGenerate:
             st["h_done"] = torch.zeros((B,), device=dev, dtype=torch.uint8)
             st["h_len"] = torch.zeros((B,), device=dev, dtype=torch.long)
             st["h_eos"] = torch.tensor(eos, device=dev, dtype=torch.long) if eos else None
+        hgraphs = st.setdefault("hgraph", {})   # w8 -> graph: a captured step holds its weights by pointer
+        if hgraphs and st.get("h_w8_pack") is not self.stack._w8:    # ... and a new pack is new pointers
+            hgraphs.pop(True, None)
+        st["h_w8_pack"] = self.stack._w8
         token, step_out, abuf, seq, seen, ws = st["h_token"], st["h_out"], st["h_answer"], st["h_seq"], st["h_seen"], st["h_ws"]
         step, base, done, lengths, eos_t = st["h_step"], st["h_base"], st["h_done"], st["h_len"], st["h_eos"]
         seq.fill_(pad)
@@ -390,7 +407,7 @@ class HipGenerate:
             HO.select(ws, step, token, seq, lengths, done, pad, V, eos=eos_t, seen=seen)
 
         def one_step():
-            self.stack.decode_step(cache, input_ids=token, out=step_out)
+            self.stack.decode_step(cache, input_ids=token, out=step_out, w8=w8)
             abuf.index_copy_(2, step.long() - base, step_out.unsqueeze(2))
             pick(step_out[:, -1])
 
@@ -401,21 +418,21 @@ class HipGenerate:
                 break
             if not graph:
                 one_step()
-            elif "hgraph" not in st and not st.get("hwarm"):
+            elif w8 not in hgraphs and w8 not in st.setdefault("hwarm", set()):
                 side = torch.cuda.Stream()                         # the warm-up a capture needs
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
                     one_step()
                 torch.cuda.current_stream().wait_stream(side)
-                st["hwarm"] = True
+                st["hwarm"].add(w8)
             else:
-                if "hgraph" not in st:
+                if w8 not in hgraphs:
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g):
                         one_step()
                     cache.steps -= 1                               # (a capture runs nothing: the replay below is this step)
-                    st["hgraph"] = g
-                st["hgraph"].replay()
+                    hgraphs[w8] = g
+                hgraphs[w8].replay()
                 cache.steps += 1
             t += 1
         n = int(lengths.max()) if eos_t is not None else T                # (tokens after every sample's end are dropped: one host read)

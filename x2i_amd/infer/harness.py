@@ -96,6 +96,11 @@ def build_parser(family):
                         "the generation_config cannot move an argmax and are dropped, any other logits processor is refused by name.  A token is "
                         "the argmax of f32 logits that are not rounded to bf16, so where the top two logits lie within one bf16 ulp it can "
                         "differ from the torch head's; Qwen2.5-VL only")
+    p.add_argument("--hip_w8", action="store_true",
+                   help="with --hip_generate: run the four linears of every layer of a decode step on e4m3 weights with one f32 scale per "
+                        "output row (Qwen2DecoderStack.pack_w8, x2i_amd/qwen_decode_w8_ops.py): half the weight bytes per generated token; "
+                        "bf16 activations, f32 sums.  The prompt pass and the lm_head stay bf16, and the bf16 weights are kept (about 6.5 GB "
+                        "more for the 7B decoder).  The generated tokens can differ from the bf16 steps'; Qwen2.5-VL only")
     p.add_argument("--decode", action="store_true", help="with --synthetic: also run the (random-weight) VAE decoder and save images")
     return p
 

@@ -14,7 +14,9 @@ from .harness import Harness, SyntheticConditioner, build_parser, stack_hidden_s
 class MultiTurnConditioner:
     """model / processor: hand in loaded ones (a test's tiny model and stub processor) and `path` is not read."""
 
-    def __init__(self, path, device, hip_generate=False, hip_head=False, model=None, processor=None):
+    def __init__(self, path, device, hip_generate=False, hip_head=False, model=None, processor=None, hip_w8=False):
+        if hip_w8 and not hip_generate:         # (before the checkpoint is read)
+            raise ValueError("--hip_w8 runs the decode steps of --hip_generate's loop on e4m3 weights: not without --hip_generate")
         if model is None or processor is None:
             from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
             model = model if model is not None else Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
@@ -28,7 +30,7 @@ class MultiTurnConditioner:
         if hip_generate:
             from ..handoff import HipGenerate
             HipGenerate.refuse_sampling(self.model.generation_config)
-            self.generate = HipGenerate(self.model, hip_head=hip_head)
+            self.generate = HipGenerate(self.model, hip_head=hip_head, w8=hip_w8)
 
     @torch.no_grad()
     def __call__(self, images=None, text_prompt=None, **_):
@@ -90,7 +92,7 @@ def main(argv=None):
     torch.cuda.set_device(device)
     if args.synthetic:
         return synthetic_turns(args, kind, device)
-    cond = MultiTurnConditioner(args.qwen_path, device, hip_generate=args.hip_generate, hip_head=args.hip_head)
+    cond = MultiTurnConditioner(args.qwen_path, device, hip_generate=args.hip_generate, hip_head=args.hip_head, hip_w8=args.hip_w8)
     h = Harness(args, kind, lambda **kw: cond(**kw)[0], device)
     turn = 0
     while True:

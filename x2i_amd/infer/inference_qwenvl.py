@@ -14,7 +14,10 @@ class QwenVLConditioner:
     """Qwen2_5_VLForConditionalGeneration prompt pass; inputs padded to 512 tokens, images resized to 128x128, videos at
     1 fps / 128*128 pixels, generate(max_new_tokens=128, output_hidden_states=True) -- infer/inference_qwenvl.py:136-180."""
 
-    def __init__(self, path, device, use_answer=False, prefill_only=True, hip_decoder=False, hip_vision=False, hip_generate=False, hip_head=False):
+    def __init__(self, path, device, use_answer=False, prefill_only=True, hip_decoder=False, hip_vision=False, hip_generate=False, hip_head=False,
+                 hip_w8=False):
+        if hip_w8 and not hip_generate:         # (before the checkpoint is read)
+            raise ValueError("--hip_w8 runs the decode steps of --hip_generate's loop on e4m3 weights: not without --hip_generate")
         from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
         self.model = Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
         self.processor = AutoProcessor.from_pretrained(path)
@@ -34,7 +37,7 @@ class QwenVLConditioner:
                 raise ValueError("--hip_generate runs the prompt pass on the HIP path itself: not together with --hip_decoder")
             from ..handoff import HipGenerate
             HipGenerate.refuse_sampling(self.model.generation_config)
-            self.generate = HipGenerate(self.model, hip_head=hip_head)
+            self.generate = HipGenerate(self.model, hip_head=hip_head, w8=hip_w8)
         elif prefill_only and not use_answer:
             from ..handoff import HiddenStateSlab, HipPrefill, find_decoder
             # hip_decoder: the same one forward with the decoder stack itself on the HIP path (x2i_amd/qwen.py)
@@ -108,7 +111,8 @@ def main(argv=None):
     torch.cuda.set_device(device)
     cond = SyntheticConditioner(kind, device) if args.synthetic else QwenVLConditioner(args.qwen_path, device, args.use_answer, prefill_only=not args.full_generate,
                                                                                             hip_decoder=args.hip_decoder, hip_vision=args.hip_vision,
-                                                                                            hip_generate=args.hip_generate, hip_head=args.hip_head)
+                                                                                            hip_generate=args.hip_generate, hip_head=args.hip_head,
+                                                                                            hip_w8=args.hip_w8)
     Harness(args, kind, cond, device).run_tasks(tasks(args))
 
 

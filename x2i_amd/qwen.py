@@ -31,7 +31,9 @@ Spad = cap -- and decode_step(cache, ...), one token per sample, eight launches 
   residual), rms_rows, decode_linear (gate|up with the SwiGLU gate), decode_linear (down_proj + residual -> the next entry of the output)
 The cache layout: a step appends at PHYSICAL slot k_hi[b] -- for a right-padded prompt the first padding slot -- so the valid keys stay one
 contiguous run under either padding; the token's POSITION comes from the RoPE table of the cache's next position, never from the slot.
-forward itself stays prefill only.
+forward itself stays prefill only.  pack_w8() adds e4m3 copies of a layer's four decode weights (one f32 scale per output row) and
+decode_step(..., w8=True) runs its four decode_linear launches on them (include/x2i_qwen_decode_w8.h): half the weight bytes per token; the
+prompt pass keeps the bf16 weights.
 """
 import torch
 import torch.nn as nn
@@ -191,6 +193,35 @@ class Qwen2DecoderStack(PackedModule):
             return r if n.startswith("embed_tokens") else r * p.shape[1] ** -0.5
 
         self._init_random(seed, rule)
+        return self.pack_()
+
+    # ------------------------------------------------------------------ e4m3 weights of the decode steps
+    _w8 = None      # per layer {"qkv", "o", "gu", "down"} -> (codes e4m3 [N, K], scale f32 [N]); None before pack_w8() and after the weights changed
+
+    @torch.no_grad()
+    def pack_w8(self):
+        """Quantises the four decode weights of every layer -- the fused q|k|v, o_proj, the fused gate|up and down_proj -- to OCP e4m3 with
+        one f32 scale per output row (ops.quantize_rows_fp8 on the device: scale = amax / 448; an all-zero row gets scale 1 and codes 0,
+        so it decodes to zeros) for decode_step(w8=True), which then streams half the weight bytes per token.  Biases, norms, embed_tokens
+        (and the surrounding model's lm_head) stay bf16.  The bf16 weights STAY: the prompt pass is compute-bound and runs on them, so the
+        pack costs memory on top -- one byte per element of the four matrices plus 4 bytes per row, about 6.5 GB for the 7B decoder
+        (28 layers of 233 M elements).  _apply, load_state_dict and init_random_ drop the pack; the next pack_w8() rebuilds it."""
+        c = self.config
+        if c.hidden_size % 16 or c.intermediate_size % 16:
+            raise ValueError("x2i_amd Qwen2DecoderStack.pack_w8: hidden_size and intermediate_size must be multiples of 16 (a lane's 16-byte "
+                             "load is 16 e4m3 weights)")
+        q = ops.quantize_rows_fp8
+        self._w8 = [dict(qkv=q(self._fused["%d.qkv.w" % i]), o=q(layer.self_attn.o_proj.weight), gu=q(self._fused["%d.gu" % i]),
+                         down=q(layer.mlp.down_proj.weight)) for i, layer in enumerate(self.layers)]
+        return self
+
+    def _moved(self, fn):
+        super()._moved(fn)
+        self._w8 = None
+
+    def pack_(self):
+        """The weights were written in place: the e4m3 pack is stale, and only pack_w8() makes it again"""
+        self._w8 = None
         return self
 
     # ------------------------------------------------------------------ workspace
@@ -324,7 +355,7 @@ class Qwen2DecoderStack(PackedModule):
         return self._prompt_pass(cache, inputs_embeds, input_ids, attention_mask, position_ids, check_mask, merge, embed_scale)
 
     @torch.no_grad()
-    def decode_step(self, cache, inputs_embeds=None, input_ids=None, out=None):
+    def decode_step(self, cache, inputs_embeds=None, input_ids=None, out=None, w8=False):
         """One token per sample against the cache: inputs_embeds bf16 [B, 1, H] (or [B, H]) or input_ids [B, 1] (or [B]) -> the hidden states
         bf16 [B, C, 1, H] of that token (HF convention, as forward).  out: a [B, C, H] view to write instead, e.g. column t of a caller's
         [B, C, T, H] answer slab, slab[:, :, t] (last stride 1, H-rows 16-byte aligned); it IS the residual stream, no copy.
@@ -332,8 +363,13 @@ class Qwen2DecoderStack(PackedModule):
         the one run [k_lo, k_hi) under either padding; the position comes from the RoPE table of the cache's next position, not from the slot.
         k_hi and the position then advance ON THE DEVICE: no host read, and after the first step no allocation but the output, so a step can
         be captured in a graph and replayed (a replay does not pass through here: its caller counts the steps, cache.steps).  Launches per
-        layer: rms, qkv linear, rope_append, attention, o_proj linear + residual, rms, gate|up linear with the gate, down linear + residual."""
+        layer: rms, qkv linear, rope_append, attention, o_proj linear + residual, rms, gate|up linear with the gate, down linear + residual.
+        w8=True: the four linears of each layer read the e4m3 weights of pack_w8() (qwen_decode_w8_ops.linear_w8); everything else is
+        unchanged.  Without a pack it raises ValueError."""
         from . import qwen_decode_ops as qd
+        if w8 and self._w8 is None:
+            raise ValueError("x2i_amd Qwen2DecoderStack.decode_step: w8=True needs the e4m3 weights; call pack_w8() first (and again after the "
+                             "weights were loaded, moved or re-initialised)")
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("Qwen2DecoderStack: pass exactly one of input_ids and inputs_embeds")
         if not isinstance(cache, Qwen2DecodeCache) or cache.owner() is not self:
@@ -366,18 +402,23 @@ class Qwen2DecoderStack(PackedModule):
         X1, X2, NRM, QKV, Qd, ATT, G, ws, slot, k_lo, k_hi = (cache.X1, cache.X2, cache.NRM, cache.QKV, cache.Qd, cache.ATT, cache.G, cache.ws,
                                                               cache.slot, cache.k_lo, cache.k_hi)
         sb, sc, scale = out.stride(0), out.stride(1), dk ** -0.5
+        if w8:
+            from .qwen_decode_w8_ops import linear_w8
+            lin = lambda i, nm, X, W, bias=None, **kw: linear_w8(X, self._w8[i][nm][0], self._w8[i][nm][1], bias, **kw)
+        else:
+            lin = lambda i, nm, X, W, bias=None, **kw: qd.linear(X, W, bias, **kw)
         for i, layer in enumerate(self.layers):
             t5_ops.rms_rows(out[:, i], layer.input_layernorm.weight, eps, out=NRM, rows=B, ldx=sb)
-            qd.linear(NRM, self._fused["%d.qkv.w" % i], self._fused["%d.qkv.b" % i], out=QKV)
+            lin(i, "qkv", NRM, self._fused["%d.qkv.w" % i], self._fused["%d.qkv.b" % i], out=QKV)
             qd.rope_append(QKV, cos, sin, slot, Qd, cache.K[i], cache.VT[i], B, Hq, Hkv, cap, dk)
             qd.attention(Qd, cache.K[i], cache.VT[i], k_lo, k_hi, ATT, ws, B, Hq, Hkv, cap, dk, scale)
-            qd.linear(ATT, layer.self_attn.o_proj.weight, res=out, res_offset=i * sc, ldr=sb, out=X1)
+            lin(i, "o", ATT, layer.self_attn.o_proj.weight, res=out, res_offset=i * sc, ldr=sb, out=X1)
             t5_ops.rms_rows(X1, layer.post_attention_layernorm.weight, eps, out=NRM)
-            qd.linear(NRM, self._fused["%d.gu" % i], gate=True, out=G)
+            lin(i, "gu", NRM, self._fused["%d.gu" % i], gate=True, out=G)
             if i + 1 < L:
-                qd.linear(G, layer.mlp.down_proj.weight, res=X1, out=out, y_offset=(i + 1) * sc, ldy=sb, B=B, N=D)
+                lin(i, "down", G, layer.mlp.down_proj.weight, res=X1, out=out, y_offset=(i + 1) * sc, ldy=sb, B=B, N=D)
             else:
-                qd.linear(G, layer.mlp.down_proj.weight, res=X1, out=X2)
+                lin(i, "down", G, layer.mlp.down_proj.weight, res=X1, out=X2)
         t5_ops.rms_rows(X2, self.norm.weight, eps, out=out[:, L], rows=B, ldy=sb)
         cache.steps += 1
         return out4
