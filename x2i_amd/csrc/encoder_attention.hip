@@ -1,6 +1,7 @@
 // The one flash-attention kernel of the encoder extensions: T5's relative-position-bias attention (include/x2i_t5.h), the causal attention
 // of the CLIP text encoder and the Qwen2 decoder prefill (include/x2i_clip.h, include/x2i_qwen.h) and the segmented attention of the
-// Qwen2.5-VL vision tower (include/x2i_vit.h).  The extern "C" entry points stay in t5.hip, clip.hip, qwen.hip and vit.hip and come here
+// Qwen2.5-VL vision tower (include/x2i_vit.h); the Qwen2 prompt extension's attention over a kept cache (include/x2i_qwen_extend.h) is CAUSAL
+// with a first row.  The extern "C" entry points stay in t5.hip, clip.hip, qwen.hip, vit.hip and qwen_extend.hip and come here
 // through the launchers at the end (x2i_kernels.h).  bf16 in and out, f32 arithmetic.
 //
 // The mapping is that of attention.hip (its 4-wave plain-HIP kernel) with the head width as a template parameter
@@ -42,6 +43,18 @@
 //
 // CAUSAL_PLAIN (CLIP, 64-wide heads): CAUSAL with rep = 1 and the range [0, S) known at compile time; the same values bit for bit
 //
+// CAUSAL_EXT (the Qwen2 prompt extension, include/x2i_qwen_extend.h): CAUSAL in absolute rows with a first row.  The n query rows row0 ..
+// row0 + n - 1 of a cache that already holds the keys before them; S = row0 + n, khi = S, and row0 travels in the kernel argument R, which
+// only RELBIAS reads otherwise, so that the other instantiations' argument list is what it was
+//   * the grid covers the 128-row query blocks that intersect [row0, S): block qt of the launch is block row0 / 128 + qt of the rows
+//   * a wave computes only when one of its rows is live (q0 + 31 >= row0); a row is stored iff row0 <= q < S, at output row q - row0
+//   * the defer-max test is per wave, so what the dead rows of a computing wave hold decides roundings of the live ones: they take the Q of
+//     the nearest live row (rows < row0 that of row0, rows >= S that of S - 1) and no stale row of Q is read.  A dead row >= S is then row
+//     S - 1 again, score for score; a dead row < row0 sees a prefix of row0's counted keys.  A live row's result is a function of the
+//     chunk's Q rows and of the K / V^T slots [klo, S) alone
+//   * a wave whose 32 rows are all >= row0 walks and masks exactly as CAUSAL does at S = row0 + n, Spad = cap, khi = S: the same values bit for
+//     bit wherever that launch's own rows >= S do not move a rescale (they read Q rows >= S, which this mode does not)
+//
 // SEGMENT (the Qwen2.5-VL vision tower): bidirectional, a key range [rlo, rhi) per QUERY ROW (device memory [B][S], clamped into [0, S];
 // [0, S) without the arrays): the windows and frames of one packed sequence, whose boundaries fall anywhere inside a tile, a wave or a
 // workgroup.  CAUSAL's scale, M_FLOOR and zero rows
@@ -62,7 +75,7 @@
 
 namespace {
 
-enum { RELBIAS = 0, CAUSAL = 1, CAUSAL_PLAIN = 2, SEGMENT = 3 };
+enum { RELBIAS = 0, CAUSAL = 1, CAUSAL_PLAIN = 2, SEGMENT = 3, CAUSAL_EXT = 4 };
 
 // DW: the head's width of data inside rows of DK elements (SEGMENT's 80-wide heads stored 128 wide); DW == DK everywhere else
 template <int DK, int MODE, int DW = DK>
@@ -94,10 +107,11 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
     const int T = gridDim.x, q = T >> 3, r = T & 7, xcd = bid & 7, idx = bid >> 3;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
-  const int qt = bid % nqt, h = (bid / nqt) % H, b = bid / (nqt * H);
+  [[maybe_unused]] const int row0 = MODE == CAUSAL_EXT ? R : 0;   // CAUSAL_EXT: the first live row
+  const int qt = bid % nqt + (MODE == CAUSAL_EXT ? row0 / 128 : 0), h = (bid / nqt) % H, b = bid / (nqt * H);
   const int q0 = qt * 128 + wave * 32;
   const long long bh = (long long)b * H + h;
-  constexpr bool RANGED = MODE == CAUSAL;   // grouped heads and a key range per sample
+  constexpr bool RANGED = MODE == CAUSAL || MODE == CAUSAL_EXT;   // grouped heads and a key range per sample
   long long bg = bh;   // the key/value head
   if constexpr (RANGED) bg = (long long)b * (H / rep) + h / rep;   // repeat_kv: query head h reads key/value head h / rep
   const bf16_t* Qh = Q + bh * Spad * DK;
@@ -149,7 +163,8 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
   // ---- Q fragments (B operand of S^T = K Q^T): lane holds Q[q0+li][ds*16 + hi*8 .. +8]; rows past Spad (Spad % 128 != 0) read the last row
   bf16x8_t qf[NDS];
   {
-    const int qrow = min(q0 + li, Spad - 1);
+    int qrow = min(q0 + li, Spad - 1);
+    if constexpr (MODE == CAUSAL_EXT) qrow = min(max(q0 + li, row0), S - 1);   // a dead row takes the nearest live row's Q
 #pragma unroll
     for (int ds = 0; ds < NDS; ++ds) qf[ds] = *(const bf16x8_t*)(Qh + (long long)qrow * DK + ds * 16 + hi * 8);
   }
@@ -207,7 +222,7 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
     t_lo = klo / KVB;
     const int t_hi = (min(min(S, qt * 128 + 128), khi) - 1) / KVB;
     ntiles = khi > klo ? t_hi - t_lo + 1 : 0;
-    t_wave = (q0 < S && q0 + 31 >= klo) ? q0 / KVB : -1;
+    t_wave = (q0 < S && q0 + 31 >= klo && (MODE != CAUSAL_EXT || q0 + 31 >= row0)) ? q0 / KVB : -1;
     qlim = min(q, khi - 1);
   }
 
@@ -240,6 +255,7 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
   // (their accumulators are still 0; 0 * finite V^T is 0 in the rows of a computing wave)
   const float inv = (MODE == RELBIAS || l_run > 0.f) ? 1.f / l_run : 0.f;
   bf16_t* orow = O + (long long)b * o_bs + (long long)q * ldo + h * DW;
+  if constexpr (MODE == CAUSAL_EXT) orow -= (long long)row0 * ldo;   // output row q - row0; only the rows row0 <= q < S are written
   if ((((uintptr_t)O) & 15) == 0 && (ldo & 7) == 0 && (o_bs & 7) == 0) {
     // half-wave exchange: two 8-byte fragments of neighbouring d-groups become one 16-byte store per lane
 #pragma unroll
@@ -253,9 +269,9 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
         const uint32_t b1 = pack_bf16x2(oacc[db][4 * g + 6] * inv, oacc[db][4 * g + 7] * inv);
         const auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
         const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-        if (q < S) *(uint4*)(orow + db * 32 + 8 * (g + hi)) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+        if (q < S && (MODE != CAUSAL_EXT || q >= row0)) *(uint4*)(orow + db * 32 + 8 * (g + hi)) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
       }
-  } else if (q < S) {
+  } else if (q < S && (MODE != CAUSAL_EXT || q >= row0)) {
 #pragma unroll
     for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -271,12 +287,13 @@ __global__ __launch_bounds__(256, 2) void encoder_attn_kernel(const bf16_t* __re
 template <int DK, int MODE, int DW = DK>
 int launch(const char* what, const void* Q, const void* K, const void* VT, const float* tab, const int* k_lo, const int* k_hi, void* O, int B, int H,
            int rep, int S, int Spad, int R, float scale2, int ldo, long long o_bs, hipStream_t stream) {
+  // R: RELBIAS's clamp distance; CAUSAL_EXT's first row (the grid is the query blocks from that row's on)
   constexpr int TILES = 2 * 2 * KVB * DK * 2;
   constexpr int TAIL = MODE == SEGMENT ? 32 : 0;   // SEGMENT: the four waves' key ranges
   const int rc = x2i_ensure_dynamic_smem((const void*)encoder_attn_kernel<DK, MODE, DW>, TILES + TAIL + (MODE == RELBIAS ? (2 * RELBIAS_RMAX + 2) * 4 : 0));
   if (rc) return rc;
   const size_t shm = TILES + TAIL + (MODE == RELBIAS ? (size_t)((2 * R + 1 + 3) & ~3) * 4 : 0);
-  const dim3 grid((unsigned)(((S + 127) / 128) * H * B));
+  const dim3 grid((unsigned)(((S + 127) / 128 - (MODE == CAUSAL_EXT ? R / 128 : 0)) * H * B));
   hipLaunchKernelGGL((encoder_attn_kernel<DK, MODE, DW>), grid, dim3(256), shm, stream, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)VT, tab, k_lo,
                      k_hi, (bf16_t*)O, H, rep, S, Spad, R, scale2, ldo, o_bs, B);
   return x2i_check_launch(what);
@@ -313,6 +330,15 @@ int x2i_launch_encoder_attention_causal(const void* Q, const void* K, const void
   const char* what = "qwen_attention";
   if (dk == 64) return launch<64, CAUSAL>(what, Q, K, VT, nullptr, k_lo, k_hi, O, B, Hq, Hq / Hkv, S, Spad, 0, scale * LOG2E, ldo, o_bs, stream);
   return launch<128, CAUSAL>(what, Q, K, VT, nullptr, k_lo, k_hi, O, B, Hq, Hq / Hkv, S, Spad, 0, scale * LOG2E, ldo, o_bs, stream);
+}
+
+// The Qwen2 prompt extension: rows row0 .. row0 + n - 1 of a cache of cap slots per head; k_lo [B] or null
+int x2i_launch_encoder_attention_causal_ext(const void* Q, const void* K, const void* VT, const int* k_lo, void* O, int B, int Hq, int Hkv, int row0,
+                                            int n, int cap, int dk, float scale, int ldo, long long o_bs, hipStream_t stream) {
+  const char* what = "qwen_extend_attention";
+  if (dk == 64)
+    return launch<64, CAUSAL_EXT>(what, Q, K, VT, nullptr, k_lo, nullptr, O, B, Hq, Hq / Hkv, row0 + n, cap, row0, scale * LOG2E, ldo, o_bs, stream);
+  return launch<128, CAUSAL_EXT>(what, Q, K, VT, nullptr, k_lo, nullptr, O, B, Hq, Hq / Hkv, row0 + n, cap, row0, scale * LOG2E, ldo, o_bs, stream);
 }
 
 // The CLIP text encoder's launch (64-wide ungrouped heads, the whole prefix) is short enough for CAUSAL's range and group arithmetic to show:

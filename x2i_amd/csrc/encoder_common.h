@@ -1,4 +1,4 @@
-// Pieces the encoder extension files share (t5.hip, clip.hip, qwen.hip, vit.hip, encoder_attention.hip): the attention kernel's constants and its
+// Pieces the encoder extension files share (t5.hip, clip.hip, qwen.hip, qwen_extend.hip, vit.hip, encoder_attention.hip): the attention kernel's constants and its
 // LDS-DMA load, the bf16 chunk unpacker, the V -> V^T tile transposer of the head-split kernels, the rotate-half RoPE head split of qwen.hip and vit.hip and the row-chunk activation kernel
 // behind the gated GELU, SwiGLU and quick-GELU entry points.  Other .hip files keep private helpers of the same names in their own anonymous
 // namespaces, so these stay out of x2i_common.h and stand in the anonymous namespace too: every includer gets its own copy, and a file that has
@@ -66,6 +66,25 @@ __device__ __forceinline__ void v_tile_to_vt(const bf16_t* __restrict__ v, long 
 }
 
 // ------------------------------------------------------------------------------------------------------------------- RoPE + head split
+// Eight rotate-half pairs (x[d], x[d + half]), d = 0 .. 7 from src, against eight entries of the half tables: lo = x1 cos - x2 sin, up = x2 cos + x1 sin,
+// packed bf16 pairs.  One rounding: both products and their sum stay f32 (the library rounds each product and the sum to bf16).
+__device__ __forceinline__ void rope_rotate8(const bf16_t* __restrict__ src, int half, const float* __restrict__ cp, const float* __restrict__ sp,
+                                             uint32_t (&lo)[4], uint32_t (&up)[4]) {
+  float x1[8], x2[8];
+  unpack8(*(const uint4*)src, x1);
+  unpack8(*(const uint4*)(src + half), x2);
+  const float4 c0 = *(const float4*)cp, c1 = *(const float4*)(cp + 4), t0 = *(const float4*)sp, t1 = *(const float4*)(sp + 4);
+  const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+  const float ss[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    lo[j >> 1] = pack_bf16x2(__fsub_rn(__fmul_rn(x1[j], cc[j]), __fmul_rn(x2[j], ss[j])),
+                             __fsub_rn(__fmul_rn(x1[j + 1], cc[j + 1]), __fmul_rn(x2[j + 1], ss[j + 1])));
+    up[j >> 1] = pack_bf16x2(__fadd_rn(__fmul_rn(x2[j], cc[j]), __fmul_rn(x1[j], ss[j])),
+                             __fadd_rn(__fmul_rn(x2[j + 1], cc[j + 1]), __fmul_rn(x1[j + 1], ss[j + 1])));
+  }
+}
+
 // The body of the kernels behind x2i_qwen_rope_split_bf16 and x2i_vit_rope_split_bf16, 256 threads, grid (64-token tiles, Hq + Hkv, B).
 // One workgroup per (64-token tile, head, sample); heads 0 .. Hq-1 are query heads, Hq .. Hq+Hkv-1 key/value heads.  A work item rotates
 // eight pairs (x[d], x[d + dk/2]), d = 8c .. 8c+7: two 16-byte loads of the row, two 32-byte pieces of each half table, two 16-byte stores.
@@ -89,21 +108,8 @@ __device__ __forceinline__ void rope_split_body(const bf16_t* __restrict__ qkv, 
     const bf16_t* src = qkv + ((long long)b * S + s) * ld + col + ch * 8;
     const float* cp = cs + ((long long)b * S + s) * half + ch * 8;
     const float* sp = sn + ((long long)b * S + s) * half + ch * 8;
-    float x1[8], x2[8];
-    unpack8(*(const uint4*)src, x1);
-    unpack8(*(const uint4*)(src + half), x2);
-    const float4 c0 = *(const float4*)cp, c1 = *(const float4*)(cp + 4), t0 = *(const float4*)sp, t1 = *(const float4*)(sp + 4);
-    const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-    const float ss[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
     uint32_t lo[4], up[4];
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-      // one rounding: both products and their sum stay f32 (the library rounds each product and the sum to bf16)
-      lo[j >> 1] = pack_bf16x2(__fsub_rn(__fmul_rn(x1[j], cc[j]), __fmul_rn(x2[j], ss[j])),
-                               __fsub_rn(__fmul_rn(x1[j + 1], cc[j + 1]), __fmul_rn(x2[j + 1], ss[j + 1])));
-      up[j >> 1] = pack_bf16x2(__fadd_rn(__fmul_rn(x2[j], cc[j]), __fmul_rn(x1[j], ss[j])),
-                               __fadd_rn(__fmul_rn(x2[j + 1], cc[j + 1]), __fmul_rn(x1[j + 1], ss[j + 1])));
-    }
+    rope_rotate8(src, half, cp, sp, lo, up);
     bf16_t* dst = dst_base + (long long)s * dkp + ch * 8;
     *(uint4*)dst = make_uint4(lo[0], lo[1], lo[2], lo[3]);
     *(uint4*)(dst + half) = make_uint4(up[0], up[1], up[2], up[3]);

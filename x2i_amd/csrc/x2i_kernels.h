@@ -53,7 +53,7 @@ int x2i_launch_attention_pp(const void* Q, const void* K, const void* VT, void* 
 int x2i_launch_attention_w4(const void* Q, const void* K, const void* VT, void* O, int B, int H, int S, int Spad, int ldo, long long o_bs,
                             float scale_log2, int prescale, hipStream_t stream, float* lse, int out8, float oinv);
 /* ---- the encoder extensions' attention (encoder_attention.hip), behind x2i_t5_attention_bf16 / x2i_clip_attention_bf16 / x2i_qwen_attention_bf16 /
-   x2i_vit_attention_bf16.
+   x2i_vit_attention_bf16 / x2i_qwen_extend_attention_bf16.
    The refusals those entry points share, under the entry point's name and in two parts, because each entry point has checks of its own (R, scale)
    between them: _shape is the Spad rule; _launch the work-item count and the alignment of the output rows and of Q, K, VT, where `heads` is the
    entry point's name for the query head count and `align_tail` what its alignment message says about k_lo / k_hi (null pointers where it has none) */
@@ -65,6 +65,9 @@ int x2i_launch_encoder_attention_relbias(const void* Q, const void* K, const voi
 int x2i_launch_encoder_attention_causal(const void* Q, const void* K, const void* VT, const int* k_lo, const int* k_hi, void* O, int B, int Hq,
                                         int Hkv, int S, int Spad, int dk, float scale, int ldo, long long o_bs,
                                         hipStream_t stream);   // Qwen2; dk 64 / 128; k_lo, k_hi both null: the whole prefix
+int x2i_launch_encoder_attention_causal_ext(const void* Q, const void* K, const void* VT, const int* k_lo, void* O, int B, int Hq, int Hkv, int row0,
+                                            int n, int cap, int dk, float scale, int ldo, long long o_bs,
+                                            hipStream_t stream);   // Qwen2 prompt extension; query rows row0 .. row0+n-1 of Q [B][Hq][cap][dk]; k_lo null: 0
 int x2i_launch_encoder_attention_causal_plain(const void* Q, const void* K, const void* VT, void* O, int B, int H, int S, int Spad, float scale,
                                               int ldo, long long o_bs, hipStream_t stream);   // CLIP; dk 64, ungrouped heads, the whole prefix
 int x2i_launch_encoder_attention_segment(const void* Q, const void* K, const void* VT, const int* row_lo, const int* row_hi, void* O, int B, int H,

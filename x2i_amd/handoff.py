@@ -173,6 +173,22 @@ def head_plan(processors):
     return 1.0 if penalty is None else penalty
 
 
+def _common_prefix(prev_ids, prev_valid, ids):
+    """common_prefix as a 0-dim int64 tensor on the ids' device: no host read"""
+    m = min(int(prev_valid), prev_ids.shape[1], ids.shape[1])
+    if prev_ids.shape[0] != ids.shape[0] or m < 1:
+        return torch.zeros((), device=ids.device, dtype=torch.long)
+    same = (prev_ids[:, :m].to(ids.device) == ids[:, :m]).all(0)
+    return same.long().cumprod(0).sum()
+
+
+def common_prefix(prev_ids, prev_valid, ids):
+    """-> P, a host int: the longest common prefix of the token ids prev_ids [B, >= prev_valid] and ids [B, S] over ALL samples (the first
+    column where any sample differs ends it), capped at prev_valid, the count of kept tokens that are valid, and at S.  Pure torch, works on
+    CPU tensors, one host read.  Another batch size gives 0."""
+    return int(_common_prefix(prev_ids, prev_valid, ids))
+
+
 class GenerateResult:
     """What HipGenerate.generate returns: prompt bf16 [B, C, S, H] (the prompt pass, HipPrefill's slab), answer bf16 [B, C, T - 1, H] (the
     decode passes: column t is the pass whose input is generated token t; the pass of the last token never runs, the HF convention),
@@ -202,9 +218,24 @@ class HipGenerate:
     With w8=True (off by default; per call generate(w8=...)) the four linears of every layer of a decode step read e4m3 weights with one
     f32 scale per output row (Qwen2DecoderStack.pack_w8, made once at first use and kept beside the bf16 weights, which the prompt pass
     still runs on): half the weight bytes per token.  The lm_head stays bf16 under either head.  The captured steps hold their weights by
-    pointer, so the graphs are kept per value of w8."""
+    pointer, so the graphs are kept per value of w8.
+    With keep_cache=True (off by default; per call generate(keep_cache=...)) the instance keeps what the previous call left -- its
+    sequences, the per-sample lengths, the decoder's position ids and the hidden rows cat(prompt, answer) along S, besides the cache itself
+    -- and a call whose prompt starts with those tokens runs only the rest of it: Qwen2DecoderStack.extend(cache, keep=P, ...) on rows
+    [P:] of the model's inputs_embeds / position_ids, P = common_prefix(...) over the valid tokens of the previous call, sequences[:, :S +
+    n - 1] (n the largest length: the pass of the last generated token never ran; passes after a sample's end token hold the pad token,
+    as the sequences do).  GenerateResult.prompt is then the kept rows, bit for bit what the earlier calls returned, followed by the new
+    rows.  Reuse needs the same B, no padding in either call (mask None or all ones), P >= 1, S - P >= 1 and the decoder's
+    position_ids[..., :P] equal to the kept ones; otherwise the call runs the whole prefill as today and `reuse_note` says why.  `reused`
+    is the last call's P (0: a whole prefill).  The extra cost of a reused turn is one host read.  The capacity is rounded up to a
+    multiple of 1024 slots instead of 64, so that cache and graphs survive several turns; a turn that does not fit gets a larger cache,
+    slots [0, P) of K / V^T copied over, and the captured graphs (which hold the old cache by pointer) are dropped.  forget() drops the
+    conversation; so does any call with keep_cache off.
+    THE CALLER'S PROMISE under keep_cache: a token match cannot see changed pixels or audio -- the placeholder ids of an image are the
+    same for every image -- so the features under a matching prefix must be unchanged from the previous call (a chat history whose
+    images never change, as inference_multi_turn's)."""
 
-    def __init__(self, model, check_mask=True, hip_head=False, w8=False):
+    def __init__(self, model, check_mask=True, hip_head=False, w8=False, keep_cache=False):
         from .qwen import Qwen2DecoderStack
         self.decoder = find_decoder(model)
         self.stack = Qwen2DecoderStack.from_hf(self.decoder)
@@ -213,8 +244,50 @@ class HipGenerate:
         self.check_mask = check_mask
         self.hip_head = hip_head
         self.w8 = w8
+        self.keep_cache = keep_cache
+        self.reused, self.reuse_note = 0, ""
         self.slab = self._cache = None
         self._state = {}
+        self._conv = None       # under keep_cache: what the previous call left (_remember)
+        self._keep = False      # this call's keep_cache
+
+    def forget(self):
+        """Drops the kept conversation: the next call runs its whole prompt"""
+        self._conv = None
+
+    def _reusable(self, B, S, ids, attention_mask, pos):
+        """-> (P, why not): how many leading slots of the kept conversation this call's prompt [B, S] can stand on.  One host read."""
+        conv = self._conv
+        if conv is None:
+            return 0, "no kept conversation"
+        if conv["B"] != B or ids is None or tuple(ids.shape) != (B, S):
+            return 0, "another batch size"
+        kept = conv["pos"]
+        if pos.dim() != kept.dim():
+            return 0, "other position axes"
+        m = min(conv["valid"], S)
+        one = torch.ones((), device=pos.device, dtype=torch.long)
+        p_pos = (pos[..., :m] == kept[..., :m]).reshape(-1, m).all(0).long().cumprod(0).sum()
+        full = one if attention_mask is None else (attention_mask != 0).all().long().to(pos.device)
+        P, p_pos, full, was_full = torch.stack((_common_prefix(conv["sequences"], conv["valid"], ids).to(pos.device), p_pos, full,
+                                                conv["unpadded"])).tolist()      # the one host read
+        if not (full and was_full):
+            return 0, "a padded batch"
+        if P < 1 or S - P < 1:
+            return 0, "no common prefix" if P < 1 else "nothing new after the common prefix"
+        if p_pos < P:
+            return 0, "the position ids under the common prefix changed"
+        return P, ""
+
+    def _remember(self, res):
+        """After a call under keep_cache: what the next one stands on"""
+        S, n = res.prompt.shape[2], res.sequences.shape[1] - res.prompt.shape[2]
+        dev = res.prompt.device
+        pos = torch.cat((self._pos_prompt, self._pos_next[..., None] + torch.arange(n - 1, device=dev)), -1)
+        hidden = torch.cat((res.prompt, res.answer), 2) if n > 1 else res.prompt
+        self._conv = dict(B=res.prompt.shape[0], sequences=res.sequences, valid=S + n - 1, lengths=res.lengths, pos=pos, hidden=hidden,
+                          unpadded=self._unpadded)
+        return res
 
     def _forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None, use_cache=None, **kw):
         from transformers.modeling_outputs import BaseModelOutputWithPast
@@ -229,12 +302,37 @@ class HipGenerate:
         B, S = (input_ids if input_ids is not None else inputs_embeds).shape[:2]
         # one cache stays resident, with the step captured on it: the next call at the same (B, cap) reuses both (a prefill resets the ranges
         # and positions; what older generations left in K / V^T outside the new ranges is finite, which is all the kernels ask)
-        key = (B, (S + self._new_tokens + 63) // 64 * 64)
+        unit = 1024 if self._keep else 64
+        key = (B, (S + self._new_tokens + unit - 1) // unit * unit)
+        P, conv = 0, None
+        if self._keep:
+            dev = self.stack.device
+            pos = torch.arange(S, device=dev)[None].expand(B, S) if position_ids is None else position_ids.to(dev)
+            if pos.dim() == 3 and pos.shape[0] == 4:
+                pos = pos[1:]
+            pos = pos.expand(*pos.shape[:-2], B, S)
+            P, self.reuse_note = self._reusable(B, S, self._ids, attention_mask, pos)
+            conv, self._conv = self._conv, None      # (the cache is rewritten from here on: a call that fails leaves no conversation)
+            self._pos_prompt = pos
+            self._unpadded = (torch.ones((), device=dev, dtype=torch.long) if attention_mask is None
+                              else (attention_mask != 0).all().long().to(dev))
+        self.reused = P
         if self._state.get("key") != key:
-            self._state = dict(key=key, cache=self.stack.new_cache(B, key[1]))
+            old = self._state.get("cache")
+            self._state = dict(key=key, cache=self.stack.new_cache(B, key[1]))     # (the captured graphs held the old cache by pointer)
+            if P:
+                self._state["cache"]._adopt(old, P)
         self._cache = self._state["cache"]
-        self.slab = self.stack.prefill(self._cache, inputs_embeds=inputs_embeds, input_ids=input_ids, attention_mask=attention_mask,
-                                       position_ids=position_ids, check_mask=self.check_mask)
+        if P:
+            cut = lambda t: None if t is None else t[:, P:]
+            new = self.stack.extend(self._cache, P, inputs_embeds=cut(inputs_embeds), input_ids=cut(input_ids), position_ids=pos[..., P:],
+                                    check=False)       # (the kept conversation is unpadded and reaches P: nothing to look up)
+            self.slab = torch.cat((conv["hidden"][:, :, :P], new), 2)
+        else:
+            self.slab = self.stack.prefill(self._cache, inputs_embeds=inputs_embeds, input_ids=input_ids, attention_mask=attention_mask,
+                                           position_ids=position_ids, check_mask=self.check_mask)
+        if self._keep:
+            self._pos_next = self._cache.pos.clone()
         return BaseModelOutputWithPast(last_hidden_state=self.slab[:, -1], past_key_values=None)
 
     @staticmethod
@@ -245,12 +343,13 @@ class HipGenerate:
 
     @torch.no_grad()
     def generate(self, model, max_new_tokens=128, eos_token_id=None, pad_token_id=None, logits_processor=None, graph=True, check_every=16,
-                 generation_config=None, hip_head=None, w8=None, **inputs):
+                 generation_config=None, hip_head=None, w8=None, keep_cache=None, **inputs):
         """-> GenerateResult.  inputs: the model's forward arguments of the prompt (input_ids required; attention_mask, pixel_values, ...).
         eos_token_id: an id, a list of ids or None (never stop early); pad_token_id: what follows a sample's end token (default: the first
         end token, else 0).  logits_processor: a list of callables (input_ids [B, len], scores f32 [B, V]) -> scores.  hip_head: None takes
         the constructor's; True needs a list that head_plan accepts.  w8: None takes the constructor's; True runs the decode steps on the
-        stack's e4m3 weights (packed at first use)."""
+        stack's e4m3 weights (packed at first use).  keep_cache: None takes the constructor's; True stands on what the previous call left
+        where the prompt allows it and keeps this call's for the next (the class docstring has the rules and the caller's promise)."""
         self.refuse_sampling(generation_config if generation_config is not None else getattr(model, "generation_config", None))
         if max_new_tokens < 1:
             raise ValueError("handoff.HipGenerate: max_new_tokens must be at least 1")
@@ -262,6 +361,10 @@ class HipGenerate:
         processors = list(logits_processor or [])
         hip_head = self.hip_head if hip_head is None else hip_head
         w8 = bool(self.w8 if w8 is None else w8)
+        self._keep, self._ids = bool(self.keep_cache if keep_cache is None else keep_cache), ids
+        self.reused, self.reuse_note = 0, ""
+        if not self._keep:
+            self._conv = None     # (this call's prefill resets the cache the conversation stood on)
         head = model.get_output_embeddings()
         if hip_head:       # every refusal comes before anything runs
             import inspect
@@ -297,7 +400,8 @@ class HipGenerate:
         rows = torch.arange(B, device=dev)
         last = (cache.k_hi - 1).long()                                   # the last valid token of each sample, under either padding
         if hip_head:
-            return self._generate_hip_head(prompt, cache, ids, head.weight, penalty, eos, pad, T, rows, last, graph, check_every, w8)
+            res = self._generate_hip_head(prompt, cache, ids, head.weight, penalty, eos, pad, T, rows, last, graph, check_every, w8)
+            return self._remember(res) if self._keep else res
         sequences = torch.full((B, S + T), pad, device=dev, dtype=torch.long)
         sequences[:, :S] = ids
         answer = torch.empty((B, C, max(T - 1, 0), H), device=dev, dtype=torch.bfloat16)
@@ -363,7 +467,8 @@ class HipGenerate:
             t += 1
         n = int(lengths.max()) if eos_t is not None else T                # (tokens after every sample's end are dropped: one host read)
         n = max(n, 1)
-        return GenerateResult(prompt, answer[:, :, :n - 1], sequences[:, :S + n], lengths)
+        res = GenerateResult(prompt, answer[:, :, :n - 1], sequences[:, :S + n], lengths)
+        return self._remember(res) if self._keep else res
 
     def _generate_hip_head(self, prompt, cache, ids, W, penalty, eos, pad, T, rows, last, graph, check_every, w8=False):
         """generate()'s loop with the head kernels: every word of the loop's state lives in buffers that stay with the cache, so that the

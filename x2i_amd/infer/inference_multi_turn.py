@@ -3,7 +3,8 @@
 chat history grows each turn, the model answers with max_new_tokens=64, and the conditioning is the prompt-pass hidden
 states concatenated along S with the generated-token hidden states (:132-141); 4 steps, 1024x1024, manual_seed(0).
 With --hip_generate a turn is one handoff.HipGenerate.generate call (the decoder stack on the HIP path over the prompt and the answer),
-with --hip_head its tokens are chosen on the HIP path too."""
+with --hip_head its tokens are chosen on the HIP path too, and with --hip_keep_cache a turn's prompt pass runs only the tokens that the
+history gained (HipGenerate(keep_cache=True): the key/value cache of the turns before stays)."""
 import time
 
 import torch
@@ -14,9 +15,11 @@ from .harness import Harness, SyntheticConditioner, build_parser, stack_hidden_s
 class MultiTurnConditioner:
     """model / processor: hand in loaded ones (a test's tiny model and stub processor) and `path` is not read."""
 
-    def __init__(self, path, device, hip_generate=False, hip_head=False, model=None, processor=None, hip_w8=False):
+    def __init__(self, path, device, hip_generate=False, hip_head=False, model=None, processor=None, hip_w8=False, keep_cache=False):
         if hip_w8 and not hip_generate:         # (before the checkpoint is read)
             raise ValueError("--hip_w8 runs the decode steps of --hip_generate's loop on e4m3 weights: not without --hip_generate")
+        if keep_cache and not hip_generate:
+            raise ValueError("--hip_keep_cache keeps the key/value cache of --hip_generate's loop between turns: not without --hip_generate")
         if model is None or processor is None:
             from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
             model = model if model is not None else Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
@@ -30,7 +33,7 @@ class MultiTurnConditioner:
         if hip_generate:
             from ..handoff import HipGenerate
             HipGenerate.refuse_sampling(self.model.generation_config)
-            self.generate = HipGenerate(self.model, hip_head=hip_head, w8=hip_w8)
+            self.generate = HipGenerate(self.model, hip_head=hip_head, w8=hip_w8, keep_cache=keep_cache)
 
     @torch.no_grad()
     def __call__(self, images=None, text_prompt=None, **_):
@@ -86,13 +89,19 @@ def synthetic_turns(args, kind, device):
 def main(argv=None):
     ap = build_parser("qwenvl")
     ap.add_argument("--turn_lengths", type=str, default=None, help="with --synthetic: comma-separated text lengths of the turns")
+    ap.add_argument("--hip_keep_cache", action="store_true",
+                    help="with --hip_generate: keep the key/value cache between turns and run only the tokens the history gained through the "
+                         "prompt pass (HipGenerate(keep_cache=True), Qwen2DecoderStack.extend); the history's images must not change")
     args = ap.parse_args(argv)
+    if args.hip_keep_cache and not args.hip_generate:      # (before a checkpoint is read)
+        raise ValueError("--hip_keep_cache keeps the key/value cache of --hip_generate's loop between turns: not without --hip_generate")
     kind = "qwen" + args.qwen_size
     device = "cuda:0"
     torch.cuda.set_device(device)
     if args.synthetic:
         return synthetic_turns(args, kind, device)
-    cond = MultiTurnConditioner(args.qwen_path, device, hip_generate=args.hip_generate, hip_head=args.hip_head, hip_w8=args.hip_w8)
+    cond = MultiTurnConditioner(args.qwen_path, device, hip_generate=args.hip_generate, hip_head=args.hip_head, hip_w8=args.hip_w8,
+                                keep_cache=args.hip_keep_cache)
     h = Harness(args, kind, lambda **kw: cond(**kw)[0], device)
     turn = 0
     while True:

@@ -31,7 +31,10 @@ Spad = cap -- and decode_step(cache, ...), one token per sample, eight launches 
   residual), rms_rows, decode_linear (gate|up with the SwiGLU gate), decode_linear (down_proj + residual -> the next entry of the output)
 The cache layout: a step appends at PHYSICAL slot k_hi[b] -- for a right-padded prompt the first padding slot -- so the valid keys stay one
 contiguous run under either padding; the token's POSITION comes from the RoPE table of the cache's next position, never from the slot.
-forward itself stays prefill only.  pack_w8() adds e4m3 copies of a layer's four decode weights (one f32 scale per output row) and
+forward itself stays prefill only.  extend(cache, keep, ...) runs a chunk of n new rows against a cache that holds the keys before them (a
+chat's next turn, chunked prefill): the prompt pass's launches at M = B * n with rope_split and the attention replaced by
+x2i_qwen_extend_rope_split_bf16 / x2i_qwen_extend_attention_bf16 (include/x2i_qwen_extend.h), which work in cache slots from `keep` on; the
+keys end at keep + n afterwards and decode_step goes on from there.  pack_w8() adds e4m3 copies of a layer's four decode weights (one f32 scale per output row) and
 decode_step(..., w8=True) runs its four decode_linear launches on them (include/x2i_qwen_decode_w8.h): half the weight bytes per token; the
 prompt pass keeps the bf16 weights.
 """
@@ -121,6 +124,7 @@ class Qwen2DecoderStack(PackedModule):
 
     def __init__(self, config=None, embed_tokens=None, device="cuda", dtype=torch.bfloat16, **kw):
         super().__init__(device)
+        self._xws = {}          # the extension's workspace of the resident (B, n): beside _ws, which a turn's extension must not evict
         f = config_fields(_FIELDS, config, kw, "Qwen2DecoderStack", extra=_rope_fields)
         if dtype != torch.bfloat16:
             raise ValueError("x2i_amd: the HIP path computes in bf16 (fp32 statistics/accumulation)")
@@ -218,6 +222,7 @@ class Qwen2DecoderStack(PackedModule):
     def _moved(self, fn):
         super()._moved(fn)
         self._w8 = None
+        self._xws = {}
 
     def pack_(self):
         """The weights were written in place: the e4m3 pack is stale, and only pack_w8() makes it again"""
@@ -241,6 +246,19 @@ class Qwen2DecoderStack(PackedModule):
                   G=torch.empty((B * S, F), **bf), arange=torch.arange(S, device=dev)[None].expand(B, S), rope={},
                   merge_err=torch.zeros((1,), device=dev, dtype=torch.int32))   # set by a plain input_ids pass that met an id outside the table
         self._ws = {(B, S): ws}  # keep one shape resident
+        return ws
+
+    def _extend_workspace(self, B, n):
+        ws = self._xws.get((B, n))
+        if ws is not None:
+            return ws
+        c = self.config
+        D, nq, nkv, F = c.hidden_size, c.num_attention_heads * c.head_dim, c.num_key_value_heads * c.head_dim, c.intermediate_size
+        bf = dict(device=self.device, dtype=torch.bfloat16)
+        ws = dict(X1=torch.empty((B * n, D), **bf), X2=torch.empty((B * n, D), **bf), NRM=torch.empty((B * n, D), **bf),
+                  QKV=torch.empty((B * n, nq + 2 * nkv), **bf), ATT=torch.empty((B * n, nq), **bf), HH=torch.empty((B * n, 2 * F), **bf),
+                  G=torch.empty((B * n, F), **bf), rope={}, merge_err=torch.zeros((1,), device=self.device, dtype=torch.int32))
+        self._xws = {(B, n): ws}  # keep one shape resident
         return ws
 
     # ------------------------------------------------------------------ forward
@@ -270,7 +288,7 @@ class Qwen2DecoderStack(PackedModule):
         if merge is not None and input_ids is None:
             raise ValueError("Qwen2DecoderStack: merge= goes with input_ids (with inputs_embeds the merge has been done)")
         c = self.config
-        D, dk, Hq, Hkv, F, eps, L = c.hidden_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads, c.intermediate_size, c.rms_norm_eps, len(self.layers)
+        D, dk, Hq, Hkv = c.hidden_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads
         nq, C = Hq * dk, len(self.layers) + 1
         B, S = (input_ids if input_ids is not None else inputs_embeds).shape[:2]
         if cache is not None and (cache.B != B or S + 1 > cache.cap):
@@ -288,8 +306,8 @@ class Qwen2DecoderStack(PackedModule):
             if not all_ones:
                 k_lo, k_hi = key_ranges(attention_mask)
         ws = self._workspace(B, S)
-        X1, X2, NRM, QKV, Q, K, VT, ATT, HH, G, Spad = (ws[k] for k in ("X1", "X2", "NRM", "QKV", "Q", "K", "VT", "ATT", "HH", "G", "Spad"))
-        dev = X1.device
+        QKV, Q, K, VT, ATT, Spad = (ws[k] for k in ("QKV", "Q", "K", "VT", "ATT", "Spad"))
+        dev = QKV.device
         if cache is not None:
             Q, Spad = cache.Q, cache.cap
         if position_ids is None:
@@ -315,16 +333,26 @@ class Qwen2DecoderStack(PackedModule):
         else:
             ops._req(inputs_embeds, torch.bfloat16, "inputs_embeds")
             slab[:, 0].copy_(inputs_embeds)
-        M, sbs, SD = B * S, C * S * D, S * D
         scale = dk ** -0.5
+        kv = (lambda i: (cache.K[i], cache.VT[i])) if cache is not None else (lambda i: (K, VT))
+        return self._layers(slab, ws, lambda i: qwen_ops.rope_split(QKV, cos, sin, Q, *kv(i), B, S, Spad, Hq, Hkv, dk),
+                            lambda i: qwen_ops.attention(Q, *kv(i), ATT, B, Hq, Hkv, S, Spad, dk, scale, nq, S * nq, k_lo, k_hi))
+
+    def _layers(self, slab, ws, rope_split, attention):
+        """The launches of every layer and the final norm over the rows of slab [B, C, S, D], whose entry 0 is written: the residual stream
+        goes through the slab as the module's docstring has it.  rope_split(i) and attention(i) are layer i's two launches that know where
+        Q, K and V^T live (a workspace, or a cache at a first slot): QKV -> Q, K, V^T and Q, K, V^T -> ATT.  ws: buffers for S rows."""
+        c = self.config
+        D, dk, Hq, F, eps, L = c.hidden_size, c.head_dim, c.num_attention_heads, c.intermediate_size, c.rms_norm_eps, len(self.layers)
+        X1, X2, NRM, QKV, ATT, HH, G = (ws[k] for k in ("X1", "X2", "NRM", "QKV", "ATT", "HH", "G"))
+        B, C, S = slab.shape[:3]
+        nq, M, sbs, SD = Hq * dk, B * S, C * S * D, S * D
         for i, layer in enumerate(self.layers):
-            if cache is not None:
-                K, VT = cache.K[i], cache.VT[i]
             for b in range(B):   # (the samples of slab[:, i] are C*S*D apart; the norm's rows have one stride)
                 t5_ops.rms_rows(slab[b, i], layer.input_layernorm.weight, eps, out=NRM[b * S:(b + 1) * S])
             ops.gemm(NRM, self._fused["%d.qkv.w" % i], self._fused["%d.qkv.b" % i], out=QKV, M=M)
-            qwen_ops.rope_split(QKV, cos, sin, Q, K, VT, B, S, Spad, Hq, Hkv, dk)
-            qwen_ops.attention(Q, K, VT, ATT, B, Hq, Hkv, S, Spad, dk, scale, nq, S * nq, k_lo, k_hi)
+            rope_split(i)
+            attention(i)
             ops.gemm(ATT, layer.self_attn.o_proj.weight, out=X1, M=S, batch=B, a_batch_stride=S * nq, c_batch_stride=SD, ldc=D,
                      res=slab, res_offset=i * SD, res_batch_stride=sbs, ldr=D)
             t5_ops.rms_rows(X1, layer.post_attention_layernorm.weight, eps, out=NRM)
@@ -353,6 +381,73 @@ class Qwen2DecoderStack(PackedModule):
         if not isinstance(cache, Qwen2DecodeCache) or cache.owner() is not self:
             raise ValueError("x2i_amd Qwen2DecoderStack.prefill: the cache must come from this stack's new_cache()")
         return self._prompt_pass(cache, inputs_embeds, input_ids, attention_mask, position_ids, check_mask, merge, embed_scale)
+
+    @torch.no_grad()
+    def extend(self, cache, keep, inputs_embeds=None, input_ids=None, position_ids=None, check=True, merge=None, embed_scale=1.0):
+        """A chunk of n new rows against a cache that holds the keys before them (a chat's next turn; chunked prefill) -> bf16 [B, C, n, H],
+        the hidden states of the new rows only, HF convention as forward.
+        keep: a host int, a SLOT index, the same for every sample: slots [0, keep) of the cache are kept, the chunk goes to slots keep ..
+        keep + n - 1, and what the cache held from keep on (decode passes past an end token, a longer old prompt) is dropped by setting
+        k_hi = keep + n on the device; k_lo stays.  Needs a prefilled cache, keep >= 1, n >= 1 and keep + n + 1 <= cap (prefill's rule).
+        check=True makes one host read of k_lo, k_hi and raises ValueError when a sample's k_hi < keep (a hole) or k_lo >= keep; False
+        skips it.  position_ids: those of the chunk, [B, n], or [3, B, n] / [4, B, n] for M-RoPE -- required, because the position is not
+        the slot.  Afterwards cache.pos is 1 + the largest position id of the chunk over all axes and cache.steps = keep + n; a
+        decode_step goes on from there, eager or replayed from a graph captured on this cache (it reads k_hi and pos from the device).
+        Per layer: the prompt pass's launches at M = B * n with x2i_qwen_extend_rope_split_bf16 / x2i_qwen_extend_attention_bf16
+        (include/x2i_qwen_extend.h) on cache.Q / K[i] / VT[i]; inputs_embeds, input_ids, merge and embed_scale as forward's, for the
+        chunk."""
+        from . import qwen_extend_ops as qx
+        if not isinstance(cache, Qwen2DecodeCache) or cache.owner() is not self:
+            raise ValueError("x2i_amd Qwen2DecoderStack.extend: the cache must come from this stack's new_cache()")
+        if cache.steps is None:
+            raise ValueError("x2i_amd Qwen2DecoderStack.extend: prefill(cache, ...) comes first")
+        if (input_ids is None) == (inputs_embeds is None):
+            raise ValueError("Qwen2DecoderStack: pass exactly one of input_ids and inputs_embeds")
+        if merge is not None and input_ids is None:
+            raise ValueError("Qwen2DecoderStack: merge= goes with input_ids (with inputs_embeds the merge has been done)")
+        if position_ids is None:
+            raise ValueError("x2i_amd Qwen2DecoderStack.extend: position_ids of the chunk are required (the position is not the slot)")
+        keep = int(keep)
+        if keep < 1:
+            raise ValueError("x2i_amd Qwen2DecoderStack.extend: keep = %d keeps nothing; a whole prompt is prefill's" % keep)
+        c = self.config
+        D, dk, Hq, Hkv, L = c.hidden_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads, len(self.layers)
+        B, n = (input_ids if input_ids is not None else inputs_embeds).shape[:2]
+        if cache.B != B or n < 1 or keep + n + 1 > cache.cap:
+            raise ValueError("x2i_amd Qwen2DecoderStack.extend: a chunk of [B, n] = [%d, %d] at slot keep = %d does not fit a cache of B = %d, "
+                             "cap = %d (n >= 1, keep + n + 1 <= cap)" % (B, n, keep, cache.B, cache.cap))
+        if position_ids.dim() == 3 and position_ids.shape[0] == 4:
+            position_ids = position_ids[1:]
+        if position_ids.dim() == 3 and c.mrope_section is None:
+            raise ValueError("x2i_amd Qwen2DecoderStack: three position axes need an mrope_section in the configuration")
+        if position_ids.dim() not in (2, 3) or tuple(position_ids.shape[-2:]) != (B, n):
+            raise ValueError("x2i_amd Qwen2DecoderStack.extend: position_ids must be [B, n] = [%d, %d], or [3, B, n] / [4, B, n] (got %s)"
+                             % (B, n, tuple(position_ids.shape)))
+        if check:
+            lo, hi = torch.stack((cache.k_lo, cache.k_hi)).tolist()
+            if min(hi) < keep:
+                raise ValueError("x2i_amd Qwen2DecoderStack.extend: keep = %d leaves a hole: a sample's keys end at slot %d" % (keep, min(hi)))
+            if max(lo) >= keep:
+                raise ValueError("x2i_amd Qwen2DecoderStack.extend: keep = %d keeps no key of a sample whose keys start at slot %d" % (keep, max(lo)))
+        ws = self._extend_workspace(B, n)
+        dev = ws["X1"].device
+        position_ids = position_ids.to(dev)
+        cos, sin = rope_tables(position_ids, dk, c.rope_theta, c.mrope_section, _scratch=ws["rope"])
+        cache._set_extension(keep, n, position_ids)
+        slab = torch.empty((B, L + 1, n, D), device=dev, dtype=torch.bfloat16)
+        if input_ids is not None:
+            if input_ids.device != dev:
+                raise ops._lib.X2IError("x2i_amd: input_ids must live on the model's device (got %s)" % input_ids.device)
+            if merge is not None:
+                merge.launch(slab[:, 0], input_ids, self.embed_tokens.weight, embed_scale)
+            else:
+                merge_ops.embed_merge(slab[:, 0], ws["merge_err"], ids=input_ids.contiguous(), table=self.embed_tokens.weight, scale=embed_scale)
+        else:
+            ops._req(inputs_embeds, torch.bfloat16, "inputs_embeds")
+            slab[:, 0].copy_(inputs_embeds)
+        QKV, ATT, nq, cap, scale = ws["QKV"], ws["ATT"], Hq * dk, cache.cap, dk ** -0.5
+        return self._layers(slab, ws, lambda i: qx.rope_split(QKV, cos, sin, cache.Q, cache.K[i], cache.VT[i], B, keep, n, cap, Hq, Hkv, dk),
+                            lambda i: qx.attention(cache.Q, cache.K[i], cache.VT[i], ATT, B, Hq, Hkv, keep, n, cap, dk, scale, nq, n * nq, cache.k_lo))
 
     @torch.no_grad()
     def decode_step(self, cache, inputs_embeds=None, input_ids=None, out=None, w8=False):
@@ -429,7 +524,8 @@ class Qwen2DecodeCache:
       K  bf16 [L, B, Hkv, cap, dk], VT bf16 [L, B, Hkv, dk, cap]   zeroed once: the kernels need them finite, not empty
       k_lo, k_hi int32 [B]    the valid keys of each sample, one contiguous run; a step appends at slot k_hi and advances it
       pos int64 [B], or [3, B] with an mrope_section    the next position of each sample (the RoPE table's argument, not a slot)
-      steps    host-side count of an upper bound of k_hi (None before a prefill); a caller that replays a captured step adds to it itself
+      steps    host-side count of an upper bound of k_hi (None before a prefill); a caller that replays a captured step adds to it itself;
+               an extension sets it to keep + n
     and the step's scratch rows, the prefill's Q [B, Hq, cap, dk] and the attention's split workspace."""
 
     def __init__(self, stack, B, capacity):
@@ -485,6 +581,23 @@ class Qwen2DecodeCache:
             pos = pos.masked_fill((attention_mask == 0).to(pos.device)[None], -1)
         self.pos.copy_((pos.amax(-1).amax(0) + 1).expand_as(self.pos) if self.mrope else pos.amax(-1)[0] + 1)
         self.steps = S
+
+    def _adopt(self, other, P):
+        """Slots [0, P) of another cache of the same stack and batch size (a conversation that outgrew it): K / V^T of every layer and k_lo
+        copied over with torch ops; the keys end at P until an extension follows."""
+        self.K[:, :, :, :P].copy_(other.K[:, :, :, :P])
+        self.VT[..., :P].copy_(other.VT[..., :P])
+        self.k_lo.copy_(other.k_lo)
+        self.k_hi.fill_(P)
+        self.steps = P
+
+    def _set_extension(self, keep, n, position_ids):
+        """After a chunk of n rows at slots keep .. keep + n - 1 (Qwen2DecoderStack.extend): the keys end at keep + n, whatever lay behind is
+        dropped, k_lo stays; next position = 1 + the largest position id of the chunk over all axes.  On the device, no host read."""
+        self.k_hi.fill_(keep + n)
+        pos = position_ids if position_ids.dim() == 3 else position_ids[None]
+        self.pos.copy_((pos.amax(-1).amax(0) + 1).expand_as(self.pos) if self.mrope else pos.amax(-1)[0] + 1)
+        self.steps = keep + n
 
     def _step_tables(self):
         """(cos, sin) f32 [B, dk/2] of the next positions, rope_tables' arithmetic into buffers of the cache; then slot = k_hi, k_hi += 1,
