@@ -9,7 +9,7 @@ So every output element has its own bound, far sharper than any rel-L2 over a ti
   f32 part.  |v - want| <= delta, with  delta = U_ACC * |gate| * (sum_k |a_mk w_nk| + |b_n|)  [+ the epilogue terms below].  bf16 -> f64 is
              exact and so are the products: `want` is the exact value of the epilogue on the operands the kernel read.  sum |a w| goes
              through an f32 GEMM: only the bound needs it.
-  epilogue.  act:      |act'(lin)| delta (+ delta^2: |act''| < 1 for GELU / SiLU) + U_ACT |act(lin)| + ACT_TAIL |lin|
+  epilogue.  act:      |act'(lin)| delta (+ delta^2: |act''| < 1 for GELU / SiLU) + U_ACT |act(lin)| + ACT_TAIL |lin|  (+ U_ERF |lin| / 2, GELU-erf)
              residual: |gate| delta + U_F32 (|res| + |gate act(lin)|)     (the one rounding of fmaf)
   output.    bf16:     |out - want| <= delta + 1/2 ulp_bf16(|want| + delta)   (the one round-to-nearest; a second rounding, or truncation, costs
                        up to another half ulp and fails wherever it lands away from the first)
@@ -18,7 +18,7 @@ So every output element has its own bound, far sharper than any rel-L2 over a ti
              Exactly that one-ulp change of x (dx) is allowed, propagated through the norm (sum x^2 -> rsqrt, mean-value bound) and the
              rotation, plus U_NORM relative to the rotation's terms for the f32 arithmetic of norm_rope8; then half a bf16 ulp.
 
-Constants (worst measured error / bound over the GPU test, tests/test_gemm_fp64_gpu.py, next to each)."""
+Constants (worst measured error / bound over the GPU tests, tests/test_gemm_fp64_gpu.py and tests/test_encoder_gemm_fp64_gpu.py, next to each)."""
 import math
 
 import torch
@@ -28,10 +28,32 @@ U_F32 = 2.0 ** -24
 # (2^-22.5 .. 2^-21.4); these bf16 MFMA kernels at K up to 15360 start from 2^-20 (9.5e-7).  Measured: at most 0.323 of the whole f32
 # allowance used (to_out pair, gated residual, K = 3072: 3.1e-7 sum |a w|); the other plain launches 0.062 (x_embedder) .. 0.185
 # (single-block proj_out, K = 15360), over every kernel form.
+# The encoder and decoder modules' launches (tests/test_encoder_gemm_fp64_gpu.py; profiles/encoder_gemm_fp64_gputest.log), worst share of
+# the whole f32 allowance per launch family, forms 128 and 256: plain and biased projections (qkv, gu / wi / fc1 without activation, pe,
+# kv_proj, K | V slabs by ldc / c_offset, a_offset) 0.118 (SigLIP pe, K = 640); residual in place (out=X, res=X) 0.117 (SigLIP fc2,
+# K = 4352; T5 wo at K = 10240: 0.087); residual with its own ldr 0.100 (Qwen2 7B o_proj); f32 gate with the residual in place
+# (InternViT layer scale) 0.218; batched with c_offset (Whisper conv1, InternViT pe, the Qwen2 slab) 0.088; overlapping A rows (Whisper
+# conv2, lda = 2 D, K = 3 D) 0.065; a weight per item (VAE attention: h, k, V^T as W) 0.038; out_f32 (projector head) 0.203; out2 / act2
+# 0.061.  K = 18944 (Qwen2 7B down_proj), beyond the 15360 above: 0.088 into the slab, 0.095 plain: no larger a share than at
+# K = 3584 (0.100), so 2^-20 holds there with the same margin.
 U_ACC = 2.0 ** -20
 # v_exp_f32 / v_rcp_f32 / erff in gelu_tanh_f, gelu_erf_f, silu_f: a few f32 ulps of the result; 32 ulps allowed.  Measured together with
-# U_ACC: the GELU-tanh launches use at most 0.157 of the allowance (proj_mlp); not measured apart, nor for GELU-erf / SiLU (no model launch).
+# U_ACC: the GELU-tanh launches use at most 0.157 of the allowance (proj_mlp); not measured apart.  GELU-erf, SiLU and ReLU, measured with
+# U_ACC as well, per activation over the toy grid of tests/test_encoder_gemm_fp64_gpu.py (every epilogue form on the 128, 256 and generic
+# kernels; the f32 output shows most, a bf16 output's rounding hides the rest): GELU-erf 0.077, SiLU 0.086, ReLU 0.084 (no activation:
+# 0.059, GELU-tanh 0.070); and in the modules' launches: GELU-erf 0.098 (InternViT fc1; Whisper fc1 0.073, its convs 0.065, the Qwen2.5-VL
+# merger at M = 25 0.059, mlp1 at K = 4096 0.081, the projector 0.060), ReLU 0.045 (Whisper projection), GELU-tanh 0.069 (SigLIP fc1).
 U_ACT = 2.0 ** -19
+# gelu_erf_f is 0.5 x (1 + erff(x / sqrt 2)) as written (csrc/x2i_common.h), and for x < 0 the sum 1 + erf cancels: what is a few ulps of erf
+# (|erf| < 1: ulps of 2^-24) is an ABSOLUTE error of the sum, however small the sum is, so the result carries 0.5 |x| times it -- relative to
+# GELU(x) that grows without limit as x falls (at x = -4 the result is 1.3e-4 and an erf error of 2^-24 moves it by 1.2e-7, 1e-3 of it; torch's
+# own f32 GELU has the same form and the same error).  U_ACT |act(x)| cannot hold there, so GELU-erf alone gets the term U_ERF 0.5 |x|, from
+# the arithmetic and not from a run: erff within 4 ulps of its result (4 * 2^-24 = 2^-22), the rounding of x / sqrt 2 (erf' z <= 0.43: under
+# 2^-25) and of the sum (half an ulp of a value in [1, 2): 2^-24; exact by Sterbenz where erf <= -1/2) -- under 2^-21 together.  The tanh
+# GELU and SiLU are x / (1 + exp2(..)): no cancellation, their error stays relative.  Without this term the f32 stand-in of
+# tests/test_gemm_ref_cpu.py itself fails (70 x its bound where 1 + erf is 0 in f32 and GELU is -1.2e-7); with it the stand-in uses 0.114
+# of the allowance and the kernels the shares above.
+U_ERF = 2.0 ** -21
 # where exp2 over- / underflows (GELU far below 0) the kernel returns +-0 for a result below 2^-100 |x|
 ACT_TAIL = 2.0 ** -100
 # f32 arithmetic of the QKV norm / rotation, relative to |y_e c| + |y_o s|: sum of 128 squares (fma chain + shuffle tree, <= 12 u), the
@@ -96,7 +118,10 @@ def _act_bound(x, y, d, act):
     """bound on |act_f32(x~) - act(x)| for |x~ - x| <= d, y = act(x)"""
     if act in (ACT_NONE, ACT_RELU):           # (ReLU is fmaxf(v, 0): exact, |max(a, 0) - max(b, 0)| <= |a - b|, no U_ACT term)
         return d
-    return (dact_f64(x, act).abs() + d) * d + U_ACT * y.abs() + ACT_TAIL * x.abs()
+    b = (dact_f64(x, act).abs() + d) * d + U_ACT * y.abs() + ACT_TAIL * x.abs()
+    if act == ACT_GELU_ERF:                   # (the one activation whose f32 form cancels: see U_ERF)
+        b = b + U_ERF * 0.5 * x.abs()
+    return b
 
 
 def _round_bound(want, d, f32):
@@ -366,6 +391,17 @@ def tag_scales(M, K, z=0, device="cpu"):
     return torch.exp2(er[:, None] + eb[None, :])
 
 
+def tag_scales_flat(n, lda, z=0, device="cpu"):
+    """`tagged` scales [n] for the flat STORAGE of an operand whose rows overlap in memory (row stride lda < K: a strided convolution's
+    A): storage element e lies in storage row e // lda, column e % lda, and gets 2^(e_row + e_blk) as in tag_scales -- per storage row and
+    per 64-wide column block.  A kernel row m spans the storage rows m, m + 1, ..: each lda-wide stretch of its K carries another row
+    exponent, so a stretch read from the neighbouring row, or the whole operand read densely (lda = K), changes the sum visibly."""
+    e = torch.arange(n, device=device)
+    er = ((torch.div(e, lda, rounding_mode="floor") + 3 * z) * 7 % 13 - 6).double()
+    eb = (torch.div(e % lda, 64, rounding_mode="floor") * 5 % 11 - 5).double()
+    return torch.exp2(er + eb)
+
+
 def lin_scale(K):
     """rough std of lin for A ~ N(0, 1), W ~ 0.02 N(0, 1), bias ~ 0.5 N(0, 1)"""
     return math.sqrt(0.0004 * K + 0.25)
@@ -376,13 +412,17 @@ ROWS = 4096     # rows per float64 block (a multiple of TILE): one [4096, 15360]
 
 
 def check_gemm(rep, A, W, bias, C, *, act=ACT_NONE, gate=None, res=None, C2=None, act2=ACT_NONE, out_f32=False, rows=ROWS):
-    """Every element of one x2i_gemm_bf16 problem: A [batch, M, K], C / res (the residual as it was BEFORE the launch) / C2 [batch, M, N]
+    """Every element of one x2i_gemm_bf16 problem: A [batch, M, K] (a view: the items may share their rows, a_batch_stride = 0, and the rows
+    may overlap in memory, lda < K -- the reference reads what the kernel reads), W [N, K] or, a weight per item (w_batch_stride != 0),
+    [batch, N, K]; C / res (the residual as it was BEFORE the launch: a clone where it shares the output's storage) / C2 [batch, M, N]
     (views), gate [batch, N] or None.  Adds to Report `rep`; returns it."""
     batch, M, _ = A.shape
+    assert W.dim() == 2 or (W.dim() == 3 and W.shape[0] == batch), (tuple(W.shape), batch)
     for z in range(batch):
+        Wz = W[z] if W.dim() == 3 else W
         for r0 in range(0, M, rows):
             r1 = min(M, r0 + rows)
-            e = gemm_expect(A[z, r0:r1], W, bias, act=act, gate=gate[z] if gate is not None else None,
+            e = gemm_expect(A[z, r0:r1], Wz, bias, act=act, gate=gate[z] if gate is not None else None,
                             res=res[z, r0:r1] if res is not None else None, act2=act2 if C2 is not None else None, out_f32=out_f32)
             (want, bound, d), e2 = (e if C2 is not None else (e, None))
             rep.check(C[z, r0:r1], want, bound, d, item=z, row0=r0)

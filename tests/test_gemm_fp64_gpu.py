@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from tests import gemm_ref as R
+from tests import gemm_replay as GR
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -45,7 +46,6 @@ ALT_FORMS = [("b1_512", "gemm_fx", 0, forms(128, 128, 2256, 2256, 2256, 2256, 25
              ("b1_512", "gemm_pair", 0, forms(128, 128, 128, 128, 128, 128, 256, 1256, 3256, 128)),
              ("b1_512", "gemm_tile", 128, forms(*[128] * 10)),
              ("b4_1024", "gemm_streamk", 0, forms(128, 256, 2256, 2256, 2256, 2256, 1256, 1256, 1256, 128))]
-TENSOR_ARGS = ("A", "W", "bias", "out", "res", "gate", "out2", "bias2", "Q", "K", "VT", "norm_q", "norm_k", "cos", "sin")
 WORST = {}      # launch -> worst share of the f32 allowance used, over everything this module ran (printed by each test)
 
 
@@ -70,25 +70,12 @@ def opt(ops):
 
 
 # ---------------------------------------------------------------------------------------------------------------- recording
-class Spec:
-    """geometry of one tensor argument: its storage (identity and size), dtype, shape, strides, offset"""
-
-    def __init__(self, t, keep=False):
-        self.key = t.untyped_storage().data_ptr()
-        self.numel = t.untyped_storage().nbytes() // t.element_size()
-        self.dtype, self.shape, self.stride, self.offset = t.dtype, tuple(t.shape), tuple(t.stride()), t.storage_offset()
-        self.obj = t if keep else None          # (kept for the RoPE tables only: the replay reads the model's own)
-
-
-def _record(kw):
-    return {k: (Spec(v, keep=k in ("cos", "sin")) if isinstance(v, torch.Tensor) else v) for k, v in kw.items()}
-
-
+# (Spec, the recorder, the operand fill and the replay itself live in tests/gemm_replay.py, shared with the encoder modules' test)
 _recordings = {}
 
 
 def recording(ops, cfg):
-    """[(op name, [problem dict])] of one prepare_conditioning + denoise at configuration cfg, with the model's scalars"""
+    """the named recording (gemm_replay.record) of one prepare_conditioning + denoise at configuration cfg, with the model's scalars"""
     if cfg in _recordings:
         return _recordings[cfg]
     from x2i_amd.flux import FluxTransformer2DModel
@@ -104,139 +91,17 @@ def recording(ops, cfg):
     img_ids[..., 1] += torch.arange(hw)[:, None]
     img_ids[..., 2] += torch.arange(hw)[None, :]
     hs = torch.randn((B, Si, 64), generator=g).to(DEV, torch.bfloat16)
-    calls, alive = [], []
-    names = {"gemm": lambda *a, **k: [_record(dict(zip(("A", "W", "bias", "out"), a), **k))],
-             "gemm_pair": lambda g0, g1: [_record(g0), _record(g1)],
-             "gemm_qkv": lambda *a, **k: [_record(dict(zip(("A", "W", "bias", "Q", "K", "VT", "norm_q", "norm_k", "cos", "sin"), a), **k))],
-             "gemm_qkv_pair": lambda g0, g1: [_record(g0), _record(g1)]}
-    orig = {n: getattr(ops, n) for n in names}
 
-    def wrap(n):
-        def f(*a, **k):
-            calls.append((n, names[n](*a, **k)))
-            alive.extend(list(a) + list(k.values()))     # (no storage is freed and reused while the recording names storages by address)
-            return orig[n](*a, **k)
-        return f
-    try:
-        for n in names:
-            setattr(ops, n, wrap(n))
+    def run():
         state = m.prepare_conditioning(enc, pooled, txt_ids.to(DEV), img_ids.reshape(-1, 3).to(DEV))
         m.denoise(state, hs, torch.full((B,), 0.75, device=DEV))
-        torch.cuda.synchronize()
-    finally:
-        for n, f in orig.items():
-            setattr(ops, n, f)
+    calls = GR.record(ops, run)
     S = ST + Si
-    rec = dict(calls=calls, B=B, Si=Si, S=S)
-    del m, state, alive
+    rec = dict(calls=calls, names=LAUNCHES, B=B, Si=Si, S=S)
+    del m
     _recordings.clear()
     _recordings[cfg] = rec
     return rec
-
-
-# ---------------------------------------------------------------------------------------------------------------- replay
-def _fill(role, spec, gen):
-    n = spec.numel
-    if role in ("out", "res", "out2", "Q", "K", "VT"):
-        return R.poison_(torch.empty(n, device=DEV, dtype=spec.dtype))
-    if role in ("norm_q", "norm_k"):
-        return (1.0 + 0.1 * torch.randn(n, device=DEV, generator=gen)).to(spec.dtype)
-    scale = {"A": 1.0, "W": 0.02, "bias": 0.5, "gate": 1.0, "bias2": 0.5}[role]
-    return (scale * torch.randn(n, device=DEV, generator=gen)).to(spec.dtype)
-
-
-def _view(buf, spec):
-    return buf.as_strided(spec.shape, spec.stride, spec.offset)
-
-
-def replay(ops, rec, idx, kind, seed):
-    """Replay launch idx of the recording on fresh `kind` operands; check every element and the sentinels.  Returns (form, worst share)."""
-    from x2i_amd import _lib
-    op, probs = rec["calls"][idx]
-    name = LAUNCHES[idx]
-    gen = torch.Generator(device=DEV).manual_seed(seed)
-    bufs = {}
-    for p in probs:
-        for role in TENSOR_ARGS:
-            s = p.get(role)
-            if isinstance(s, Spec) and s.key not in bufs and role not in ("cos", "sin"):
-                bufs[s.key] = _fill(role, s, gen)
-    qkv = op.startswith("gemm_qkv")
-    launch_args, checks, masks = [], [], {}
-    for p in probs:
-        kw = {k: v for k, v in p.items() if not isinstance(v, Spec)}
-        t = {r: (_view(bufs[s.key], s) if r not in ("cos", "sin") else s.obj) for r, s in p.items() if isinstance(s, Spec)}
-        Aspec, Wspec = p["A"], p["W"]
-        batch, M = p.get("batch", 1), p["M"]
-        Kd = Wspec.shape[-1] if qkv or p.get("K") is None else p["K"]      # (a QKV problem's "K" is the K output)
-        N = (3 * p["H"] * 128) if qkv else (p.get("N") or Wspec.shape[-2])
-        lda = p.get("lda") or Aspec.shape[-1]
-        A3 = bufs[Aspec.key].as_strided((batch, M, Kd), (p.get("a_batch_stride", 0), lda, 1), Aspec.offset + p.get("a_offset", 0))
-        W2 = bufs[Wspec.key].as_strided((N, Kd), (Wspec.stride[-2], 1), Wspec.offset)
-        bias = t["bias"].reshape(-1)[:N] if "bias" in t else None
-        if kind == "tagged":
-            for z in range(batch):
-                A3[z].copy_((A3[z].double() * R.tag_scales(M, Kd, z, device=DEV)).to(A3.dtype))
-        chk = dict(qkv=qkv, A3=A3, W2=W2, bias=bias, M=M, N=N, batch=batch, p=p, t=t)
-        if not qkv:
-            out = p["out"]
-            ldc = p.get("ldc") or N
-            c_bs = p.get("c_batch_stride", 0)
-            C3 = bufs[out.key].as_strided((batch, M, N), (c_bs, ldc, 1), out.offset + p.get("c_offset", 0))
-            masks.setdefault(out.key, []).append(((batch, M, N), (c_bs, ldc, 1), out.offset + p.get("c_offset", 0)))
-            chk["C3"] = C3
-            if "out2" in t:
-                chk["C2"] = bufs[p["out2"].key].as_strided((batch, M, N), (c_bs, ldc, 1), p["out2"].offset + p.get("c_offset", 0))
-                masks.setdefault(p["out2"].key, []).append(((batch, M, N), (c_bs, ldc, 1), p["out2"].offset + p.get("c_offset", 0)))
-            if "gate" in t:
-                gs = p["gate"]
-                chk["gate"] = bufs[gs.key].as_strided((batch, N), (p.get("gate_batch_stride", 0), 1), gs.offset)
-            if "res" in t:
-                rs = p["res"]
-                res3 = bufs[rs.key].as_strided((batch, M, N), (p.get("res_batch_stride", 0), p.get("ldr") or ldc, 1), rs.offset + p.get("res_offset", 0))
-                for z in range(batch):
-                    for r0 in range(0, M, R.ROWS):
-                        r1 = min(M, r0 + R.ROWS)
-                        if kind == "cancel":       # res = -gate * lin: the output is the tiny rounding residual of res
-                            lin, _ = R.linear_f64(A3[z, r0:r1], W2, bias)
-                            gz = chk["gate"][z].double() if "gate" in chk else 1.0
-                            res3[z, r0:r1] = (-gz * lin).to(res3.dtype)
-                            del lin
-                        else:
-                            res3[z, r0:r1] = (R.lin_scale(Kd) * torch.randn((r1 - r0, N), device=DEV, generator=gen)).to(res3.dtype)
-                chk["res"] = res3.clone()
-        checks.append(chk)
-        # the tensors of the call itself: the recorded views on the fresh storages
-        args = dict(kw)
-        args.update({r: v for r, v in t.items()})
-        launch_args.append(args)
-    fn = getattr(ops, op)
-    if op in ("gemm_pair", "gemm_qkv_pair"):
-        fn(launch_args[0], launch_args[1])
-    else:
-        fn(**launch_args[0])
-    form = int(_lib.get_option("last_gemm_tile"))
-    torch.cuda.synchronize()
-    worst = 0.0
-    for i, c in enumerate(checks):
-        p, t = c["p"], c["t"]
-        rep = R.Report(f"{name}[{i}] {kind}")
-        if c["qkv"]:
-            R.check_qkv(rep, c["A3"], c["W2"], c["bias"], t["norm_q"].reshape(-1)[:128], t["norm_k"].reshape(-1)[:128], t["cos"], t.get("sin"),
-                        t["Q"], t["K"], t["VT"], H=p["H"], tok_off=p["tok_off"], rows_per_sample=p["rows_per_sample"],
-                        q_scale=p.get("q_scale", 1.0), eps=p.get("eps", 1e-6), vt_perm=bool(p.get("vt_perm", False)))
-        else:
-            R.check_gemm(rep, c["A3"], c["W2"], c["bias"], c["C3"], act=p.get("act", 0), gate=c.get("gate"), res=c.get("res"),
-                         C2=c.get("C2"), act2=p.get("act2", 0), out_f32=bool(p.get("out_f32", False)))
-        worst = max(worst, rep.done())
-    if qkv:
-        p, t = checks[0]["p"], checks[0]["t"]
-        R.check_qkv_padding(f"{name} {kind}", t["Q"], t["K"], t["VT"], rec["S"], bool(p.get("vt_perm", False)))
-    for key, views in masks.items():
-        buf = bufs[key]
-        R.check_untouched(f"{name} {kind}", buf, R.write_mask(buf, views), row_len=views[0][1][1])
-    del bufs, checks
-    return form, worst
 
 
 def check_launch_list(rec):
@@ -262,7 +127,7 @@ def run_config(ops, rec, kinds, label):
     seen = {}
     for kind in kinds:
         for i, name in enumerate(LAUNCHES):
-            form, worst = replay(ops, rec, i, kind, seed=1000 * i + R.KINDS.index(kind))   # (new A, W, bias per kind)
+            form, worst = GR.replay(ops, rec, name, kind, seed=1000 * i + R.KINDS.index(kind))   # (new A, W, bias per kind)
             seen.setdefault(name, set()).add(form)
             WORST[name] = max(WORST.get(name, 0.0), worst)
     ops.streamk_check(sync=True)

@@ -172,8 +172,165 @@ def test_truncation_of_a_gelu_epilogue_is_rejected():
     assert msg is not None and f"tile ({FT[0]}, {FT[1]})" in msg
 
 
+# ---------------------------------------------------------------------------------------------------------------- encoder launches
+# What the encoder modules' launches add to the checker (tests/gemm_replay.py, tests/test_encoder_gemm_fp64_gpu.py): a weight per item,
+# A rows that overlap in memory, a residual in the output's own storage, and the GELU-erf / SiLU / ReLU epilogues.  Small shapes: two items,
+# one ragged tile each.
+M2, N2, D2 = 70, 100, 64
+LDA2, K2 = 2 * D2, 3 * D2                # the stride-2 convolution as a GEMM: a row starts 2 D after the last and is 3 D long
+
+
+def act_f32(v, act):
+    """the activations as csrc/x2i_common.h writes them, in f32"""
+    if act == R.ACT_GELU_TANH:
+        return v / (1.0 + torch.exp2(v * (v * v * -0.10294324 - 2.3022082)))
+    if act == R.ACT_GELU_ERF:
+        return 0.5 * v * (1.0 + torch.erf(v * 0.7071067811865476))
+    if act == R.ACT_SILU:
+        return v / (1.0 + torch.exp2(-1.4426950408889634 * v))
+    if act == R.ACT_RELU:
+        return v.clamp_min(0.0)
+    return v
+
+
+def standin2(A, W, bias, *, act=R.ACT_NONE, gate=None, res=None, fault=None):
+    """x2i_gemm_bf16 on A [batch, M, K] (any view), W [N, K] or [batch, N, K], gate [batch, N], res [batch, M, N]: bf16 [batch, M, N].
+    fault: "w_prev" (item z multiplies the weight of item z - 1), "act_tanh" (the tanh GELU whatever was asked), "double_round" (a bf16
+    rounding before the residual add), "gate_shift" (column n takes the gate of channel n + 1)."""
+    out = []
+    for z in range(A.shape[0]):
+        Wz = W if W.dim() == 2 else W[z - 1 if (fault == "w_prev" and z > 0) else z]
+        v = acc_f32(A[z], Wz) + (bias.float() if bias is not None else 0.0)
+        v = act_f32(v, R.ACT_GELU_TANH if fault == "act_tanh" else act)
+        if res is not None:
+            g = gate[z] if gate is not None else torch.ones(v.shape[1])
+            if fault == "gate_shift":
+                g = torch.roll(g, -1)
+            if fault == "double_round":
+                v = v.to(bf).float()
+            v = f32_fma(g, v, res[z].float())
+        out.append(v.to(bf))
+    return torch.stack(out)
+
+
+def failure2(A, W, bias, C, **kw):
+    try:
+        R.check_gemm(R.Report("launch"), A, W, bias, C, **kw).done()
+    except AssertionError as e:
+        return str(e)
+    return None
+
+
+def names_item_row_col(msg, item=None):
+    import re
+    return msg is not None and re.search(r"item %s: .*\(m=\d+, n=\d+\)" % (r"\d+" if item is None else item), msg) is not None
+
+
+def small_operands(kind, seed, K=K2, w_batch=False):
+    g = torch.Generator().manual_seed(seed)
+    A = torch.randn((B, M2, K), generator=g)
+    if kind == "tagged":
+        A = torch.stack([A[z] * R.tag_scales(M2, K, z) for z in range(B)])
+    W = (0.02 * torch.randn((B, N2, K) if w_batch else (N2, K), generator=g)).to(bf)
+    bias = (0.5 * torch.randn((N2,), generator=g)).to(bf)
+    return A.to(bf), W, bias
+
+
+def overlapped_A(kind, seed):
+    """(the strided view [B, M2, K2] with lda = LDA2 < K2, the same storage read densely with lda = K2): the storage is filled, and `tagged`
+    scales the storage (a copy_ into an overlapping view is refused)"""
+    per_item = M2 * K2                    # (room for the dense reading too)
+    st = torch.randn(B * per_item, generator=torch.Generator().manual_seed(seed))
+    if kind == "tagged":
+        n = (M2 - 1) * LDA2 + K2
+        for z in range(B):
+            st[z * per_item:z * per_item + n] *= R.tag_scales_flat(n, LDA2, z).float()
+    st = st.to(bf)
+    return st.as_strided((B, M2, K2), (per_item, LDA2, 1)), st.as_strided((B, M2, K2), (per_item, K2, 1))
+
+
+@pytest.mark.parametrize("kind", R.KINDS)
+def test_standin_passes_with_a_weight_per_item_and_a_shared_a(kind):
+    A, W, bias = small_operands(kind, 31, w_batch=True)
+    assert failure2(A, W, bias, standin2(A, W, bias)) is None
+    shared = A[:1].expand(B, M2, K2)          # a_batch_stride = 0: every item reads the same rows
+    assert shared.stride(0) == 0
+    assert failure2(shared, W, bias, standin2(shared, W, bias)) is None
+    # the previous item's weight is rejected, in item 1 and not in item 0
+    msg = failure2(A, W, bias, standin2(A, W, bias, fault="w_prev"))
+    assert names_item_row_col(msg, 1) and "item 0" not in msg, msg
+    with pytest.raises(AssertionError):
+        R.check_gemm(R.Report("shape"), A, W[:1], bias, standin2(A, W, bias))       # a batch of weights that is not the launch's
+
+
+@pytest.mark.parametrize("kind", R.KINDS)
+def test_standin_passes_with_overlapping_a_rows_and_the_dense_reading_is_rejected(kind):
+    A, dense = overlapped_A(kind, 32)
+    assert A.stride() == (M2 * K2, LDA2, 1) and torch.equal(A[0, 1, :D2], A[0, 0, LDA2:])       # the rows do overlap
+    _, W, bias = small_operands("random", 33)
+    assert failure2(A, W, bias, standin2(A, W, bias)) is None
+    msg = failure2(A, W, bias, standin2(dense, W, bias))
+    assert names_item_row_col(msg), msg
+    assert "(m=0," not in msg                     # row 0 reads the same elements either way
+    if kind == "tagged":                          # the storage tags differ from row to row and from 64-block to 64-block
+        t = R.tag_scales_flat(2 * LDA2, LDA2)
+        assert float(t[0]) != float(t[64]) and float(t[0]) != float(t[LDA2]) and bool((torch.log2(t) == torch.log2(t).round()).all())
+
+
+@pytest.mark.parametrize("kind", R.KINDS)
+def test_standin_passes_with_the_residual_in_the_outputs_storage(kind):
+    """out=X, res=X: the residual is filled into the shared storage, a clone of it is what the reference reads"""
+    A, W, bias = small_operands(kind, 34)
+    g = torch.Generator().manual_seed(35)
+    gate = torch.randn((B, N2), generator=g)
+    if kind == "cancel":
+        X = torch.stack([(-gate[z].double() * R.linear_f64(A[z], W, bias)[0]).to(bf) for z in range(B)])
+    else:
+        X = (R.lin_scale(K2) * torch.randn((B, M2, N2), generator=g)).to(bf)
+    before = X.clone()
+    X.copy_(standin2(A, W, bias, gate=gate, res=X))
+    assert failure2(A, W, bias, X, gate=gate, res=before) is None
+    assert failure2(A, W, bias, X, gate=gate, res=X) is not None            # the storage after the launch is not the residual
+    # a second bf16 rounding before the add; the gate read one channel off
+    X2 = before.clone()
+    X2.copy_(standin2(A, W, bias, gate=gate, res=X2, fault="double_round"))
+    msg = failure2(A, W, bias, X2, gate=gate, res=before)
+    assert names_item_row_col(msg), (kind, msg)
+    X3 = before.clone()
+    X3.copy_(standin2(A, W, bias, gate=gate, res=X3, fault="gate_shift"))
+    msg = failure2(A, W, bias, X3, gate=gate, res=before)
+    assert names_item_row_col(msg), (kind, msg)
+
+
+@pytest.mark.parametrize("act", [R.ACT_GELU_ERF, R.ACT_SILU, R.ACT_RELU], ids=["gelu_erf", "silu", "relu"])
+def test_standin_passes_with_each_activation(act):
+    A, W, bias = small_operands("random", 36 + act, K=1024)
+    A = (A.float() * 3.0).to(bf)                  # lin reaches +-6: the tails of the activations, and the cancelling side of 1 + erf
+    lin = R.linear_f64(A[0], W, bias)[0]
+    assert float(lin.min()) < -5.0 and float(lin.max()) > 5.0
+    rep = R.check_gemm(R.Report("act"), A, W, bias, standin2(A, W, bias, act=act), act=act)
+    share = rep.done()
+    print(f"\n  act {act}: share of the f32 allowance used by the stand-in {share:.3f}")
+    assert share < 1.0
+    # and as a second output: C = v, C2 = act(v)
+    C = standin2(A, W, bias)
+    C2 = torch.stack([act_f32(acc_f32(A[z], W) + bias.float(), act).to(bf) for z in range(B)])
+    assert R.check_gemm(R.Report("act2"), A, W, bias, C, C2=C2, act2=act).done() < 1.0
+
+
+def test_tanh_gelu_where_erf_was_asked_is_rejected():
+    A, W, bias = small_operands("random", 38, K=1024)
+    msg = failure2(A, W, bias, standin2(A, W, bias, act=R.ACT_GELU_ERF, fault="act_tanh"), act=R.ACT_GELU_ERF)
+    assert names_item_row_col(msg), msg
+    # ... and the widened erf term does not let the tanh form through on the negative side alone either
+    neg = (-0.25 * A.float().abs()).to(bf), W.abs(), None         # lin near -3.3: GELU near -1.6e-3, the two forms 3e-4 apart
+    msg = failure2(*neg, standin2(*neg, act=R.ACT_GELU_ERF, fault="act_tanh"), act=R.ACT_GELU_ERF)
+    assert names_item_row_col(msg), msg
+    assert failure2(*neg, standin2(*neg, act=R.ACT_GELU_ERF), act=R.ACT_GELU_ERF) is None
+
+
 # ---------------------------------------------------------------------------------------------------------------- fused QKV
-H, ST, SI, NS = 2, 40, 300, 2           # two heads (one 256-column tile per section), 40 text + 300 image tokens, two samples
+H, ST, SI, NS = 2, 40, 300, 2          # two heads (one 256-column tile per section), 40 text + 300 image tokens, two samples
 S = ST + SI
 SPAD = (S + 127) // 128 * 128
 KQ = 512
