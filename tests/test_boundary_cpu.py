@@ -7,6 +7,8 @@ import os
 import re
 import subprocess
 
+from tests import headers
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = open(os.path.join(ROOT, "include", "x2i.h")).read()
 
@@ -95,7 +97,7 @@ def header_prototypes():
     """{export: (return type, [argument types])} of every prototype in include/x2i.h, as the ctypes objects the binding must use"""
     from x2i_amd import _lib
     structs = {"x2i_gemm_args": _lib.GemmArgs, "x2i_conv_desc": _lib.ConvDesc, "x2i_qkv_desc": _lib.QkvDesc, "x2i_fp8_desc": _lib.Fp8Desc}
-    scalars = {"int32_t": C.c_int32, "int": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "x2i_stream_t": C.c_void_p}
+    scalars = headers.SCALARS
 
     def ctype(decl, named):
         """`const float* x` / `int32_t B` (named) or a bare return type -> the ctypes type"""
@@ -112,9 +114,8 @@ def header_prototypes():
             return C.POINTER(structs[base])
         return {("int64_t", False): C.POINTER(C.c_int64), ("char", True): C.c_char_p}.get((base, const), C.c_void_p)
 
-    text = re.sub(r"/\*.*?\*/", "", HDR, flags=re.S)
     out = {}
-    for ret, name, params in re.findall(r"^(int|int64_t|const char\*)\s+(x2i_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+    for ret, name, params in headers.raw_prototypes(HDR):
         params = " ".join(params.split())
         out[name] = (ctype(ret, False), [] if params == "void" else [ctype(p, True) for p in params.split(",")])
     return out

@@ -1,6 +1,5 @@
 """CPU-side checks of the CLIP text encoder work (no GPU): the float64 restatement of the model against the library in float64, the checkers
-of tests/clip_ref.py against the mistakes they are there to catch, pooling known answers, the extension header include/x2i_clip.h against
-its binding and the built library, and the host module's refusals and key spellings."""
+of tests/clip_ref.py against the mistakes they are there to catch, pooling known answers, the extension header include/x2i_clip.h (its prototypes against the binding: tests/test_extension_boundary_cpu.py), and the host module's refusals and key spellings."""
 import ctypes as C
 import os
 
@@ -8,10 +7,6 @@ import pytest
 import torch
 
 from tests import clip_ref as CR
-from tests.test_t5_ref_cpu import _header_prototypes, _header_prototypes_any
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"x2i_clip_attention_bf16", "x2i_clip_embed_bf16", "x2i_clip_quick_gelu_bf16", "x2i_clip_pool_bf16"}
 
 
 # ---------------------------------------------------------------------------------------------------------------- float64 restatement
@@ -88,27 +83,6 @@ def test_pooling_known_answers():
 
 
 # ---------------------------------------------------------------------------------------------------------------- boundary
-def test_extension_header_matches_its_binding_and_the_library_exports_it():
-    from x2i_amd import _lib, clip_ops, t5_ops
-    want = _header_prototypes(os.path.join(ROOT, "include", "x2i_clip.h"))
-    assert set(want) == set(clip_ops._EXPORTS) == NAMES
-    for name, args in want.items():
-        assert len(clip_ops._EXPORTS[name]) == len(args), name
-        for i, (got, exp) in enumerate(zip(clip_ops._EXPORTS[name], args)):
-            assert got == exp, "%s: argument %d is %s in the binding, %s in the header" % (name, i, got.__name__, exp.__name__)
-        assert args[-1] == C.c_void_p                  # the stream comes last
-    lib = clip_ops.load()
-    for name in want:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == clip_ops._EXPORTS[name]
-    # the closed table of include/x2i.h and the T5 extension are as they were
-    base = _header_prototypes_any(os.path.join(ROOT, "include", "x2i.h"))
-    assert len(base) == 80 and not (set(base) & set(want)) and not (set(_lib._EXPORTS) & set(want))
-    t5 = _header_prototypes_any(os.path.join(ROOT, "include", "x2i_t5.h"))
-    assert len(t5) == 4 and t5 == set(t5_ops._EXPORTS) and not (t5 & set(want))
-    md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert "Extension header `include/x2i_clip.h`" in md and all("`%s`" % n in md for n in want)
-
-
 def test_entry_points_validate_their_arguments_without_a_gpu():
     from x2i_amd import clip_ops
     lib = clip_ops.load()

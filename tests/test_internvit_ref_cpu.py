@@ -9,10 +9,8 @@ import torch
 from safetensors.torch import load_file
 
 from tests import internvit_ref as IR
-from tests.test_t5_ref_cpu import _header_prototypes  # (a helper; its tests are not re-collected here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"x2i_internvit_patch_rows_bf16", "x2i_internvit_embed_bf16", "x2i_internvit_shuffle_ln_bf16"}
 RESTATEMENT_BOUND = 1e-10
 F64 = torch.float64
 
@@ -124,23 +122,6 @@ def test_gelu_form_is_invisible_without_the_activation_probe(fx, truth):
 
 
 # ---------------------------------------------------------------------------------------------------------------- boundary
-def test_extension_header_matches_its_binding_and_the_library_exports_it():
-    from x2i_amd import _lib, internvit_ops, ops
-    want = _header_prototypes(os.path.join(ROOT, "include", "x2i_internvit.h"))
-    assert set(want) == set(internvit_ops._EXPORTS) == NAMES
-    for name, args in want.items():
-        assert len(internvit_ops._EXPORTS[name]) == len(args), name
-        for i, (got, exp) in enumerate(zip(internvit_ops._EXPORTS[name], args)):
-            assert got == exp, "%s: argument %d is %s in the binding, %s in the header" % (name, i, got.__name__, exp.__name__)
-        assert args[-1] == C.c_void_p                  # the stream comes last
-    lib = internvit_ops.load()
-    for name in want:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == internvit_ops._EXPORTS[name]
-    assert not (set(_lib._EXPORTS) & set(want)) and not any(hasattr(ops, n) for n in ("internvit_patch_rows", "internvit_embed", "internvit_shuffle_ln"))
-    md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert "Extension header `include/x2i_internvit.h`" in md and all("`%s`" % n in md for n in want)
-
-
 def test_entry_points_validate_their_arguments_without_a_gpu():
     from x2i_amd import internvit_ops
     lib = internvit_ops.load()

@@ -1,7 +1,6 @@
 """CPU checks of the e4m3 decode linear's reference and checker (tests/qwen_decode_w8_ref.py): the dequantisation against torch's own
 float8_e4m3fn, an f32 stand-in of the kernel's documented summation order that must pass, the likely bugs planted in it that must fail --
-with what a whole-output rel-L2 threshold of the old kind would have said beside each -- and the boundary: include/x2i_qwen_decode_w8.h
-against its binding, the built library and INTEGRATION.md, and every refusal of the entry point."""
+with what a whole-output rel-L2 threshold of the old kind would have said beside each -- and the boundary: include/x2i_qwen_decode_w8.h (its prototypes against the binding: tests/test_extension_boundary_cpu.py), and every refusal of the entry point."""
 import ctypes as C
 import os
 
@@ -12,10 +11,9 @@ from tests import fp8_ref as F8
 from tests import gemm_ref as G
 from tests import qwen_decode_w8_ref as WR
 from tests import qwen_ref as QR
-from tests.test_t5_ref_cpu import _header_prototypes, _header_prototypes_any
+from tests.headers import header_prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"x2i_qwen_decode_linear_w8_bf16"}
 ERR_ARG, ERR_SHAPE, ERR_ALIGN = -1, -2, -3       # X2I_ERR_* of include/x2i.h
 
 
@@ -150,30 +148,13 @@ def test_mixed_reference_is_the_decode_reference_when_both_state_dicts_are_one()
 
 
 # ---------------------------------------------------------------------------------------------------------------- boundary
-def test_extension_header_matches_its_binding_and_the_library_exports_it():
-    from x2i_amd import _lib, clip_ops, merge_ops, qwen_decode_ops, qwen_decode_w8_ops, qwen_head_ops, qwen_ops, t5_ops, vit_ops
+def test_the_header_is_the_bf16_prototype_with_the_scale_and_states_its_promises():
     path = os.path.join(ROOT, "include", "x2i_qwen_decode_w8.h")
-    want = _header_prototypes(path)
-    assert set(want) == set(qwen_decode_w8_ops._EXPORTS) == NAMES
-    for name, args in want.items():
-        assert len(qwen_decode_w8_ops._EXPORTS[name]) == len(args), name
-        for i, (got, exp) in enumerate(zip(qwen_decode_w8_ops._EXPORTS[name], args)):
-            assert got == exp, "%s: argument %d is %s in the binding, %s in the header" % (name, i, got.__name__, exp.__name__)
-        assert args[-1] == C.c_void_p                  # the stream comes last
     # the bf16 entry point's prototype with the scale inserted after ldw
-    bf16 = _header_prototypes(os.path.join(ROOT, "include", "x2i_qwen_decode.h"))["x2i_qwen_decode_linear_bf16"]
-    assert want["x2i_qwen_decode_linear_w8_bf16"] == bf16[:4] + [C.c_void_p] + bf16[4:]
-    lib = qwen_decode_w8_ops.load()
-    for name in want:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == qwen_decode_w8_ops._EXPORTS[name]
-    others = set(_lib._EXPORTS) | _header_prototypes_any(os.path.join(ROOT, "include", "x2i.h"))
-    for mod in (t5_ops, clip_ops, qwen_ops, vit_ops, qwen_decode_ops, qwen_head_ops, merge_ops):
-        others |= set(mod._EXPORTS)
-    assert not (others & set(want))
+    bf16 = header_prototypes(os.path.join(ROOT, "include", "x2i_qwen_decode.h"))["x2i_qwen_decode_linear_bf16"]
+    assert header_prototypes(path)["x2i_qwen_decode_linear_w8_bf16"] == bf16[:4] + [C.c_void_p] + bf16[4:]
     text = open(path).read()
     assert "16 l + 1024 i + j" in text and "unspecified" in text and "bit-identical" in text       # the order and the two promises are stated
-    md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert "`include/x2i_qwen_decode_w8.h`" in md and all("`%s`" % n in md for n in want)
 
 
 def test_entry_point_validates_its_arguments_without_a_gpu():

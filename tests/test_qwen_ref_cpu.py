@@ -1,18 +1,12 @@
 """CPU-side checks of the Qwen2 decoder prefill work (no GPU): the float64 restatement of the stack against the library in float64 under both
 paddings and under M-RoPE, rope_tables bit for bit against the library's rotary embedding, the key ranges of a mask, the checkers of
-tests/qwen_ref.py against the mistakes they are there to catch, the extension header include/x2i_qwen.h against its binding and the built
-library, and the host module's refusals and parameter names."""
+tests/qwen_ref.py against the mistakes they are there to catch, the extension header include/x2i_qwen.h (its prototypes against the binding: tests/test_extension_boundary_cpu.py), and the host module's refusals and parameter names."""
 import ctypes as C
-import os
 
 import pytest
 import torch
 
 from tests import qwen_ref as QR
-from tests.test_t5_ref_cpu import _header_prototypes, _header_prototypes_any
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"x2i_qwen_attention_bf16", "x2i_qwen_rope_split_bf16", "x2i_qwen_swiglu_bf16"}
 
 
 # ---------------------------------------------------------------------------------------------------------------- float64 restatement
@@ -255,28 +249,6 @@ def test_swiglu_checker_accepts_one_rounding_and_rejects_other_gates_and_two_rou
 
 
 # ---------------------------------------------------------------------------------------------------------------- boundary
-def test_extension_header_matches_its_binding_and_the_library_exports_it():
-    from x2i_amd import _lib, clip_ops, qwen_ops, t5_ops
-    want = _header_prototypes(os.path.join(ROOT, "include", "x2i_qwen.h"))
-    assert set(want) == set(qwen_ops._EXPORTS) == NAMES
-    for name, args in want.items():
-        assert len(qwen_ops._EXPORTS[name]) == len(args), name
-        for i, (got, exp) in enumerate(zip(qwen_ops._EXPORTS[name], args)):
-            assert got == exp, "%s: argument %d is %s in the binding, %s in the header" % (name, i, got.__name__, exp.__name__)
-        assert args[-1] == C.c_void_p                  # the stream comes last
-    lib = qwen_ops.load()
-    for name in want:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == qwen_ops._EXPORTS[name]
-    # the closed table of include/x2i.h and the two earlier extensions are as they were
-    base = _header_prototypes_any(os.path.join(ROOT, "include", "x2i.h"))
-    assert len(base) == 80 and not (set(base) & set(want)) and not (set(_lib._EXPORTS) & set(want))
-    t5 = _header_prototypes_any(os.path.join(ROOT, "include", "x2i_t5.h"))
-    clip = _header_prototypes_any(os.path.join(ROOT, "include", "x2i_clip.h"))
-    assert len(t5) == 4 and t5 == set(t5_ops._EXPORTS) and len(clip) == 4 and clip == set(clip_ops._EXPORTS) and not ((t5 | clip) & set(want))
-    md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert "Extension header `include/x2i_qwen.h`" in md and all("`%s`" % n in md for n in want)
-
-
 def test_entry_points_validate_their_arguments_without_a_gpu():
     from x2i_amd import qwen_ops
     lib = qwen_ops.load()

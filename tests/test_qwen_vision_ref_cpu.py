@@ -1,17 +1,13 @@
 """The Qwen2.5-VL vision tower without a GPU: the host work of a call (x2i_amd/qwen_vision.py: plan) against the library's own functions, the
 padded packed weights and the float64 restatement of tests/qwen_vision_ref.py against the library in float64, the extension header
-include/x2i_vit.h against its binding and the built library, and every refusal."""
+include/x2i_vit.h (its prototypes against the binding: tests/test_extension_boundary_cpu.py), and every refusal."""
 import ctypes as C
-import os
 
 import pytest
 import torch
 
 from tests import qwen_vision_ref as VR
-from tests.test_t5_ref_cpu import _header_prototypes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"x2i_vit_attention_bf16", "x2i_vit_rope_split_bf16"}
 TWO_GRIDS = [(1, 10, 10), (2, 6, 14)]
 GRIDS = [[(1, 10, 10)], TWO_GRIDS, [(1, 4, 4)], [(1, 18, 10), (1, 2, 2)]]
 TINY = dict(depth=4, hidden_size=160, num_heads=2, intermediate_size=172, out_hidden_size=64, fullatt_block_indexes=[1, 3])
@@ -152,23 +148,6 @@ def test_attention_reference_and_checker():
 
 
 # ---------------------------------------------------------------------------------------------------------------- boundary
-def test_extension_header_matches_its_binding_and_the_library_exports_it():
-    from x2i_amd import _lib, ops, vit_ops
-    want = _header_prototypes(os.path.join(ROOT, "include", "x2i_vit.h"))
-    assert set(want) == set(vit_ops._EXPORTS) == NAMES
-    for name, args in want.items():
-        assert len(vit_ops._EXPORTS[name]) == len(args), name
-        for i, (got, exp) in enumerate(zip(vit_ops._EXPORTS[name], args)):
-            assert got == exp, "%s: argument %d is %s in the binding, %s in the header" % (name, i, got.__name__, exp.__name__)
-        assert args[-1] == C.c_void_p                  # the stream comes last
-    lib = vit_ops.load()
-    for name in want:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == vit_ops._EXPORTS[name]
-    assert not (set(_lib._EXPORTS) & set(want)) and not any(hasattr(ops, n) for n in ("vit_attention", "vit_rope_split"))
-    md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert "Extension header `include/x2i_vit.h`" in md and all("`%s`" % n in md for n in want)
-
-
 def test_entry_points_validate_their_arguments_without_a_gpu():
     from x2i_amd import vit_ops
     lib = vit_ops.load()

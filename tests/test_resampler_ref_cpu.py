@@ -1,6 +1,6 @@
 """The MiniCPM-o Resampler without a GPU: the float64 restatement of tests/resampler_ref.py against the reference module's recorded
 float64 output (tests/golden/resampler_tiny.safetensors), the position table and ids, the checkers against the mistakes they are there to
-catch, the extension header include/x2i_resampler.h against its binding and the built library, and the host module's plumbing."""
+catch, the extension header include/x2i_resampler.h (its prototypes against the binding: tests/test_extension_boundary_cpu.py), and the host module's plumbing."""
 import ctypes as C
 import os
 
@@ -9,11 +9,9 @@ import torch
 from safetensors import safe_open
 
 from tests import resampler_ref as RR
-from tests.test_t5_ref_cpu import _header_prototypes  # (a helper; its tests are not re-collected here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "resampler_tiny.safetensors")
-NAMES = {"x2i_resampler_attention_bf16", "x2i_resampler_ln_pos_bf16", "x2i_resampler_kv_split_bf16"}
 RESTATEMENT_BOUND = 1e-10       # both sides float64; they differ in summation order only
 
 
@@ -144,23 +142,6 @@ def test_library_comparator_agrees_with_the_restatement_in_float64(golden):
 
 
 # ---------------------------------------------------------------------------------------------------------------- boundary
-def test_extension_header_matches_its_binding_and_the_library_exports_it():
-    from x2i_amd import _lib, ops, resampler_ops
-    want = _header_prototypes(os.path.join(ROOT, "include", "x2i_resampler.h"))
-    assert set(want) == set(resampler_ops._EXPORTS) == NAMES
-    for name, args in want.items():
-        assert len(resampler_ops._EXPORTS[name]) == len(args), name
-        for i, (got, exp) in enumerate(zip(resampler_ops._EXPORTS[name], args)):
-            assert got == exp, "%s: argument %d is %s in the binding, %s in the header" % (name, i, got.__name__, exp.__name__)
-        assert args[-1] == C.c_void_p                  # the stream comes last
-    lib = resampler_ops.load()
-    for name in want:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == resampler_ops._EXPORTS[name]
-    assert not (set(_lib._EXPORTS) & set(want)) and not any(hasattr(ops, n) for n in ("resampler_attention", "resampler_ln_pos", "resampler_kv_split"))
-    md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert "Extension header `include/x2i_resampler.h`" in md and all("`%s`" % n in md for n in want)
-
-
 def test_entry_points_validate_their_arguments_without_a_gpu():
     from x2i_amd import resampler_ops
     lib = resampler_ops.load()

@@ -1,19 +1,15 @@
 """The MiniCPM-o SigLIP vision tower without a GPU: the bucketised position ids against the library's, the float64 restatement of
 tests/siglip_ref.py against the library in float64, the zero padding of the heads and of the MLP, the packed weights of
-x2i_amd/siglip.py, the extension header include/x2i_siglip.h against its binding and the built library, every refusal, and the wiring of
+x2i_amd/siglip.py, the extension header include/x2i_siglip.h (its prototypes against the binding: tests/test_extension_boundary_cpu.py), every refusal, and the wiring of
 handoff.HipSiglip and --hip_vision."""
 import ctypes as C
-import os
 
 import pytest
 import torch
 
 from tests import siglip_ref as SR
 from tests.test_qwen_vision_ref_cpu import RESTATEMENT_BOUND  # (a constant; its tests are not re-collected here)
-from tests.test_t5_ref_cpu import _header_prototypes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"x2i_siglip_patch_rows_bf16", "x2i_siglip_add_positions_bf16", "x2i_siglip_head_split_bf16"}
 GRIDS = [(1, 1), (3, 5), (9, 9), (20, 27), (32, 32), (1, 70)]
 TINY = dict(hidden_size=144, num_attention_heads=2, num_hidden_layers=2, intermediate_size=300)
 
@@ -161,23 +157,6 @@ def test_packed_weights_are_the_zero_padded_parameters():
 
 
 # ---------------------------------------------------------------------------------------------------------------- boundary
-def test_extension_header_matches_its_binding_and_the_library_exports_it():
-    from x2i_amd import _lib, ops, siglip_ops
-    want = _header_prototypes(os.path.join(ROOT, "include", "x2i_siglip.h"))
-    assert set(want) == set(siglip_ops._EXPORTS) == NAMES
-    for name, args in want.items():
-        assert len(siglip_ops._EXPORTS[name]) == len(args), name
-        for i, (got, exp) in enumerate(zip(siglip_ops._EXPORTS[name], args)):
-            assert got == exp, "%s: argument %d is %s in the binding, %s in the header" % (name, i, got.__name__, exp.__name__)
-        assert args[-1] == C.c_void_p                  # the stream comes last
-    lib = siglip_ops.load()
-    for name in want:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == siglip_ops._EXPORTS[name]
-    assert not (set(_lib._EXPORTS) & set(want)) and not any(hasattr(ops, n) for n in ("siglip_patch_rows", "siglip_add_positions", "siglip_head_split"))
-    md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert "Extension header `include/x2i_siglip.h`" in md and all("`%s`" % n in md for n in want)
-
-
 def test_entry_points_validate_their_arguments_without_a_gpu():
     from x2i_amd import siglip_ops
     lib = siglip_ops.load()

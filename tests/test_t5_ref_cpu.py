@@ -1,17 +1,14 @@
 """CPU-side checks of the T5 encoder work (no GPU): the bias table against the library's compute_bias, the float64 restatement of the stack
 against the library in float64, the checkers of tests/t5_ref.py against the mistakes they are there to catch, the extension header
-include/x2i_t5.h against its binding and the built library, and the host modules' refusals."""
+include/x2i_t5.h (its prototypes against the binding: tests/test_extension_boundary_cpu.py), and the host modules' refusals."""
 import ctypes as C
 import math
 import os
-import re
 
 import pytest
 import torch
 
 from tests import t5_ref as TR
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _lib_stack(d_model, heads, d_kv, d_ff, layers, vocab=64):
@@ -148,47 +145,6 @@ def test_gated_gelu_checker_accepts_one_rounding_and_rejects_the_erf_form():
 
 
 # ---------------------------------------------------------------------------------------------------------------- boundary
-def _header_prototypes(path):
-    """{export: [ctypes argument types]} of every `int x2i_...(...)` prototype of a header, in the manner of tests/test_boundary_cpu.py"""
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    scalars = {"int32_t": C.c_int32, "int": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "x2i_stream_t": C.c_void_p}
-    out = {}
-    for ret, name, params in re.findall(r"^(int|int64_t|const char\*)\s+(x2i_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-        assert ret == "int", name
-        args = []
-        for p in " ".join(params.split()).split(","):
-            words = [w for w in p.replace("*", " * ").split() if w != "const"]
-            assert len(words) >= 2, p                  # a type and a name
-            words = words[:-1] if words[-1] != "*" else words
-            args.append(C.c_void_p if "*" in words else scalars[words[0]])
-        out[name] = args
-    return out
-
-
-def test_extension_header_matches_its_binding_and_the_library_exports_it():
-    from x2i_amd import _lib, t5_ops
-    want = _header_prototypes(os.path.join(ROOT, "include", "x2i_t5.h"))
-    assert set(want) == set(t5_ops._EXPORTS) == {"x2i_t5_attention_bf16", "x2i_t5_head_split_bf16", "x2i_t5_rms_rows_bf16", "x2i_t5_gated_gelu_bf16"}
-    for name, args in want.items():
-        assert len(t5_ops._EXPORTS[name]) == len(args), name
-        for i, (got, exp) in enumerate(zip(t5_ops._EXPORTS[name], args)):
-            assert got == exp, "%s: argument %d is %s in the binding, %s in the header" % (name, i, got.__name__, exp.__name__)
-        assert args[-1] == C.c_void_p                  # the stream comes last
-    lib = t5_ops.load()
-    for name in want:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == t5_ops._EXPORTS[name]
-    # the closed table of include/x2i.h is as it was
-    base = _header_prototypes_any(os.path.join(ROOT, "include", "x2i.h"))
-    assert len(base) == 80 and not (set(base) & set(want)) and not (set(_lib._EXPORTS) & set(want))
-    md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert all("`%s`" % n in md for n in want)
-
-
-def _header_prototypes_any(path):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return set(re.findall(r"^(?:int|int64_t|const char\*)\s+(x2i_\w+)\s*\([^)]*\)\s*;", text, flags=re.M))
-
-
 def test_entry_points_validate_their_arguments_without_a_gpu():
     from x2i_amd import t5_ops
     lib = t5_ops.load()

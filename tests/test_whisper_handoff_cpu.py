@@ -1,17 +1,13 @@
 """The MiniCPM-o Whisper audio tower without a GPU: the parameter names and the packed storage of x2i_amd/whisper.py, the plan's arithmetic,
-every refusal, the extension header include/x2i_whisper.h against its binding and the built library, and the wiring of handoff.HipAudio,
+every refusal, the extension header include/x2i_whisper.h (its prototypes against the binding: tests/test_extension_boundary_cpu.py), and the wiring of handoff.HipAudio,
 MiniCPMConditioner(hip_audio=True) and --hip_audio."""
 import ctypes as C
-import os
 
 import pytest
 import torch
 
 from tests import whisper_ref as WR
-from tests.test_t5_ref_cpu import _header_prototypes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"x2i_whisper_mel_rows_bf16", "x2i_whisper_pool_rows_bf16"}
 TINY = dict(d_model=128, encoder_attention_heads=2, encoder_ffn_dim=256, encoder_layers=2, max_source_positions=150, embed_dim=96, pool_step=2)
 
 
@@ -144,23 +140,6 @@ def test_refusals():
 
 
 # ---------------------------------------------------------------------------------------------------------------- boundary
-def test_extension_header_matches_its_binding_and_the_library_exports_it():
-    from x2i_amd import _lib, ops, whisper_ops
-    want = _header_prototypes(os.path.join(ROOT, "include", "x2i_whisper.h"))
-    assert set(want) == set(whisper_ops._EXPORTS) == NAMES
-    for name, args in want.items():
-        assert len(whisper_ops._EXPORTS[name]) == len(args), name
-        for i, (got, exp) in enumerate(zip(whisper_ops._EXPORTS[name], args)):
-            assert got == exp, "%s: argument %d is %s in the binding, %s in the header" % (name, i, got.__name__, exp.__name__)
-        assert args[-1] == C.c_void_p                  # the stream comes last
-    lib = whisper_ops.load()
-    for name in want:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == whisper_ops._EXPORTS[name]
-    assert not (set(_lib._EXPORTS) & set(want)) and not any(hasattr(ops, n) for n in ("mel_rows", "pool_rows"))
-    md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert "Extension header `include/x2i_whisper.h`" in md and all("`%s`" % n in md for n in want)
-
-
 def test_entry_points_validate_their_arguments_without_a_gpu():
     from x2i_amd import whisper_ops
     lib = whisper_ops.load()

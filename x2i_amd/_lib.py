@@ -176,18 +176,29 @@ def load():
     return lib
 
 
-def bind_extension(lib, exports, header_name):
-    """Set the prototypes of an extension header on lib, the CDLL object of load(); the caller does so once per CDLL object.  exports:
-    name -> argtypes, all returning int; such entry points are not in _EXPORTS (include/x2i.h's table is closed under its ABI version), so a
-    missing symbol means a stale build."""
-    for name, argtypes in exports.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise X2IError("x2i_amd: %s does not export %s (include/%s) (stale build? run `python -m x2i_amd.build`)" % (LIB_PATH, name, header_name))
-        fn.argtypes = argtypes
-        fn.restype = C.c_int
-    return lib
+def extension(header_name, exports):
+    """The load() of an extension header's binding module: a callable that returns the library of load() with the header's prototypes set.
+    exports: name -> argtypes, all returning int; such entry points are not in _EXPORTS (include/x2i.h's table is closed under its ABI
+    version), so they get their argtypes on the CDLL object the first time the callable is used, again whenever load() returns another
+    object, and a missing symbol means a stale build."""
+    bound = None
+
+    def load_extension():
+        nonlocal bound
+        lib = load()        # the module attribute, looked up on every call
+        if bound is not lib:
+            for name, argtypes in exports.items():
+                try:
+                    fn = getattr(lib, name)
+                except AttributeError:
+                    raise X2IError("x2i_amd: %s does not export %s (include/%s) (stale build? run `python -m x2i_amd.build`)"
+                                   % (LIB_PATH, name, header_name))
+                fn.argtypes = argtypes
+                fn.restype = C.c_int
+            bound = lib
+        return lib
+
+    return load_extension
 
 
 def pad64(n):

@@ -9,37 +9,11 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------------------------- patch rows
-// One thread per 16-byte chunk of Xp.  Column col = ci*P*P + y*P + x of row b*L + r*gw + q is img[b][ci][r*P + y][q*P + x]: (ci, y, x) is
-// divided out once per chunk and then carried.  A patch row starts at a multiple of P elements (28 bytes for P = 14), so the image is read
-// element by element (consecutive lanes read consecutive 16-byte runs of one image row most of the time); columns >= 3*P*P are zero.
+// patch_rows_body (encoder_common.h) on the gh x gw grid of a tile
 __global__ __launch_bounds__(256) void internvit_patch_rows_kernel(const bf16_t* __restrict__ img, long long ibs, long long ics, long long ild,
                                                                    bf16_t* __restrict__ Xp, long long ldx, long long rows, int L, int gw, int P,
                                                                    int Kp) {
-  const int nc = Kp >> 3, PP = P * P, K3 = 3 * PP;
-  const long long total = rows * nc;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const long long row = i / nc;
-    const int ch = (int)(i - row * nc);
-    const long long b = row / L;
-    const int p = (int)(row - b * L);
-    const int r = p / gw, q = p - r * gw;
-    const bf16_t* src = img + b * ibs + (long long)r * P * ild + (long long)q * P;
-    int col = ch * 8;
-    int ci = col / PP;
-    int y = (col - ci * PP) / P;
-    int x = col - ci * PP - y * P;
-    bf16_t e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j, ++col) {
-      e[j] = col < K3 ? src[ci * ics + y * ild + x] : (bf16_t)0;
-      if (++x == P) {
-        x = 0;
-        if (++y == P) { y = 0; ++ci; }
-      }
-    }
-    *(uint4*)(Xp + row * ldx + ch * 8) = make_uint4(e[0] | ((uint32_t)e[1] << 16), e[2] | ((uint32_t)e[3] << 16), e[4] | ((uint32_t)e[5] << 16),
-                                                   e[6] | ((uint32_t)e[7] << 16));
-  }
+  patch_rows_body(img, ibs, ics, ild, Xp, ldx, rows, L, gw, P, Kp);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- embeddings
@@ -127,8 +101,6 @@ __global__ __launch_bounds__(256) void internvit_shuffle_ln_kernel(const bf16_t*
     }
   }
 }
-
-inline unsigned chunk_blocks(long long chunks) { return (unsigned)((chunks + 255) / 256 < 8192 ? (chunks + 255) / 256 : 8192); }
 
 }  // namespace
 

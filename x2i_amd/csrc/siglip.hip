@@ -9,38 +9,11 @@
 
 namespace {
 
-inline int stored_width(int dk) { return dk == 80 ? 128 : dk; }   // heads of 80 are stored 128 wide (include/x2i_vit.h)
-
 // ------------------------------------------------------------------------------------------------------------------- patch rows
-// One thread per 16-byte chunk of Xp.  Column col = ci*P*P + r*P + c of row b*L + p is strips[b][ci][r][P*p + c]: (ci, r, c) is divided out
-// once per chunk and then carried.  A patch starts at a multiple of P elements (28 bytes for P = 14), so the strip is read element by
-// element; columns >= 3*P*P are zero.
+// patch_rows_body (encoder_common.h) on a grid of one row of L patches: column ci*P*P + r*P + c of row b*L + p is strips[b][ci][r][P*p + c]
 __global__ __launch_bounds__(256) void siglip_patch_rows_kernel(const bf16_t* __restrict__ strips, long long sbs, long long sld,
                                                                 bf16_t* __restrict__ Xp, long long ldx, long long rows, int L, int P, int Kp) {
-  const int nc = Kp >> 3, PP = P * P, K3 = 3 * PP;
-  const long long total = rows * nc;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const long long row = i / nc;
-    const int ch = (int)(i - row * nc);
-    const long long b = row / L;
-    const int p = (int)(row - b * L);
-    const bf16_t* src = strips + b * sbs + (long long)P * p;
-    int col = ch * 8;
-    int ci = col / PP;
-    int r = (col - ci * PP) / P;
-    int c = col - ci * PP - r * P;
-    bf16_t e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j, ++col) {
-      e[j] = col < K3 ? src[(long long)(ci * P + r) * sld + c] : (bf16_t)0;
-      if (++c == P) {
-        c = 0;
-        if (++r == P) { r = 0; ++ci; }
-      }
-    }
-    *(uint4*)(Xp + row * ldx + ch * 8) = make_uint4(e[0] | ((uint32_t)e[1] << 16), e[2] | ((uint32_t)e[3] << 16), e[4] | ((uint32_t)e[5] << 16),
-                                                   e[6] | ((uint32_t)e[7] << 16));
-  }
+  patch_rows_body(strips, sbs, P * sld, sld, Xp, ldx, rows, L, L, P, Kp);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- position embedding
@@ -66,29 +39,12 @@ __global__ __launch_bounds__(256) void siglip_add_positions_kernel(bf16_t* __res
 }
 
 // ------------------------------------------------------------------------------------------------------------------- head split
-// t5_head_split_kernel with heads stored dkp >= dk wide: one workgroup per (64-token tile, head, sample); Q and K rows are 16-byte copies
-// into rows of dkp elements, V goes through v_tile_to_vt into the head's dkp V^T rows.  Only d < dk and s < S are written.
+// head_split_body (encoder_common.h) with heads stored dkp >= dk wide, as x2i_vit_attention_bf16 reads them
 __global__ __launch_bounds__(256) void siglip_head_split_kernel(const bf16_t* __restrict__ qkv, long long ld, bf16_t* __restrict__ Q,
                                                                 bf16_t* __restrict__ K, bf16_t* __restrict__ VT, int S, int Spad, int H, int dk,
                                                                 int dkp) {
-  const int tid = threadIdx.x;
-  const int s0 = blockIdx.x * 64, h = blockIdx.y, b = blockIdx.z;
-  const int ck = dk >> 3;           // 16-byte chunks per head row
-  const long long bh = (long long)b * H + h;
-  const int inner = H * dk;
-  for (int c = tid; c < 64 * ck; c += 256) {
-    const int tok = c / ck, ch = c - tok * ck;
-    const int s = s0 + tok;
-    if (s >= S) continue;
-    const bf16_t* src = qkv + ((long long)b * S + s) * ld + h * dk + ch * 8;
-    const long long dst = (bh * Spad + s) * dkp + ch * 8;
-    *(uint4*)(Q + dst) = *(const uint4*)src;
-    *(uint4*)(K + dst) = *(const uint4*)(src + inner);
-  }
-  v_tile_to_vt(qkv + (long long)b * S * ld + 2 * inner + h * dk, ld, VT + bh * dkp * Spad, s0, S, Spad, dk);
+  head_split_body(qkv, ld, Q, K, VT, S, Spad, H, dk, dkp);
 }
-
-inline unsigned chunk_blocks(long long chunks) { return (unsigned)((chunks + 255) / 256 < 8192 ? (chunks + 255) / 256 : 8192); }
 
 }  // namespace
 

@@ -9,24 +9,10 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------------------------- head split
-// One workgroup per (64-token tile, head, sample).  Q and K rows are 16-byte copies; V goes through v_tile_to_vt.
+// head_split_body (encoder_common.h) with the heads stored at their own width
 __global__ __launch_bounds__(256) void t5_head_split_kernel(const bf16_t* __restrict__ qkv, long long ld, bf16_t* __restrict__ Q, bf16_t* __restrict__ K,
                                                             bf16_t* __restrict__ VT, int S, int Spad, int H, int dk) {
-  const int tid = threadIdx.x;
-  const int s0 = blockIdx.x * 64, h = blockIdx.y, b = blockIdx.z;
-  const int ck = dk >> 3;           // 16-byte chunks per head row
-  const long long bh = (long long)b * H + h;
-  const int inner = H * dk;
-  for (int c = tid; c < 64 * ck; c += 256) {
-    const int tok = c / ck, ch = c - tok * ck;
-    const int s = s0 + tok;
-    if (s >= S) continue;
-    const bf16_t* src = qkv + ((long long)b * S + s) * ld + h * dk + ch * 8;
-    const long long dst = (bh * Spad + s) * dk + ch * 8;
-    *(uint4*)(Q + dst) = *(const uint4*)src;
-    *(uint4*)(K + dst) = *(const uint4*)(src + inner);
-  }
-  v_tile_to_vt(qkv + (long long)b * S * ld + 2 * inner + h * dk, ld, VT + bh * dk * Spad, s0, S, Spad, dk);
+  head_split_body(qkv, ld, Q, K, VT, S, Spad, H, dk, dk);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- T5LayerNorm

@@ -8,8 +8,6 @@
 
 namespace {
 
-inline int stored_width(int dk) { return dk == 80 ? 128 : dk; }   // heads of 80 are stored 128 wide (include/x2i_vit.h)
-
 // RoPE + head split: rope_split_body of encoder_common.h (qwen.hip's kernel) with as many key/value heads as query heads -- [q | k | v] of
 // nn.Linear(dim, 3 dim) is its column layout at Hq = Hkv = H -- and heads stored dkp wide.  dk / 2 = 40 is five groups of eight pairs.
 __global__ __launch_bounds__(256) void vit_rope_split_kernel(const bf16_t* __restrict__ qkv, long long ld, const float* __restrict__ cs,

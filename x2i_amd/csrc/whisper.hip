@@ -79,8 +79,6 @@ __global__ __launch_bounds__(256) void whisper_pool_rows_kernel(const bf16_t* __
   }
 }
 
-inline unsigned chunk_blocks(long long chunks) { return (unsigned)((chunks + 255) / 256 < 8192 ? (chunks + 255) / 256 : 8192); }
-
 }  // namespace
 
 extern "C" {

@@ -87,6 +87,40 @@ class HiddenStateSlab:
         return self.slab
 
 
+class _Patch:
+    """Attribute `name` of obj replaced ON THE INSTANCE by a callable: install() (idempotent, returns self) sets it and remove() (idempotent)
+    puts back what the instance's own __dict__ held, or deletes the attribute where it held none, so that the class's attribute shows
+    again.  `_original` is what getattr gave at install (the bound method the replacement may fall back to).  Also a context manager,
+    which restores on exceptions too.  The hand-offs below derive from it."""
+    _installed = False
+
+    def __init__(self, obj, name, replacement):
+        self._patched = (obj, name, replacement)
+
+    def install(self):
+        if not self._installed:
+            obj, name, replacement = self._patched
+            self._had, self._saved, self._original = name in obj.__dict__, obj.__dict__.get(name), getattr(obj, name, None)
+            setattr(obj, name, replacement)
+            self._installed = True
+        return self
+
+    def remove(self):
+        if self._installed:
+            obj, name, _ = self._patched
+            if self._had:
+                setattr(obj, name, self._saved)
+            else:
+                delattr(obj, name)
+            self._installed = False
+
+    def __enter__(self):
+        return self.install()
+
+    def __exit__(self, *exc):
+        self.remove()
+
+
 class HipPrefill:
     """HiddenStateSlab's `prefill(model, **inputs)` / `capture(run)` with the decoder stack itself on the HIP path (x2i_amd/qwen.py:
     Qwen2DecoderStack, a bf16 copy of the decoder's weights on its device; the token table is shared).  During the call the decoder
@@ -127,16 +161,8 @@ class HipPrefill:
     @torch.no_grad()
     def capture(self, run):
         self.slab = None
-        had = "forward" in self.decoder.__dict__
-        saved = self.decoder.__dict__.get("forward")
-        self.decoder.forward = self._forward
-        try:
+        with _Patch(self.decoder, "forward", self._forward):
             run()
-        finally:
-            if had:
-                self.decoder.forward = saved
-            else:
-                del self.decoder.forward
         if self.slab is None:
             raise RuntimeError("handoff: the decoder stack did not run")
         slab, self.slab = self.slab, None
@@ -381,16 +407,8 @@ class HipGenerate:
             self.stack.pack_w8()
         self.slab = self._cache = None
         self._new_tokens = max_new_tokens
-        had = "forward" in self.decoder.__dict__
-        saved = self.decoder.__dict__.get("forward")
-        self.decoder.forward = self._forward
-        try:
+        with _Patch(self.decoder, "forward", self._forward):
             out = model(**inputs, use_cache=False)
-        finally:
-            if had:
-                self.decoder.forward = saved
-            else:
-                del self.decoder.forward
         if self.slab is None:
             raise RuntimeError("handoff: the decoder stack did not run")
         prompt, cache, self.slab, self._cache = self.slab, self._cache, None, None
@@ -554,7 +572,7 @@ def find_visual(model):
     raise RuntimeError("handoff: no vision tower (model.visual / model.model.visual) found in %s" % type(model).__name__)
 
 
-class HipVision:
+class HipVision(_Patch):
     """The vision tower behind `model.visual` on the HIP path (x2i_amd/qwen_vision.py: Qwen2_5VisionTower, a bf16 copy of the tower's weights on
     its device).  install() replaces the tower module's `forward` ON THE INSTANCE and remove() restores it; between the two the surrounding
     model's get_image_features / get_video_features and its embedding merge run as they always do and get the library's output object from
@@ -565,33 +583,11 @@ class HipVision:
         self.visual = find_visual(model)
         self.tower = Qwen2_5VisionTower.from_hf(self.visual)
         self.calls = 0
-        self._installed = False
+        _Patch.__init__(self, self.visual, "forward", self._forward)
 
     def _forward(self, hidden_states, grid_thw=None, **kw):
         self.calls += 1
         return self.tower(hidden_states, grid_thw=grid_thw)
-
-    def install(self):
-        if not self._installed:
-            self._had = "forward" in self.visual.__dict__
-            self._saved = self.visual.__dict__.get("forward")
-            self.visual.forward = self._forward
-            self._installed = True
-        return self
-
-    def remove(self):
-        if self._installed:
-            if self._had:
-                self.visual.forward = self._saved
-            else:
-                del self.visual.forward
-            self._installed = False
-
-    def __enter__(self):
-        return self.install()
-
-    def __exit__(self, *exc):
-        self.remove()
 
 
 def find_vpm(model):
@@ -602,7 +598,7 @@ def find_vpm(model):
     raise RuntimeError("handoff: no vision tower (model.vpm) found in %s" % type(model).__name__)
 
 
-class HipSiglip:
+class HipSiglip(_Patch):
     """The vision tower behind `model.vpm` on the HIP path (x2i_amd/siglip.py: SiglipVisionTower, a bf16 copy of the tower's weights on its
     device).  HipVision's interface: install() replaces the tower module's `forward` ON THE INSTANCE and remove() restores it; between the
     two the surrounding model's get_vllm_embedding, its Resampler (the model's own, or HipResampler's when that is installed too) and its
@@ -614,33 +610,11 @@ class HipSiglip:
         self.vpm = find_vpm(model)
         self.tower = SiglipVisionTower.from_hf(self.vpm)
         self.calls = 0
-        self._installed = False
+        _Patch.__init__(self, self.vpm, "forward", self._forward)
 
     def _forward(self, pixel_values, patch_attention_mask=None, tgt_sizes=None, **kw):
         self.calls += 1
         return self.tower(pixel_values, patch_attention_mask=patch_attention_mask, tgt_sizes=tgt_sizes)
-
-    def install(self):
-        if not self._installed:
-            self._had = "forward" in self.vpm.__dict__
-            self._saved = self.vpm.__dict__.get("forward")
-            self.vpm.forward = self._forward
-            self._installed = True
-        return self
-
-    def remove(self):
-        if self._installed:
-            if self._had:
-                self.vpm.forward = self._saved
-            else:
-                del self.vpm.forward
-            self._installed = False
-
-    def __enter__(self):
-        return self.install()
-
-    def __exit__(self, *exc):
-        self.remove()
 
 
 def find_resampler(model):
@@ -651,7 +625,7 @@ def find_resampler(model):
     raise RuntimeError("handoff: no resampler (model.resampler) found in %s" % type(model).__name__)
 
 
-class HipResampler:
+class HipResampler(_Patch):
     """The perceiver behind `model.resampler` on the HIP path (x2i_amd/resampler.py: Resampler, a bf16 copy of the module's weights on its
     device).  HipSiglip's interface: install() replaces the module's `forward` ON THE INSTANCE and remove() restores it; between the two
     the surrounding model's get_vllm_embedding and its embedding scatter run as they always do and get a [B, NQ, D] tensor from the HIP
@@ -662,33 +636,11 @@ class HipResampler:
         self.module = find_resampler(model)
         self.resampler = Resampler.from_hf(self.module)
         self.calls = 0
-        self._installed = False
+        _Patch.__init__(self, self.module, "forward", self._forward)
 
     def _forward(self, x, tgt_sizes=None, **kw):
         self.calls += 1
         return self.resampler(x, tgt_sizes=tgt_sizes)
-
-    def install(self):
-        if not self._installed:
-            self._had = "forward" in self.module.__dict__
-            self._saved = self.module.__dict__.get("forward")
-            self.module.forward = self._forward
-            self._installed = True
-        return self
-
-    def remove(self):
-        if self._installed:
-            if self._had:
-                self.module.forward = self._saved
-            else:
-                del self.module.forward
-            self._installed = False
-
-    def __enter__(self):
-        return self.install()
-
-    def __exit__(self, *exc):
-        self.remove()
 
 
 def find_apm(model):
@@ -699,7 +651,7 @@ def find_apm(model):
     raise RuntimeError("handoff: no audio tower (model.apm) found in %s" % type(model).__name__)
 
 
-class HipAudio:
+class HipAudio(_Patch):
     """The audio tower behind `model.apm`, with `model.audio_projection_layer` and `model.audio_avg_pooler`, on the HIP path
     (x2i_amd/whisper.py: WhisperAudioTower, a bf16 copy of the modules' weights on their device).  The model's `apm` is never called as a
     module for this -- get_audio_embedding builds the mask and picks hidden_states[-1] itself -- so install() replaces
@@ -725,7 +677,7 @@ class HipAudio:
             raise RuntimeError("handoff: no pooling step (model.config.audio_pool_step / model.audio_avg_pooler) found in %s" % type(model).__name__)
         self.tower = WhisperAudioTower.from_hf(self.apm, proj, int(step))
         self.calls = 0
-        self._installed = False
+        _Patch.__init__(self, self.model, "get_audio_embedding", self._get_audio_embedding)
 
     def _get_audio_embedding(self, data, chunk_length=-1, dummy=True):
         model = self.model
@@ -747,29 +699,6 @@ class HipAudio:
             final.append(mine)
         return final
 
-    def install(self):
-        if not self._installed:
-            self._had = "get_audio_embedding" in self.model.__dict__
-            self._saved = self.model.__dict__.get("get_audio_embedding")
-            self._original = self.model.get_audio_embedding
-            self.model.get_audio_embedding = self._get_audio_embedding
-            self._installed = True
-        return self
-
-    def remove(self):
-        if self._installed:
-            if self._had:
-                self.model.get_audio_embedding = self._saved
-            else:
-                del self.model.get_audio_embedding
-            self._installed = False
-
-    def __enter__(self):
-        return self.install()
-
-    def __exit__(self, *exc):
-        self.remove()
-
 
 def find_extract_feature(model):
     """What extract_feature of an InternVL2.5 chat model runs: (`model.vision_model`, `model.mlp1`), of a model that has the method"""
@@ -779,7 +708,7 @@ def find_extract_feature(model):
     raise RuntimeError("handoff: no extract_feature with model.vision_model and model.mlp1 found in %s" % type(model).__name__)
 
 
-class HipInternVision:
+class HipInternVision(_Patch):
     """What `extract_feature` of an InternVL2.5 chat model computes -- `model.vision_model` (InternViT), the class token dropped,
     pixel_shuffle and `model.mlp1` -- on the HIP path (x2i_amd/internvit.py: InternVLVision over an InternVisionTower, a bf16 copy of the
     modules' weights on their device).  The shuffle and mlp1 live in the chat model and not in vision_model, so install() replaces
@@ -798,36 +727,13 @@ class HipInternVision:
         self.vision = InternVLVision(InternVisionTower.from_hf(vision_model), mlp1, downsample_ratio=pick("downsample_ratio", 0.5),
                                      ps_version=pick("ps_version", "v2"), select_layer=pick("select_layer", -1), graph=graph)
         self.calls = 0
-        self._installed = False
+        _Patch.__init__(self, self.model, "extract_feature", self._extract_feature)
 
     def _extract_feature(self, pixel_values):
         if self.model.training:
             return self._original(pixel_values)
         self.calls += 1
         return self.vision(pixel_values)
-
-    def install(self):
-        if not self._installed:
-            self._had = "extract_feature" in self.model.__dict__
-            self._saved = self.model.__dict__.get("extract_feature")
-            self._original = self.model.extract_feature
-            self.model.extract_feature = self._extract_feature
-            self._installed = True
-        return self
-
-    def remove(self):
-        if self._installed:
-            if self._had:
-                self.model.extract_feature = self._saved
-            else:
-                del self.model.extract_feature
-            self._installed = False
-
-    def __enter__(self):
-        return self.install()
-
-    def __exit__(self, *exc):
-        self.remove()
 
 
 def generate_positions(attention_mask, pad_position=0):
@@ -840,7 +746,7 @@ def generate_positions(attention_mask, pad_position=0):
     return (attention_mask.long().cumsum(-1) - 1).masked_fill_(attention_mask == 0, pad_position)
 
 
-class _PromptHandoff:
+class _PromptHandoff(_Patch):
     """What the two prompt hand-offs share: the decoder stack on the HIP path called DIRECTLY -- not through the surrounding causal LM, so no
     lm_head runs on the prompt -- and HipAudio's interface around it: install() replaces `generate` ON THE INSTANCE by one prompt pass and
     remove() restores it; also a context manager, which restores on exceptions too."""
@@ -859,29 +765,7 @@ class _PromptHandoff:
         self.n_layers = len(self.decoder.layers)
         self.C = self.n_layers + 1
         self.calls = 0
-        self._installed = False
-
-    def install(self):
-        if not self._installed:
-            self._had = "generate" in self.model.__dict__
-            self._saved = self.model.__dict__.get("generate")
-            self.model.generate = self._generate
-            self._installed = True
-        return self
-
-    def remove(self):
-        if self._installed:
-            if self._had:
-                self.model.generate = self._saved
-            else:
-                del self.model.generate
-            self._installed = False
-
-    def __enter__(self):
-        return self.install()
-
-    def __exit__(self, *exc):
-        self.remove()
+        _Patch.__init__(self, self.model, "generate", self._generate)
 
 
 class HipInternVLPrompt(_PromptHandoff):

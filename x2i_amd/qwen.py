@@ -283,10 +283,7 @@ class Qwen2DecoderStack(PackedModule):
         """forward's launches; with a cache (prefill) rope_split and the attention run with Spad = cap on the cache's own per-layer K / V^T, and
         the cache's ranges and next positions are set: the same kernels on the same values, so the slab is bit-identical.
         embed_scale: what the token rows (not the feature rows) are multiplied by, one f32 multiply and one rounding (MiniCPM's scale_emb)."""
-        if (input_ids is None) == (inputs_embeds is None):
-            raise ValueError("Qwen2DecoderStack: pass exactly one of input_ids and inputs_embeds")
-        if merge is not None and input_ids is None:
-            raise ValueError("Qwen2DecoderStack: merge= goes with input_ids (with inputs_embeds the merge has been done)")
+        self._one_input(inputs_embeds, input_ids, merge)
         c = self.config
         D, dk, Hq, Hkv = c.hidden_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads
         nq, C = Hq * dk, len(self.layers) + 1
@@ -310,22 +307,40 @@ class Qwen2DecoderStack(PackedModule):
         dev = QKV.device
         if cache is not None:
             Q, Spad = cache.Q, cache.cap
-        if position_ids is None:
-            position_ids = ws["arange"]
-        elif position_ids.dim() == 3 and position_ids.shape[0] == 4:
-            position_ids = position_ids[1:]
-        if position_ids.dim() == 3 and c.mrope_section is None:
-            raise ValueError("x2i_amd Qwen2DecoderStack: three position axes need an mrope_section in the configuration")
+        position_ids = ws["arange"] if position_ids is None else self._position_axes(position_ids)
         if tuple(position_ids.shape[-2:]) != (B, S):
             position_ids = position_ids.expand(*position_ids.shape[:-2], B, S)
         cos, sin = rope_tables(position_ids.to(dev), dk, c.rope_theta, c.mrope_section, _scratch=ws["rope"])
         if cache is not None:
             cache._set_prompt(S, k_lo, k_hi, attention_mask, position_ids.to(dev))
         slab = torch.empty((B, C, S, D), device=dev, dtype=torch.bfloat16)
+        self._write_entry0(slab, ws, inputs_embeds, input_ids, merge, embed_scale)
+        scale = dk ** -0.5
+        kv = (lambda i: (cache.K[i], cache.VT[i])) if cache is not None else (lambda i: (K, VT))
+        return self._layers(slab, ws, lambda i: qwen_ops.rope_split(QKV, cos, sin, Q, *kv(i), B, S, Spad, Hq, Hkv, dk),
+                            lambda i: qwen_ops.attention(Q, *kv(i), ATT, B, Hq, Hkv, S, Spad, dk, scale, nq, S * nq, k_lo, k_hi))
+
+    @staticmethod
+    def _one_input(inputs_embeds, input_ids, merge=None):
+        if (input_ids is None) == (inputs_embeds is None):
+            raise ValueError("Qwen2DecoderStack: pass exactly one of input_ids and inputs_embeds")
+        if merge is not None and input_ids is None:
+            raise ValueError("Qwen2DecoderStack: merge= goes with input_ids (with inputs_embeds the merge has been done)")
+
+    def _position_axes(self, position_ids):
+        """Of four position axes the first (the text positions the library builds its mask from) is dropped; three need an mrope_section"""
+        if position_ids.dim() == 3 and position_ids.shape[0] == 4:
+            position_ids = position_ids[1:]
+        if position_ids.dim() == 3 and self.config.mrope_section is None:
+            raise ValueError("x2i_amd Qwen2DecoderStack: three position axes need an mrope_section in the configuration")
+        return position_ids
+
+    def _write_entry0(self, slab, ws, inputs_embeds, input_ids, merge, embed_scale):
+        """Entry 0 of the slab, for a prompt or a chunk: the token lookup and the embedding merge are ONE launch (without a plan: every row
+        a table row, ws's merge_err set by an id outside the table); inputs_embeds are copied."""
         if input_ids is not None:
-            if input_ids.device != dev:
+            if input_ids.device != slab.device:
                 raise ops._lib.X2IError("x2i_amd: input_ids must live on the model's device (got %s)" % input_ids.device)
-            # the token lookup and the embedding merge are ONE launch that writes entry 0 (without a plan: every row a table row)
             if merge is not None:
                 merge.launch(slab[:, 0], input_ids, self.embed_tokens.weight, embed_scale)
             else:
@@ -333,10 +348,10 @@ class Qwen2DecoderStack(PackedModule):
         else:
             ops._req(inputs_embeds, torch.bfloat16, "inputs_embeds")
             slab[:, 0].copy_(inputs_embeds)
-        scale = dk ** -0.5
-        kv = (lambda i: (cache.K[i], cache.VT[i])) if cache is not None else (lambda i: (K, VT))
-        return self._layers(slab, ws, lambda i: qwen_ops.rope_split(QKV, cos, sin, Q, *kv(i), B, S, Spad, Hq, Hkv, dk),
-                            lambda i: qwen_ops.attention(Q, *kv(i), ATT, B, Hq, Hkv, S, Spad, dk, scale, nq, S * nq, k_lo, k_hi))
+
+    def _own(self, cache, method):
+        if not isinstance(cache, Qwen2DecodeCache) or cache.owner() is not self:
+            raise ValueError("x2i_amd Qwen2DecoderStack.%s: the cache must come from this stack's new_cache()" % method)
 
     def _layers(self, slab, ws, rope_split, attention):
         """The launches of every layer and the final norm over the rows of slab [B, C, S, D], whose entry 0 is written: the residual stream
@@ -378,8 +393,7 @@ class Qwen2DecoderStack(PackedModule):
         Spad = cap on the cache's own per-layer K / V^T.  Sets the cache's key ranges (from the mask) and every sample's next position: one
         more than the largest position id of its valid tokens over all axes -- for plain Qwen2 the count of valid tokens, for Qwen2.5-VL what
         the library's rope_deltas yields.  Refuses S + 1 > cap."""
-        if not isinstance(cache, Qwen2DecodeCache) or cache.owner() is not self:
-            raise ValueError("x2i_amd Qwen2DecoderStack.prefill: the cache must come from this stack's new_cache()")
+        self._own(cache, "prefill")
         return self._prompt_pass(cache, inputs_embeds, input_ids, attention_mask, position_ids, check_mask, merge, embed_scale)
 
     @torch.no_grad()
@@ -397,14 +411,10 @@ class Qwen2DecoderStack(PackedModule):
         (include/x2i_qwen_extend.h) on cache.Q / K[i] / VT[i]; inputs_embeds, input_ids, merge and embed_scale as forward's, for the
         chunk."""
         from . import qwen_extend_ops as qx
-        if not isinstance(cache, Qwen2DecodeCache) or cache.owner() is not self:
-            raise ValueError("x2i_amd Qwen2DecoderStack.extend: the cache must come from this stack's new_cache()")
+        self._own(cache, "extend")
         if cache.steps is None:
             raise ValueError("x2i_amd Qwen2DecoderStack.extend: prefill(cache, ...) comes first")
-        if (input_ids is None) == (inputs_embeds is None):
-            raise ValueError("Qwen2DecoderStack: pass exactly one of input_ids and inputs_embeds")
-        if merge is not None and input_ids is None:
-            raise ValueError("Qwen2DecoderStack: merge= goes with input_ids (with inputs_embeds the merge has been done)")
+        self._one_input(inputs_embeds, input_ids, merge)
         if position_ids is None:
             raise ValueError("x2i_amd Qwen2DecoderStack.extend: position_ids of the chunk are required (the position is not the slot)")
         keep = int(keep)
@@ -416,10 +426,7 @@ class Qwen2DecoderStack(PackedModule):
         if cache.B != B or n < 1 or keep + n + 1 > cache.cap:
             raise ValueError("x2i_amd Qwen2DecoderStack.extend: a chunk of [B, n] = [%d, %d] at slot keep = %d does not fit a cache of B = %d, "
                              "cap = %d (n >= 1, keep + n + 1 <= cap)" % (B, n, keep, cache.B, cache.cap))
-        if position_ids.dim() == 3 and position_ids.shape[0] == 4:
-            position_ids = position_ids[1:]
-        if position_ids.dim() == 3 and c.mrope_section is None:
-            raise ValueError("x2i_amd Qwen2DecoderStack: three position axes need an mrope_section in the configuration")
+        position_ids = self._position_axes(position_ids)
         if position_ids.dim() not in (2, 3) or tuple(position_ids.shape[-2:]) != (B, n):
             raise ValueError("x2i_amd Qwen2DecoderStack.extend: position_ids must be [B, n] = [%d, %d], or [3, B, n] / [4, B, n] (got %s)"
                              % (B, n, tuple(position_ids.shape)))
@@ -435,16 +442,7 @@ class Qwen2DecoderStack(PackedModule):
         cos, sin = rope_tables(position_ids, dk, c.rope_theta, c.mrope_section, _scratch=ws["rope"])
         cache._set_extension(keep, n, position_ids)
         slab = torch.empty((B, L + 1, n, D), device=dev, dtype=torch.bfloat16)
-        if input_ids is not None:
-            if input_ids.device != dev:
-                raise ops._lib.X2IError("x2i_amd: input_ids must live on the model's device (got %s)" % input_ids.device)
-            if merge is not None:
-                merge.launch(slab[:, 0], input_ids, self.embed_tokens.weight, embed_scale)
-            else:
-                merge_ops.embed_merge(slab[:, 0], ws["merge_err"], ids=input_ids.contiguous(), table=self.embed_tokens.weight, scale=embed_scale)
-        else:
-            ops._req(inputs_embeds, torch.bfloat16, "inputs_embeds")
-            slab[:, 0].copy_(inputs_embeds)
+        self._write_entry0(slab, ws, inputs_embeds, input_ids, merge, embed_scale)
         QKV, ATT, nq, cap, scale = ws["QKV"], ws["ATT"], Hq * dk, cache.cap, dk ** -0.5
         return self._layers(slab, ws, lambda i: qx.rope_split(QKV, cos, sin, cache.Q, cache.K[i], cache.VT[i], B, keep, n, cap, Hq, Hkv, dk),
                             lambda i: qx.attention(cache.Q, cache.K[i], cache.VT[i], ATT, B, Hq, Hkv, keep, n, cap, dk, scale, nq, n * nq, cache.k_lo))
@@ -465,10 +463,8 @@ class Qwen2DecoderStack(PackedModule):
         if w8 and self._w8 is None:
             raise ValueError("x2i_amd Qwen2DecoderStack.decode_step: w8=True needs the e4m3 weights; call pack_w8() first (and again after the "
                              "weights were loaded, moved or re-initialised)")
-        if (input_ids is None) == (inputs_embeds is None):
-            raise ValueError("Qwen2DecoderStack: pass exactly one of input_ids and inputs_embeds")
-        if not isinstance(cache, Qwen2DecodeCache) or cache.owner() is not self:
-            raise ValueError("x2i_amd Qwen2DecoderStack.decode_step: the cache must come from this stack's new_cache()")
+        self._one_input(inputs_embeds, input_ids)
+        self._own(cache, "decode_step")
         if cache.steps is None:
             raise ValueError("x2i_amd Qwen2DecoderStack.decode_step: prefill(cache, ...) comes first")
         if cache.steps + 1 > cache.cap:
@@ -576,11 +572,15 @@ class Qwen2DecodeCache:
         if k_lo is not None:
             self.k_lo.copy_(k_lo)
             self.k_hi.copy_(k_hi)
+        self._set_next_position(position_ids, attention_mask)
+        self.steps = S
+
+    def _set_next_position(self, position_ids, attention_mask=None):
+        """pos = 1 + the largest position id over all axes (of the valid tokens, with a mask).  On the device, no host read."""
         pos = position_ids if position_ids.dim() == 3 else position_ids[None]
         if attention_mask is not None:
             pos = pos.masked_fill((attention_mask == 0).to(pos.device)[None], -1)
         self.pos.copy_((pos.amax(-1).amax(0) + 1).expand_as(self.pos) if self.mrope else pos.amax(-1)[0] + 1)
-        self.steps = S
 
     def _adopt(self, other, P):
         """Slots [0, P) of another cache of the same stack and batch size (a conversation that outgrew it): K / V^T of every layer and k_lo
@@ -595,8 +595,7 @@ class Qwen2DecodeCache:
         """After a chunk of n rows at slots keep .. keep + n - 1 (Qwen2DecoderStack.extend): the keys end at keep + n, whatever lay behind is
         dropped, k_lo stays; next position = 1 + the largest position id of the chunk over all axes.  On the device, no host read."""
         self.k_hi.fill_(keep + n)
-        pos = position_ids if position_ids.dim() == 3 else position_ids[None]
-        self.pos.copy_((pos.amax(-1).amax(0) + 1).expand_as(self.pos) if self.mrope else pos.amax(-1)[0] + 1)
+        self._set_next_position(position_ids)
         self.steps = keep + n
 
     def _step_tables(self):

@@ -1,9 +1,9 @@
 """ctypes binding and torch-tensor wrapper of the extension header include/x2i_qwen_decode_w8.h: the decode-step linear with an e4m3 weight
 (csrc/qwen_decode_w8.hip).
 
-Like qwen_decode_ops.py: the entry point is not in _lib._EXPORTS (include/x2i.h's table is closed under ABI version 5); it gets its argtypes on
-the CDLL object of _lib.load() the first time this module is used.  PyTorch supplies device memory and the current stream, every computation
-happens in libx2i_hip.so, nothing here allocates behind the caller's back or synchronises, and there is no fallback.
+Like qwen_decode_ops.py: the entry point is not in _lib._EXPORTS (include/x2i.h's table is closed under ABI version 5); _lib.extension binds
+it.  PyTorch supplies device memory and the current stream, every computation happens in libx2i_hip.so, nothing here allocates behind the
+caller's back or synchronises, and there is no fallback.
 """
 import ctypes as C
 
@@ -14,21 +14,12 @@ from ._lib import X2IError, check
 
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
 
-# Every export of include/x2i_qwen_decode_w8.h: name -> argtypes (all return int).  tests/test_qwen_decode_w8_ref_cpu.py checks it against the header.
+# Every export of include/x2i_qwen_decode_w8.h: name -> argtypes (all return int).  tests/test_extension_boundary_cpu.py checks it against the header's prototypes.
 _EXPORTS = {
     "x2i_qwen_decode_linear_w8_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
 }
 
-_bound = None
-
-
-def load():
-    """The library of _lib.load() with the extension's prototypes set (once).  A missing symbol means a stale build."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        _bound = _lib.bind_extension(lib, _EXPORTS, "x2i_qwen_decode_w8.h")
-    return lib
+load = _lib.extension("x2i_qwen_decode_w8.h", _EXPORTS)
 
 
 def linear_w8(X, W8, w_scale, bias=None, res=None, out=None, gate=False, B=None, N=None, ldx=None, ldw=None, ldr=None, ldy=None, y_offset=0,

@@ -1,9 +1,8 @@
 """ctypes binding and torch-tensor wrappers of the extension header include/x2i_qwen.h: the Qwen2 decoder prefill's kernels (csrc/qwen.hip, csrc/encoder_attention.hip).
 
-The three entry points are not in _lib._EXPORTS (include/x2i.h's table is closed under ABI version 5); they get their argtypes on the
-CDLL object of _lib.load() the first time this module is used.  Like ops.py, t5_ops.py and clip_ops.py: PyTorch supplies device memory and
-the current stream, every computation happens in libx2i_hip.so, nothing here allocates behind the caller's back or synchronises, and there
-is no fallback.
+The three entry points are not in _lib._EXPORTS (include/x2i.h's table is closed under ABI version 5); _lib.extension binds them.  Like
+ops.py, t5_ops.py and clip_ops.py: PyTorch supplies device memory and the current stream, every computation happens in libx2i_hip.so,
+nothing here allocates behind the caller's back or synchronises, and there is no fallback.
 """
 import ctypes as C
 
@@ -14,7 +13,7 @@ from ._lib import X2IError, check
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
-# Every export of include/x2i_qwen.h: name -> argtypes (all return int).  tests/test_qwen_ref_cpu.py checks it against the header's prototypes.
+# Every export of include/x2i_qwen.h: name -> argtypes (all return int).  tests/test_extension_boundary_cpu.py checks it against the header's prototypes.
 _EXPORTS = {
     "x2i_qwen_attention_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i64, _vp],
     "x2i_qwen_rope_split_bf16": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
@@ -24,16 +23,7 @@ _EXPORTS = {
 pad64 = _lib.pad64
 
 
-_bound = None
-
-
-def load():
-    """The library of _lib.load() with the extension's prototypes set (once).  A missing symbol means a stale build."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        _bound = _lib.bind_extension(lib, _EXPORTS, "x2i_qwen.h")
-    return lib
+load = _lib.extension("x2i_qwen.h", _EXPORTS)
 
 
 def _range(t, B, name):
