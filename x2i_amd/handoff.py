@@ -700,6 +700,53 @@ class HipAudio(_Patch):
         return final
 
 
+class _HipFeatureExtractor:
+    """What HipLogMel puts in a processor's `feature_extractor`: every attribute is the original's (hop_length, model_input_names, ...),
+    and a call in the form the MiniCPM-o processor uses runs LogMel"""
+
+    def __init__(self, original, logmel, owner):
+        self.__dict__.update(_fe=original, _logmel=logmel, _owner=owner)
+
+    def __getattr__(self, name):
+        return getattr(self._fe, name)
+
+    def __call__(self, raw_speech, *args, **kw):
+        from transformers.feature_extraction_utils import BatchFeature
+        fe, lm = self._fe, self._logmel
+        served = (not args and set(kw) <= {"sampling_rate", "padding", "return_attention_mask", "return_tensors"}
+                  and kw.get("sampling_rate") == 16000 and kw.get("padding") == "max_length" and kw.get("return_attention_mask") is True
+                  and kw.get("return_tensors") == "pt" and fe.sampling_rate == 16000
+                  and isinstance(raw_speech, (list, tuple)) and len(raw_speech) > 0
+                  and all(getattr(w, "ndim", 0) == 1 and 1 <= len(w) <= lm.n_samples for w in raw_speech))
+        if not served:
+            return fe(raw_speech, *args, **kw)
+        self._owner.calls += 1
+        T = lm.T
+        features, lens = lm(list(raw_speech), out_dtype=torch.float32, T_out=T)
+        mask = (torch.arange(T)[None, :] < torch.tensor(lens)[:, None]).to(torch.int32)          # on the host: the processor slices by its sums
+        return BatchFeature({"input_features": features, "attention_mask": mask})
+
+
+class HipLogMel(_Patch):
+    """The log-mel front end in front of the audio tower on the HIP path (x2i_amd/logmel.py: LogMel, the tables of the processor's own
+    WhisperFeatureExtractor on `device`).  install() replaces `feature_extractor` ON THE PROCESSOR INSTANCE by an object that forwards every
+    attribute to the original and serves the call the MiniCPM-o processor makes (sampling_rate=16000, padding="max_length",
+    return_attention_mask=True, return_tensors="pt", 1-D waveforms of at most n_samples): `input_features` float32
+    [n, n_mels, n_samples / 160] ON THE DEVICE and `attention_mask` on the host with L_b ones per row, so the processor's slicing by
+    lengths reads nothing back.  Any other call goes to the original.  remove() restores it.  Also a context manager.  Independent of
+    HipAudio; with both, get_audio_embedding takes the device features as they are."""
+
+    def __init__(self, processor, device="cuda"):
+        from .logmel import LogMel
+        fe = getattr(processor, "feature_extractor", None)
+        if fe is None or not callable(fe):
+            raise RuntimeError("handoff: no feature extractor (processor.feature_extractor) found in %s" % type(processor).__name__)
+        self.processor = processor
+        self.logmel = LogMel.from_hf(fe, device)
+        self.calls = 0
+        _Patch.__init__(self, processor, "feature_extractor", _HipFeatureExtractor(fe, self.logmel, self))
+
+
 def find_extract_feature(model):
     """What extract_feature of an InternVL2.5 chat model runs: (`model.vision_model`, `model.mlp1`), of a model that has the method"""
     v, m = getattr(model, "vision_model", None), getattr(model, "mlp1", None)

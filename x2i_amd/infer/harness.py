@@ -87,6 +87,11 @@ def build_parser(family):
                    help="run MiniCPM-o's Whisper audio tower (model.apm with audio_projection_layer and audio_avg_pooler, what "
                         "get_audio_embedding computes) on the HIP path (x2i_amd/whisper.py) instead of the model's own; independent of "
                         "--hip_vision, --hip_resampler and --full_generate; MiniCPM-o only")
+    p.add_argument("--hip_mel", action="store_true",
+                   help="compute the audio tower's input on the HIP path: the log-mel front end (x2i_amd/logmel.py) in place of the "
+                        "processor's WhisperFeatureExtractor (handoff.HipLogMel), so that a waveform reaches the device as samples and the "
+                        "features never exist on the host; independent of --hip_audio, which takes the device features as they are; "
+                        "MiniCPM-o only")
     p.add_argument("--hip_generate", action="store_true",
                    help="run the MLLM's greedy 128-token generate() with the decoder stack on the HIP path over the prompt and over the "
                         "generated tokens (key/value cache, x2i_amd/qwen.py decode_step); serves --use_answer; Qwen2.5-VL only")

@@ -26,7 +26,7 @@ class MiniCPMConditioner:
     dependence on the reference's patched generate() returning `.hidden_states`.  full_generate: the reference's form."""
 
     def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None, processor=None, hip_vision=False, hip_resampler=False,
-                 hip_audio=False, hip_decoder=False, use_answer=False):
+                 hip_audio=False, hip_decoder=False, use_answer=False, hip_mel=False):
         if hip_decoder and not (prefill_only and not use_answer):     # (refused before a checkpoint is read)
             raise ValueError("--hip_decoder serves the prompt pass only: not with --full_generate or --use_answer")
         if model is None:
@@ -63,6 +63,12 @@ class MiniCPMConditioner:
         if hip_audio:
             from ..handoff import HipAudio
             self.audio = HipAudio(self.model).install()
+        # hip_mel: the log-mel features of an audio prompt on the HIP path (x2i_amd/logmel.py) in place of the processor's feature extractor:
+        # the processor hands on device tensors, and with hip_audio the tower reads them where they are
+        self.mel = None
+        if hip_mel:
+            from ..handoff import HipLogMel
+            self.mel = HipLogMel(self.processor, device).install()
 
     def hidden_states(self, inputs):
         """processor outputs -> [B, C, S, H]"""
@@ -120,6 +126,7 @@ def main(argv=None):
                                                                                               hip_vision=args.hip_vision,
                                                                                               hip_resampler=args.hip_resampler,
                                                                                               hip_audio=args.hip_audio,
+                                                                                              hip_mel=args.hip_mel,
                                                                                               hip_decoder=args.hip_decoder,
                                                                                               use_answer=args.use_answer)
     Harness(args, "minicpm", cond, device).run_tasks(tasks(args))
