@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import flux as OF
+from tests.cnx_bwd_ref import _wgrad_bound_terms
 from tests.util import seeded
 
 pytestmark = pytest.mark.gpu
@@ -28,15 +29,6 @@ def _nhwc(x):
 
 
 # -------------------------------------------------------------------------------------------------------------- conv weight gradient
-def _wgrad_bound_terms(B, OH, OW, Cin, Cout, k):
-    """Accumulation length of x2i_conv_wgrad_bf16 per output element: the 32-product MFMA steps of one split, then the splits' partials."""
-    from x2i_amd import ops
-    n = ops.conv_wgrad_workspace_floats(B, OH, OW, Cin, Cout, k, k)
-    nsplit = n // (Cout * Cin * k * k + Cout)
-    steps = math.ceil(math.ceil(B * OH * OW / 32) / nsplit)
-    return steps, nsplit
-
-
 # (Cin, Cout, k, stride, pad, B, H, W): the table's layers on reduced grids, B = 1 / 2 / 3 and a non-square grid
 WGRAD_CASES = [(64, 64, 3, 1, 1, 2, 48, 48), (64, 128, 3, 1, 1, 1, 40, 56), (128, 128, 3, 1, 1, 3, 32, 32), (128, 128, 3, 2, 1, 2, 64, 48),
                (128, 256, 3, 1, 1, 2, 24, 40), (256, 256, 3, 1, 1, 2, 32, 32), (128, 256, 1, 1, 0, 2, 32, 24), (256, 256, 3, 2, 1, 1, 48, 64),
