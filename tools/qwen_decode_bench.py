@@ -22,6 +22,13 @@ line beside each `decode_linear` line -- the two rings captured in a graph each 
 (halved) weight bytes, the ratio to the bf16 kernel and min .. max over the reps of both -- and in the generate table a `hip w8` side
 (HipGenerate(w8=True), graph-replayed, torch head) next to `hip graph`, with `hip head + w8` under --vocab real
 (profiles/qwen_decode_w8_bench.log).
+With --vocab real --sample the sampled step joins (include/ext/sample/x2i_sample.h): HipGenerate(hip_head=True, sample=True) under a sampling
+generation_config (temperature 0.7, top-k 50, top-p 0.8, penalty 1.05) against the greedy hip_head step under the same penalty, both
+graph-replayed and alternating in the same run; then the select launch alone, x2i_sample_select_f32 beside x2i_qwen_head_select on the
+same scores and workspace, a graph of 16 launches each, replayed alternately, for four settings of (top_k, top_p), and the step's tail --
+the head launch with the scores written plus the sampled select against the greedy pair -- over a ring of distinct head weights.
+--sample_step_batches limits the batch sizes whose whole generate loops run.  --only sample runs nothing else
+(profiles/qwen_sample_bench.log).
 Output: stdout and, with --log, a file (profiles/qwen_decode_bench.log, profiles/qwen_head_bench.log)."""
 import argparse
 import os
@@ -36,6 +43,7 @@ from x2i_amd import ops  # noqa: E402
 from x2i_amd import qwen_decode_ops as qd  # noqa: E402
 from x2i_amd import qwen_decode_w8_ops as qd8  # noqa: E402
 from x2i_amd import qwen_head_ops as qh  # noqa: E402
+from x2i_amd import sample_binding as sb  # noqa: E402
 from x2i_amd.handoff import HipGenerate  # noqa: E402
 
 CONFIGS = {
@@ -269,6 +277,85 @@ def bench_head(say, name, c, batches, reps):
     torch.cuda.empty_cache()
 
 
+def bench_sample(say, name, c, batches, step_batches, S, T, reps):
+    """the sampled hip_head step against the greedy one, alternating (step_batches); then, per batch size, the two select launches alone on the
+    same scores, and the head launch with each of them over a ring of distinct head weights"""
+    from transformers import GenerationConfig
+    from transformers.generation.logits_process import (RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper,
+                                                        TopPLogitsWarper)
+    model = library_model(c)
+    V, K = c["vocab_size"], c["hidden_size"]
+    gc = GenerationConfig(do_sample=True, temperature=0.7, top_k=50, top_p=0.8, repetition_penalty=1.05, eos_token_id=None, pad_token_id=0)
+    greedy = [RepetitionPenaltyLogitsProcessor(1.05)]
+    sampled = greedy + [TemperatureLogitsWarper(0.7), TopKLogitsWarper(50), TopPLogitsWarper(0.8)]
+    hg = HipGenerate(model, check_mask=False, hip_head=True)
+    for B in step_batches:
+        ids = torch.randint(0, V, (B, S), generator=torch.Generator().manual_seed(B)).cuda()
+        mask = torch.ones_like(ids)
+        sides = {
+            "hip head": lambda n: hg.generate(model, max_new_tokens=n, graph=True, logits_processor=greedy, input_ids=ids, attention_mask=mask),
+            "hip sample": lambda n: hg.generate(model, max_new_tokens=n, graph=True, logits_processor=sampled, generation_config=gc, sample=True, seed=0,
+                                                input_ids=ids, attention_mask=mask),
+        }
+        for fn in sides.values():
+            fn(T)
+            fn(1)
+        per = {k: [] for k in sides}
+        for _ in range(reps):
+            for k, fn in sides.items():
+                tT, _ = wall(lambda: fn(T))
+                t1, _ = wall(lambda: fn(1))
+                per[k].append((tT - t1) / (T - 1))
+        for k in sides:
+            say("%-3s B=%d prompt %d, %d tokens, %-10s: %.3f ms per token (min %.3f .. max %.3f, %d reps)"
+                % (name, B, S, T, k, statistics.median(per[k]), min(per[k]), max(per[k]), reps))
+        h, m = statistics.median(per["hip head"]), statistics.median(per["hip sample"])
+        say("%-3s B=%d                              : hip sample %.3f ms against hip head (greedy) %.3f ms per token: %+.3f ms, %.3f x"
+            % (name, B, m, h, m - h, m / h))
+    del hg, model
+    torch.cuda.empty_cache()
+    nbytes = V * K * 2
+    ring = max(4, -(-(1 << 30) // nbytes))
+    W = torch.randn((ring, V, K), device="cuda", dtype=torch.bfloat16) * K ** -0.5
+    for B in batches:
+        # the select launches alone, on the scores of one head launch
+        x = torch.randn((B, K), device="cuda").bfloat16()
+        ws = torch.empty((qh.workspace_floats(B, V),), device="cuda", dtype=torch.float32)
+        logits = torch.empty((B, V), device="cuda", dtype=torch.float32)
+        step, token = torch.zeros((1,), device="cuda", dtype=torch.int32), torch.zeros((B,), device="cuda", dtype=torch.long)
+        seq, lengths = torch.zeros((B, 64), device="cuda", dtype=torch.long), torch.zeros((B,), device="cuda", dtype=torch.long)
+        done = torch.zeros((B,), device="cuda", dtype=torch.uint8)
+        rng = sb.rng_state(0, 0, "cuda")
+        seen = (torch.rand((B, V), device="cuda") < 0.004).to(torch.uint8)       # about 600 ids: a 512-token prompt and its answer
+        qh.logits_argmax(x, W[0], ws, step=step, logits=logits)
+        n = 16
+        for top_k, top_p in ((50, 0.8), (50, 1.0), (0, 0.8), (0, 1.0)):
+            ms_s, ms_g = graph_ms_interleaved(
+                [lambda: [sb.select(logits, ws, step, token, seq, lengths, done, 0, temperature=0.7, top_k=top_k, top_p=top_p, rng=rng) for _ in range(n)],
+                 lambda: [qh.select(ws, step, token, seq, lengths, done, 0, V) for _ in range(n)]], 10)
+            us_s, us_g = [t / n * 1e3 for t in ms_s], [t / n * 1e3 for t in ms_g]
+            say("%-3s select        V=%-6d B=%d top_k=%-2d top_p=%.1f: x2i_sample_select_f32 %.1f us (min %.1f .. max %.1f); x2i_qwen_head_select %.1f us "
+                "(min %.1f .. max %.1f)" % (name, V, B, top_k, top_p, statistics.median(us_s), min(us_s), max(us_s), statistics.median(us_g), min(us_g),
+                                           max(us_g)))
+
+        # the tail of a step: the head launch (penalty 1.05) with the scores written and the sampled select, against the greedy pair
+        def pairs(sample):
+            step.zero_()
+            for i in range(ring):
+                qh.logits_argmax(x, W[i], ws, seen=seen, penalty=1.05, step=step, logits=logits if sample else None)
+                if sample:
+                    sb.select(logits, ws, step, token, seq, lengths, done, 0, temperature=0.7, top_k=50, top_p=0.8, rng=rng, seen=seen)
+                else:
+                    qh.select(ws, step, token, seq, lengths, done, 0, V, seen=seen)
+        ms_s, ms_g = graph_ms_interleaved([lambda: pairs(True), lambda: pairs(False)], 10)
+        us_s, us_g = [t / ring * 1e3 for t in ms_s], [t / ring * 1e3 for t in ms_g]
+        say("%-3s head + select V=%-6d B=%d top_k=50 top_p=0.8: scores written + sampled select %.1f us (min %.1f .. max %.1f); greedy pair %.1f us "
+            "(min %.1f .. max %.1f): %+.1f us per token" % (name, V, B, statistics.median(us_s), min(us_s), max(us_s), statistics.median(us_g), min(us_g),
+                                                            max(us_g), statistics.median(us_s) - statistics.median(us_g)))
+    del W
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="7b,3b")
@@ -276,12 +363,19 @@ def main():
     ap.add_argument("--prompt", type=int, default=512)
     ap.add_argument("--tokens", type=int, default=128)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--only", choices=("all", "generate", "linears", "head"), default="all")
+    ap.add_argument("--only", choices=("all", "generate", "linears", "head", "sample"), default="all")
     ap.add_argument("--vocab", choices=("small", "real"), default="small",
                     help="real: the models' own vocabularies, and the hip_head side in the generate table")
     ap.add_argument("--w8", action="store_true", help="add the e4m3 weight-only sides: decode_linear_w8 per shape, hip w8 (and hip head + w8) per generate")
+    ap.add_argument("--sample", action="store_true", help="with --vocab real: add the sampled hip_head step against the greedy one, and the select "
+                                                          "launches alone")
+    ap.add_argument("--sample_step_batches", default=None,
+                    help="with --sample: the batch sizes whose whole generate loops are timed (default: --batches; the launches alone are timed at "
+                         "every size of --batches)")
     ap.add_argument("--log", default=None)
     a = ap.parse_args()
+    if (a.sample or a.only == "sample") and a.vocab != "real":
+        raise SystemExit("qwen_decode_bench: --sample times the step over the models' own vocabularies: it needs --vocab real")
     if not torch.cuda.is_available():
         raise SystemExit("qwen_decode_bench: no GPU visible; there is nothing to time on the CPU")
     lines = []
@@ -304,6 +398,9 @@ def main():
         if a.only == "head" or (a.only == "all" and real):
             with torch.no_grad():
                 bench_head(say, name, dict(CONFIGS[name], vocab_size=REAL_VOCAB[name]), batches, 10)
+        if a.sample or a.only == "sample":
+            bench_sample(say, name, c, batches, [int(b) for b in a.sample_step_batches.split(",") if b] if a.sample_step_batches is not None
+                         else batches, a.prompt, a.tokens, a.reps)
     if a.log:
         os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
         with open(a.log, "w") as fh:

@@ -8,6 +8,7 @@
 #include "encoder_common.h"
 #include "x2i_kernels.h"
 #include "decode_linear_core.h"
+#include "qwen_head_book.h"
 #include "../../include/x2i_qwen_head.h"
 
 #include <cmath>
@@ -15,8 +16,8 @@
 namespace {
 
 constexpr int ROWS = X2I_QWEN_HEAD_ROWS;
-constexpr int HDR = 4;        // f32 words in front of the partials: word 0 is the snapshot of the step counter
-constexpr int NO_STEP = -0x7fffffff - 1;   // the snapshot of a logits call without a counter
+using head_book::HDR;
+using head_book::NO_STEP;
 static_assert(ROWS == 16, "four waves of four rows");
 
 // Workgroup g owns the rows [16 g, 16 g + 16), wave w four of them.  Lane 0 of a wave holds the wave's R * NB sums and does its epilogue; the
@@ -95,19 +96,7 @@ __global__ __launch_bounds__(256) void head_select_kernel(const float* __restric
     __syncthreads();
   }
   if (tid != 0) return;
-  int amax = si[0];
-  amax = amax < 0 ? 0 : (amax >= V ? V - 1 : amax);             // whatever the workspace held: the next step's gather stays inside the table
-  const int col = __float_as_int(ws[0]);
-  const bool was_done = done[b] != 0;
-  const long long tok = was_done ? pad : (long long)amax;
-  token[b] = tok;
-  if (col >= 0 && col < ncols) sequences[(long long)b * ld_seq + col] = tok;
-  if (!was_done) lengths[b] += 1;
-  bool hit = false;
-  for (int e = 0; e < n_eos; ++e) hit |= eos[e] == tok;
-  done[b] = (was_done || hit) ? 1 : 0;
-  if (seen) seen[(long long)b * ld_seen + tok] = 1;
-  if (b == 0 && col != NO_STEP && col != 0x7fffffff) *step = col + 1;
+  head_book::generated_token(b, si[0], __float_as_int(ws[0]), V, step, token, sequences, ld_seq, ncols, lengths, done, eos, n_eos, pad, seen, ld_seen);
 }
 
 template <int NB>

@@ -199,6 +199,58 @@ def head_plan(processors):
     return 1.0 if penalty is None else penalty
 
 
+def sample_plan(generation_config, processors):
+    """What HipGenerate(hip_head=True, sample=True) makes of a generation_config and a list of `transformers` logits processors: -> (penalty,
+    temperature, top_k, top_p), what the head launch and x2i_sample_select_f32 (include/ext/sample/x2i_sample.h) apply; 1.0, 1.0, 0 and 1.0
+    where the list has no such processor.  Needs no GPU.  Accepted: what head_plan accepts, at most one of each and in the library's order
+    only (RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper: the order the kernels apply them
+    in), TopPLogitsWarper with min_tokens_to_keep = 1, both filters with the value -inf.  A generation_config that does not sample
+    (do_sample false) gives top_k = 1, the argmax.  Refused with a ValueError naming the class, before anything runs: any other processor
+    (MinPLogitsWarper, TypicalLogitsWarper, EpsilonLogitsWarper, EtaLogitsWarper, ...), a subclass included; num_beams > 1."""
+    from transformers.generation.logits_process import (RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper,
+                                                        TopPLogitsWarper)
+    beams = getattr(generation_config, "num_beams", 1) or 1
+    if beams > 1:
+        raise ValueError("handoff.HipGenerate: sample draws one token per sample, and this generation_config asks for num_beams=%r; run with "
+                         "--full_generate instead" % (beams,))
+    order = (RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper)
+    penalty, temperature, top_k, top_p, rank = 1.0, 1.0, 0, 1.0, -1
+    for p in processors or []:
+        name = type(p).__name__
+        if type(p) not in order:
+            raise ValueError("handoff.HipGenerate: sample cannot fuse the logits processor %s (it fuses %s); run with --full_generate instead"
+                             % (name, ", ".join(c.__name__ for c in order)))
+        if order.index(type(p)) <= rank:
+            raise ValueError("handoff.HipGenerate: sample fuses at most one of each processor, in the library's order (%s), and %s comes after "
+                             "%s; run with --full_generate instead" % (", ".join(c.__name__ for c in order), name, order[rank].__name__))
+        rank = order.index(type(p))
+        if getattr(p, "filter_value", -float("inf")) != -float("inf"):
+            raise ValueError("handoff.HipGenerate: sample removes a filtered token, and %s has filter_value=%r; run with --full_generate instead"
+                             % (name, p.filter_value))
+        if type(p) is RepetitionPenaltyLogitsProcessor:
+            if p.prompt_ignore_length:
+                raise ValueError("handoff.HipGenerate: hip_head cannot fuse %s with prompt_ignore_length=%r (the kernel penalises every id of "
+                                 "the sequence); run with --full_generate instead" % (name, p.prompt_ignore_length))
+            penalty = float(p.penalty)
+        elif type(p) is TemperatureLogitsWarper:
+            temperature = float(p.temperature)
+            if not (temperature > 0 and temperature < float("inf")):
+                raise ValueError("handoff.HipGenerate: sample needs a positive finite temperature, and %s has %r" % (name, p.temperature))
+        else:
+            if getattr(p, "min_tokens_to_keep", 1) != 1:
+                raise ValueError("handoff.HipGenerate: sample keeps at least one token, and %s has min_tokens_to_keep=%r; run with "
+                                 "--full_generate instead" % (name, p.min_tokens_to_keep))
+            if type(p) is TopKLogitsWarper:
+                top_k = int(p.top_k)
+            else:
+                top_p = float(p.top_p)
+                if not 0 < top_p <= 1:
+                    raise ValueError("handoff.HipGenerate: sample needs 0 < top_p <= 1, and %s has %r" % (name, p.top_p))
+    if generation_config is not None and not getattr(generation_config, "do_sample", False):
+        top_k = 1
+    return penalty, temperature, top_k, top_p
+
+
 def _common_prefix(prev_ids, prev_valid, ids):
     """common_prefix as a 0-dim int64 tensor on the ids' device: no host read"""
     m = min(int(prev_valid), prev_ids.shape[1], ids.shape[1])
@@ -241,6 +293,13 @@ class HipGenerate:
     kernels on each sample's last valid prompt row.  head_plan decides which processor lists fuse; any other raises.  A token is then the
     argmax of f32-accumulated logits that were never rounded to bf16: where the top two logits lie within one bf16 ulp the torch head ties
     them and takes the lower index, so the two paths can pick different tokens there.
+    With sample=True (off by default; per call generate(sample=..., seed=...); needs hip_head) a generation_config that samples is no longer
+    refused: the head launch also writes its f32 scores and x2i_sample_select_f32 (x2i_amd/sample_binding.py, include/ext/sample/x2i_sample.h)
+    stands in the place of the argmax -- temperature, top-k, top-p and one inverse-CDF draw, for token 0 and inside the captured step.
+    sample_plan decides which generation_config and processor lists fuse; any other raises.  The draws come from Philox4x32-10 under {seed,
+    offset}, kept in device memory with the loop's other state; the counter of a token is the offset plus its column, the offset advances by
+    the tokens a call generated, and a call with an explicit seed restarts at offset 0, so the same seed and inputs give the same sequences,
+    eager or replayed.  Tokens of equal score are kept or dropped by top-p together (the library splits such a run by sort position).
     With w8=True (off by default; per call generate(w8=...)) the four linears of every layer of a decode step read e4m3 weights with one
     f32 scale per output row (Qwen2DecoderStack.pack_w8, made once at first use and kept beside the bf16 weights, which the prompt pass
     still runs on): half the weight bytes per token.  The lm_head stays bf16 under either head.  The captured steps hold their weights by
@@ -261,7 +320,7 @@ class HipGenerate:
     same for every image -- so the features under a matching prefix must be unchanged from the previous call (a chat history whose
     images never change, as inference_multi_turn's)."""
 
-    def __init__(self, model, check_mask=True, hip_head=False, w8=False, keep_cache=False):
+    def __init__(self, model, check_mask=True, hip_head=False, w8=False, keep_cache=False, sample=False, seed=0):
         from .qwen import Qwen2DecoderStack
         self.decoder = find_decoder(model)
         self.stack = Qwen2DecoderStack.from_hf(self.decoder)
@@ -271,6 +330,8 @@ class HipGenerate:
         self.hip_head = hip_head
         self.w8 = w8
         self.keep_cache = keep_cache
+        self.sample = sample
+        self._rng = [int(seed), 0]      # under sample: the seed, and the offset of the next call (the tokens generated so far)
         self.reused, self.reuse_note = 0, ""
         self.slab = self._cache = None
         self._state = {}
@@ -369,14 +430,22 @@ class HipGenerate:
 
     @torch.no_grad()
     def generate(self, model, max_new_tokens=128, eos_token_id=None, pad_token_id=None, logits_processor=None, graph=True, check_every=16,
-                 generation_config=None, hip_head=None, w8=None, keep_cache=None, **inputs):
+                 generation_config=None, hip_head=None, w8=None, keep_cache=None, sample=None, seed=None, **inputs):
         """-> GenerateResult.  inputs: the model's forward arguments of the prompt (input_ids required; attention_mask, pixel_values, ...).
         eos_token_id: an id, a list of ids or None (never stop early); pad_token_id: what follows a sample's end token (default: the first
         end token, else 0).  logits_processor: a list of callables (input_ids [B, len], scores f32 [B, V]) -> scores.  hip_head: None takes
         the constructor's; True needs a list that head_plan accepts.  w8: None takes the constructor's; True runs the decode steps on the
         stack's e4m3 weights (packed at first use).  keep_cache: None takes the constructor's; True stands on what the previous call left
-        where the prompt allows it and keeps this call's for the next (the class docstring has the rules and the caller's promise)."""
-        self.refuse_sampling(generation_config if generation_config is not None else getattr(model, "generation_config", None))
+        where the prompt allows it and keeps this call's for the next (the class docstring has the rules and the caller's promise).
+        sample: None takes the constructor's; True needs hip_head and a generation_config and list that sample_plan accepts.  seed: None goes
+        on in the instance's stream of draws; a value restarts it at offset 0 under that seed."""
+        generation_config = generation_config if generation_config is not None else getattr(model, "generation_config", None)
+        sample = bool(self.sample if sample is None else sample)
+        if not sample:
+            self.refuse_sampling(generation_config)
+        elif not (self.hip_head if hip_head is None else hip_head):
+            raise ValueError("handoff.HipGenerate: sample draws the tokens of the hip_head step: not without hip_head (--hip_sample needs "
+                             "--hip_generate --hip_head)")
         if max_new_tokens < 1:
             raise ValueError("handoff.HipGenerate: max_new_tokens must be at least 1")
         ids = inputs.get("input_ids")
@@ -394,7 +463,13 @@ class HipGenerate:
         head = model.get_output_embeddings()
         if hip_head:       # every refusal comes before anything runs
             import inspect
-            penalty = head_plan(processors)
+            samp = None
+            if sample:
+                penalty, *samp = sample_plan(generation_config, processors)
+                if seed is not None:
+                    self._rng = [int(seed), 0]
+            else:
+                penalty = head_plan(processors)
             if len(eos) > 8:
                 raise ValueError("handoff.HipGenerate: hip_head takes at most 8 end tokens (got %d)" % len(eos))
             if getattr(head, "bias", None) is not None or head.weight.dtype != torch.bfloat16 or not head.weight.is_contiguous():
@@ -418,7 +493,7 @@ class HipGenerate:
         rows = torch.arange(B, device=dev)
         last = (cache.k_hi - 1).long()                                   # the last valid token of each sample, under either padding
         if hip_head:
-            res = self._generate_hip_head(prompt, cache, ids, head.weight, penalty, eos, pad, T, rows, last, graph, check_every, w8)
+            res = self._generate_hip_head(prompt, cache, ids, head.weight, penalty, eos, pad, T, rows, last, graph, check_every, w8, samp)
             return self._remember(res) if self._keep else res
         sequences = torch.full((B, S + T), pad, device=dev, dtype=torch.long)
         sequences[:, :S] = ids
@@ -488,15 +563,18 @@ class HipGenerate:
         res = GenerateResult(prompt, answer[:, :, :n - 1], sequences[:, :S + n], lengths)
         return self._remember(res) if self._keep else res
 
-    def _generate_hip_head(self, prompt, cache, ids, W, penalty, eos, pad, T, rows, last, graph, check_every, w8=False):
+    def _generate_hip_head(self, prompt, cache, ids, W, penalty, eos, pad, T, rows, last, graph, check_every, w8=False, samp=None):
         """generate()'s loop with the head kernels: every word of the loop's state lives in buffers that stay with the cache, so that the
-        captured step (gather, decode_step, the copy into the answer at the device counter's column, both head kernels) replays."""
+        captured step (gather, decode_step, the copy into the answer at the device counter's column, both head kernels) replays.
+        samp: None, or [temperature, top_k, top_p]: the head launch also writes its f32 scores and x2i_sample_select_f32 stands in the place
+        of the greedy select; the draw's counter is the random-number offset plus the step counter, both in device memory."""
         from . import qwen_head_ops as HO
+        from . import sample_binding as SB
         dev = prompt.device
         B, C, S, H = prompt.shape
         V = W.shape[0]
         st = self._state
-        hkey = (W.data_ptr(), V, penalty, pad, tuple(eos))         # what a captured step holds by value
+        hkey = (W.data_ptr(), V, penalty, pad, tuple(eos), None if samp is None else tuple(samp))         # what a captured step holds by value
         if st.get("hkey") != hkey or st["h_answer"].shape[2] < T - 1:
             st.pop("hgraph", None)
             st["hkey"] = hkey
@@ -511,6 +589,8 @@ class HipGenerate:
             st["h_done"] = torch.zeros((B,), device=dev, dtype=torch.uint8)
             st["h_len"] = torch.zeros((B,), device=dev, dtype=torch.long)
             st["h_eos"] = torch.tensor(eos, device=dev, dtype=torch.long) if eos else None
+            st["h_logits"] = torch.empty((B, V), device=dev, dtype=torch.float32) if samp is not None else None
+            st["h_rng"] = torch.zeros((2,), device=dev, dtype=torch.long)
         hgraphs = st.setdefault("hgraph", {})   # w8 -> graph: a captured step holds its weights by pointer
         if hgraphs and st.get("h_w8_pack") is not self.stack._w8:    # ... and a new pack is new pointers
             hgraphs.pop(True, None)
@@ -524,10 +604,17 @@ class HipGenerate:
         base.fill_(S + 1)                                          # the pass of token t - 1 runs with the counter at S + t: answer column t - 1
         done.zero_()
         lengths.zero_()
+        logits, rng = st["h_logits"], st["h_rng"]
+        if samp is not None:
+            rng.copy_(SB.rng_state(self._rng[0], self._rng[1], dev))
 
         def pick(x):
-            HO.logits_argmax(x, W, ws, seen=seen, penalty=penalty, step=step)
-            HO.select(ws, step, token, seq, lengths, done, pad, V, eos=eos_t, seen=seen)
+            HO.logits_argmax(x, W, ws, seen=seen, penalty=penalty, step=step, logits=logits)
+            if samp is None:
+                HO.select(ws, step, token, seq, lengths, done, pad, V, eos=eos_t, seen=seen)
+            else:
+                SB.select(logits, ws, step, token, seq, lengths, done, pad, temperature=samp[0], top_k=samp[1], top_p=samp[2], rng=rng,
+                          eos=eos_t, seen=seen)
 
         def one_step():
             self.stack.decode_step(cache, input_ids=token, out=step_out, w8=w8)
@@ -560,6 +647,8 @@ class HipGenerate:
             t += 1
         n = int(lengths.max()) if eos_t is not None else T                # (tokens after every sample's end are dropped: one host read)
         n = max(n, 1)
+        if samp is not None:
+            self._rng[1] += n                                         # the next call goes on in the stream
         return GenerateResult(prompt, abuf[:, :, :n - 1].clone(), seq[:, :S + n].clone(), lengths.clone())
 
 

@@ -98,7 +98,8 @@ def build_parser(family):
     p.add_argument("--hip_head", action="store_true",
                    help="with --hip_generate: choose every token on the HIP path too (x2i_amd/qwen_head_ops.py) -- the lm_head, the repetition "
                         "penalty and the argmax inside the captured step, no [B, V] logits written; the temperature, top-k and top-p warpers of "
-                        "the generation_config cannot move an argmax and are dropped, any other logits processor is refused by name.  A token is "
+                        "the generation_config cannot move an argmax and are dropped (--hip_sample applies them and draws), any other logits "
+                        "processor is refused by name.  A token is "
                         "the argmax of f32 logits that are not rounded to bf16, so where the top two logits lie within one bf16 ulp it can "
                         "differ from the torch head's; Qwen2.5-VL only")
     p.add_argument("--hip_w8", action="store_true",
@@ -106,6 +107,14 @@ def build_parser(family):
                         "output row (Qwen2DecoderStack.pack_w8, x2i_amd/qwen_decode_w8_ops.py): half the weight bytes per generated token; "
                         "bf16 activations, f32 sums.  The prompt pass and the lm_head stay bf16, and the bf16 weights are kept (about 6.5 GB "
                         "more for the 7B decoder).  The generated tokens can differ from the bf16 steps'; Qwen2.5-VL only")
+    p.add_argument("--hip_sample", action="store_true",
+                   help="with --hip_generate --hip_head: draw every token inside the captured step too (x2i_amd/sample_binding.py, "
+                        "include/ext/sample/x2i_sample.h) -- the temperature, top-k and top-p of a generation_config with do_sample=True and "
+                        "one inverse-CDF draw from a Philox stream kept in device memory, in place of the argmax; such a generation_config is "
+                        "then no longer refused.  Tokens of equal score are kept or dropped by top-p together; any other logits processor is "
+                        "refused by name; Qwen2.5-VL only")
+    p.add_argument("--hip_sample_seed", type=int, default=None,
+                   help="with --hip_sample: the seed of the draws (default: --seed where it is given, otherwise 0)")
     p.add_argument("--decode", action="store_true", help="with --synthetic: also run the (random-weight) VAE decoder and save images")
     return p
 
@@ -125,6 +134,13 @@ def stack_hidden_states(hidden_states, use_answer=False):
 def strip_module_prefix(state_dict):
     """Checkpoints are saved from DDP-wrapped modules (train/train_qwenvl.py:641-647): drop 'module.'."""
     return {k.replace("module.", ""): v for k, v in state_dict.items()}
+
+
+def sample_seed(args):
+    """--hip_sample_seed, or the script's --seed, or 0"""
+    if getattr(args, "hip_sample_seed", None) is not None:
+        return args.hip_sample_seed
+    return args.seed if getattr(args, "seed", None) is not None else 0
 
 
 def load_projector(kind, path=None, device="cuda", seed=0):

@@ -9,15 +9,18 @@ import time
 
 import torch
 
-from .harness import Harness, SyntheticConditioner, build_parser, stack_hidden_states
+from .harness import Harness, SyntheticConditioner, build_parser, sample_seed, stack_hidden_states
 
 
 class MultiTurnConditioner:
     """model / processor: hand in loaded ones (a test's tiny model and stub processor) and `path` is not read."""
 
-    def __init__(self, path, device, hip_generate=False, hip_head=False, model=None, processor=None, hip_w8=False, keep_cache=False):
+    def __init__(self, path, device, hip_generate=False, hip_head=False, model=None, processor=None, hip_w8=False, keep_cache=False,
+                 hip_sample=False, hip_sample_seed=0):
         if hip_w8 and not hip_generate:         # (before the checkpoint is read)
             raise ValueError("--hip_w8 runs the decode steps of --hip_generate's loop on e4m3 weights: not without --hip_generate")
+        if hip_sample and not (hip_generate and hip_head):
+            raise ValueError("--hip_sample draws the tokens inside --hip_generate --hip_head's captured step: not without both")
         if keep_cache and not hip_generate:
             raise ValueError("--hip_keep_cache keeps the key/value cache of --hip_generate's loop between turns: not without --hip_generate")
         if model is None or processor is None:
@@ -32,8 +35,9 @@ class MultiTurnConditioner:
             raise ValueError("--hip_head chooses the tokens of --hip_generate's loop: not without --hip_generate")
         if hip_generate:
             from ..handoff import HipGenerate
-            HipGenerate.refuse_sampling(self.model.generation_config)
-            self.generate = HipGenerate(self.model, hip_head=hip_head, w8=hip_w8, keep_cache=keep_cache)
+            if not hip_sample:
+                HipGenerate.refuse_sampling(self.model.generation_config)
+            self.generate = HipGenerate(self.model, hip_head=hip_head, w8=hip_w8, keep_cache=keep_cache, sample=hip_sample, seed=hip_sample_seed)
 
     @torch.no_grad()
     def __call__(self, images=None, text_prompt=None, **_):
@@ -101,7 +105,7 @@ def main(argv=None):
     if args.synthetic:
         return synthetic_turns(args, kind, device)
     cond = MultiTurnConditioner(args.qwen_path, device, hip_generate=args.hip_generate, hip_head=args.hip_head, hip_w8=args.hip_w8,
-                                keep_cache=args.hip_keep_cache)
+                                keep_cache=args.hip_keep_cache, hip_sample=args.hip_sample, hip_sample_seed=sample_seed(args))
     h = Harness(args, kind, lambda **kw: cond(**kw)[0], device)
     turn = 0
     while True:

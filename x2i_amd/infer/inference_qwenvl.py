@@ -7,7 +7,7 @@
 """
 import torch
 
-from .harness import Harness, SyntheticConditioner, asset, build_parser, stack_hidden_states
+from .harness import Harness, SyntheticConditioner, asset, build_parser, sample_seed, stack_hidden_states
 
 
 class QwenVLConditioner:
@@ -15,9 +15,11 @@ class QwenVLConditioner:
     1 fps / 128*128 pixels, generate(max_new_tokens=128, output_hidden_states=True) -- infer/inference_qwenvl.py:136-180."""
 
     def __init__(self, path, device, use_answer=False, prefill_only=True, hip_decoder=False, hip_vision=False, hip_generate=False, hip_head=False,
-                 hip_w8=False):
+                 hip_w8=False, hip_sample=False, hip_sample_seed=0):
         if hip_w8 and not hip_generate:         # (before the checkpoint is read)
             raise ValueError("--hip_w8 runs the decode steps of --hip_generate's loop on e4m3 weights: not without --hip_generate")
+        if hip_sample and not (hip_generate and hip_head):
+            raise ValueError("--hip_sample draws the tokens inside --hip_generate --hip_head's captured step: not without both")
         from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
         self.model = Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
         self.processor = AutoProcessor.from_pretrained(path)
@@ -36,8 +38,9 @@ class QwenVLConditioner:
             if hip_decoder:
                 raise ValueError("--hip_generate runs the prompt pass on the HIP path itself: not together with --hip_decoder")
             from ..handoff import HipGenerate
-            HipGenerate.refuse_sampling(self.model.generation_config)
-            self.generate = HipGenerate(self.model, hip_head=hip_head, w8=hip_w8)
+            if not hip_sample:
+                HipGenerate.refuse_sampling(self.model.generation_config)
+            self.generate = HipGenerate(self.model, hip_head=hip_head, w8=hip_w8, sample=hip_sample, seed=hip_sample_seed)
         elif prefill_only and not use_answer:
             from ..handoff import HiddenStateSlab, HipPrefill, find_decoder
             # hip_decoder: the same one forward with the decoder stack itself on the HIP path (x2i_amd/qwen.py)
@@ -112,7 +115,8 @@ def main(argv=None):
     cond = SyntheticConditioner(kind, device) if args.synthetic else QwenVLConditioner(args.qwen_path, device, args.use_answer, prefill_only=not args.full_generate,
                                                                                             hip_decoder=args.hip_decoder, hip_vision=args.hip_vision,
                                                                                             hip_generate=args.hip_generate, hip_head=args.hip_head,
-                                                                                            hip_w8=args.hip_w8)
+                                                                                            hip_w8=args.hip_w8, hip_sample=args.hip_sample,
+                                                                                            hip_sample_seed=sample_seed(args))
     Harness(args, kind, cond, device).run_tasks(tasks(args))
 
 
