@@ -836,6 +836,85 @@ class HipLogMel(_Patch):
         _Patch.__init__(self, processor, "feature_extractor", _HipFeatureExtractor(fe, self.logmel, self))
 
 
+class _HipImageProcessor:
+    """What HipImage puts in a processor's `image_processor`: every attribute is the original's (get_slice_image_placeholder, version,
+    max_slice_nums, ...), and a call in the form the MiniCPM-o processor uses, on images none of which is sliced, runs ImageFrontEnd"""
+
+    def __init__(self, original, front, owner):
+        self.__dict__.update(_ip=original, _front=front, _owner=owner, _feature=type(original.preprocess([[]])))
+
+    def __getattr__(self, name):
+        return getattr(self._ip, name)
+
+    def _route(self, images, args, kw):
+        """The nested list of RGB PIL images of a call that is served, else the reason it is not"""
+        from PIL import Image
+        ip = self._ip
+        if args or not set(kw) <= {"do_pad", "max_slice_nums", "return_tensors"}:
+            return "another form of call"
+        if isinstance(images, Image.Image):
+            images = [[images]]
+        elif isinstance(images, (list, tuple)) and len(images) and isinstance(images[0], Image.Image):
+            images = [images]
+        if not isinstance(images, (list, tuple)) or not len(images) or not all(isinstance(g, (list, tuple)) and len(g) for g in images):
+            return "an empty or unknown batch"
+        slices = kw.get("max_slice_nums")
+        slices = ip.max_slice_nums if slices is None else int(slices)
+        for im in (im for g in images for im in g):
+            if not isinstance(im, Image.Image) or im.mode != "RGB":
+                return "an input that is not an RGB image of 8 bits per channel"
+            if ip.get_sliced_grid(im.size, slices) is not None:
+                return "an image that is sliced"
+            why = self._front.served(*im.size)              # a side over 70 patches, a scale whose LDS plan does not fit
+            if why is not None:
+                return why
+        return [list(g) for g in images]
+
+    def __call__(self, images, *args, **kw):
+        import numpy as np
+        routed = self._route(images, args, kw)
+        if isinstance(routed, str):
+            self._owner.fallbacks += 1
+            self._owner.last_reason = routed
+            return self._ip(images, *args, **kw)
+        self._owner.calls += 1
+        flat = [im for g in routed for im in g]
+        values, tgt = self._front(flat)
+        pixel_values, image_sizes, tgt_sizes, at = [], [], [], 0
+        for g in routed:
+            pixel_values.append(values[at:at + len(g)])
+            image_sizes.append([im.size for im in g])
+            tgt_sizes.append(np.vstack(tgt[at:at + len(g)]))
+            at += len(g)
+        # the processor's own feature type converts host values the way the original's return does; a tensor it would drop, so the
+        # device tensors go in afterwards, in the original's key order
+        feat = self._feature(data={"image_sizes": image_sizes, "tgt_sizes": tgt_sizes}, tensor_type=kw.get("return_tensors"))
+        feat.data = {"pixel_values": pixel_values, "image_sizes": feat.data["image_sizes"], "tgt_sizes": feat.data["tgt_sizes"]}
+        return feat
+
+
+class HipImage(_Patch):
+    """The image front end in front of the SigLIP tower on the HIP path (x2i_amd/image.py: ImageFrontEnd with the processor's own
+    scale_resolution, mean and std on `device`).  install() replaces `image_processor` ON THE PROCESSOR INSTANCE by an object that forwards
+    every attribute to the original and serves the call the MiniCPM-o processor makes (images, do_pad=, max_slice_nums=, return_tensors=):
+    the processor's own batch-feature type with `pixel_values` float32 [3, 14, 14 L] ON THE DEVICE and `image_sizes` and `tgt_sizes` as
+    the original gives them, nothing read back.  The WHOLE call goes to the original where an image would be sliced under the call's
+    max_slice_nums, is not an RGB PIL image, has a side over 70 patches or a scale the kernel refuses, or the call has another form;
+    `calls` and `fallbacks` count the two routes and `last_reason` says why the last fallback happened.  remove() restores the original.
+    Also a context manager.  Independent of HipSiglip and the other hand-offs."""
+
+    def __init__(self, processor, device="cuda"):
+        from .image import ImageFrontEnd
+        ip = getattr(processor, "image_processor", None)
+        if ip is None or not callable(ip) or not callable(getattr(ip, "get_sliced_grid", None)):
+            raise RuntimeError("handoff: no MiniCPM-o image processor (processor.image_processor) found in %s" % type(processor).__name__)
+        self.processor = processor
+        self.front = ImageFrontEnd.from_hf(ip, device)
+        self.calls = self.fallbacks = 0
+        self.last_reason = None
+        _Patch.__init__(self, processor, "image_processor", _HipImageProcessor(ip, self.front, self))
+
+
 def find_extract_feature(model):
     """What extract_feature of an InternVL2.5 chat model runs: (`model.vision_model`, `model.mlp1`), of a model that has the method"""
     v, m = getattr(model, "vision_model", None), getattr(model, "mlp1", None)

@@ -1,0 +1,204 @@
+"""The MiniCPM-o image front end on the HIP path: what `MiniCPMVImageProcessor.preprocess` computes on the host for an image that is
+not sliced (max_slice_nums = 1, a video's frames) -- Pillow's BICUBIC resize to the processor's best size, / 255, (x - mean) / std, the strip
+layout [3, 14, 14 L] -- as one launch of libx2i_hip.so per group of equally sized frames (include/frontend/x2i_image.h, csrc/image.hip).
+The tower behind it is x2i_amd/siglip.py.
+
+The arithmetic (Pillow's integer resample with its 22-bit coefficients and the uint8 image between the two passes, a 256-entry table per
+channel for the normalisation) stands in the header; the result equals the processor's float32 values bit for bit.
+
+Host work of a call: the coefficient tables are made once per (in, out) pair, in float64, and kept on the device; the normalisation table is
+made once (from_hf).  A call copies each group of equally sized frames into one pinned buffer, starts one asynchronous transfer and one
+launch per group.  No device-to-host read.  The only wait is for the previous call's transfers out of the same pinned buffer, before it is
+overwritten.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import image_binding as ib
+
+PATCH = ib.PATCH
+
+
+def cubic(t, a=-0.5):
+    t = abs(t)
+    if t < 1.0:
+        return ((a + 2.0) * t - (a + 3.0)) * t * t + 1.0
+    if t < 2.0:
+        return (((t - 5.0) * t + 8.0) * t - 4.0) * a
+    return 0.0
+
+
+def axis_tables(n_in, n_out):
+    """(bound int32 [n_out, 2], coef int32 [n_out, ksize]) of include/frontend/x2i_image.h for one axis, in float64 with the sums in
+    Pillow's order.  ValueError where sum |K| 255 + 2^21 would not fit the int32 accumulator."""
+    k = ib.ksize(n_in, n_out)
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    bound = np.zeros((n_out, 2), dtype=np.int32)
+    coef = np.zeros((n_out, k), dtype=np.int32)
+    one = float(1 << ib.PRECISION_BITS)
+    for xx in range(n_out):
+        xmin, xmax = ib.window(n_in, n_out, xx)
+        center = (xx + 0.5) * scale
+        w = [cubic((x + xmin - center + 0.5) / fs) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        bound[xx] = (xmin, xmax)
+        for x in range(xmax):
+            kx = w[x] / ww
+            coef[xx, x] = int(kx * one + 0.5) if kx >= 0 else int(kx * one - 0.5)
+    worst = int(np.abs(coef.astype(np.int64)).sum(axis=1).max())
+    if worst * 255 + (1 << (ib.PRECISION_BITS - 1)) >= 1 << 31:
+        raise ValueError("x2i_amd ImageFrontEnd: the coefficients of %d -> %d sum to %d in absolute value; the int32 accumulator holds "
+                         "sums below %d" % (n_in, n_out, worst, ((1 << 31) - (1 << (ib.PRECISION_BITS - 1))) // 255))
+    return bound, coef
+
+
+def norm_lut(mean, std):
+    """float32 [3, 256]: the processor's own numpy expressions, astype(float32) / 255 and then (x - mean) / std with mean and std cast to
+    float32 (transformers' normalize casts them to the image's dtype)"""
+    v = np.arange(256, dtype=np.uint8).astype(np.float32) / 255
+    return np.stack([(v - np.float32(mean[c])) / np.float32(std[c]) for c in range(3)]).astype(np.float32)
+
+
+class ImagePlan:
+    """The buffers of calls on at most `nbytes` bytes of frames (ImageFrontEnd.plan)"""
+
+
+class ImageFrontEnd:
+    """frames -> ([float32 [3, 14, 14 L] on the device], tgt_sizes).  mean, std: three values each; scale_resolution: the processor's."""
+
+    def __init__(self, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), scale_resolution=448, device="cuda"):
+        mean, std = [float(v) for v in mean], [float(v) for v in std]
+        if len(mean) != 3 or len(std) != 3 or not all(std):
+            raise ValueError("x2i_amd ImageFrontEnd: mean and std must hold three values, std none of them zero (got %r, %r)" % (mean, std))
+        if int(scale_resolution) < PATCH:
+            raise ValueError("x2i_amd ImageFrontEnd: scale_resolution = %r must be at least the patch size 14" % (scale_resolution,))
+        self.scale_resolution, self.device = int(scale_resolution), torch.device(device)
+        self.lut = torch.from_numpy(norm_lut(mean, std)).to(self.device)
+        self._tables = {}
+        self._plan = None
+
+    @classmethod
+    def from_hf(cls, image_processor, device="cuda"):
+        """The front end of a MiniCPMVImageProcessor: its scale_resolution, mean and std.  ValueError, naming the field, for what the kernel
+        does not serve."""
+        ip = image_processor
+        if ip.patch_size != PATCH:
+            raise ValueError("x2i_amd ImageFrontEnd: patch_size = %r; the kernel is built for patch_size = 14" % (ip.patch_size,))
+        if not getattr(ip, "slice_mode", True):
+            raise ValueError("x2i_amd ImageFrontEnd: slice_mode is off; without it the processor does not resize and the front end does not apply")
+        return cls(np.asarray(ip.mean).reshape(-1), np.asarray(ip.std).reshape(-1), ip.scale_resolution, device)
+
+    def best_size(self, w, h):
+        """The processor's find_best_resize((w, h), scale_resolution, 14, allow_upscale=True)"""
+        r = w / h
+        height = int(self.scale_resolution / math.sqrt(r))
+        width = int(height * r)
+        fit = lambda v: max(round(v / PATCH) * PATCH, PATCH)   # noqa: E731
+        return fit(width), fit(height)
+
+    def tables(self, n_in, n_out):
+        """(bound, coef) of one axis on the device, made once per (n_in, n_out); (None, None) where the axis does not resize"""
+        if n_in == n_out:
+            return None, None
+        t = self._tables.get((n_in, n_out))
+        if t is None:
+            t = self._tables[(n_in, n_out)] = tuple(torch.from_numpy(a).to(self.device) for a in axis_tables(n_in, n_out))
+        return t
+
+    def served(self, w, h):
+        """None where frames of w x h pixels are served, else the reason they are not (the kernel's own refusal)"""
+        try:
+            ow, oh = self.best_size(w, h)
+            ib.check_sizes(w, h, ow, oh)
+        except ib.X2IError as e:
+            return str(e)
+        return None
+
+    # ------------------------------------------------------------------ plan
+    def plan(self, nbytes):
+        """The pinned staging buffer and the device frame buffer of calls on at most nbytes bytes of frames"""
+        nbytes = int(nbytes)
+        if nbytes < 1:
+            raise ValueError("x2i_amd ImageFrontEnd: a plan needs at least one byte of frames (got %d)" % nbytes)
+        p = ImagePlan()
+        cuda = self.device.type == "cuda"
+        p.nbytes, p.device = nbytes, self.device
+        p.stage = torch.empty(nbytes, dtype=torch.uint8, pin_memory=cuda)
+        p.dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        p.sent = torch.cuda.Event() if cuda else None
+        p.busy = False
+        return p
+
+    @staticmethod
+    def _as_arrays(frames):
+        """A list of uint8 [H, W, 3] arrays of PIL RGB images, arrays, or one [n, H, W, 3] array"""
+        if isinstance(frames, np.ndarray) and frames.ndim == 4:
+            frames = list(frames)
+        out = []
+        for f in frames:
+            if not isinstance(f, np.ndarray):
+                if getattr(f, "mode", None) != "RGB":
+                    raise ValueError("x2i_amd ImageFrontEnd: a frame must be a PIL image of mode RGB or a uint8 [H, W, 3] array (got %r)"
+                                     % (getattr(f, "mode", type(f).__name__),))
+                f = np.asarray(f)
+            if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or not f.shape[0] or not f.shape[1]:
+                raise ValueError("x2i_amd ImageFrontEnd: a frame must be a uint8 [H, W, 3] array (got %s %s)" % (f.dtype, f.shape))
+            out.append(f)
+        if not out:
+            raise ValueError("x2i_amd ImageFrontEnd: frames must be a non-empty list")
+        return out
+
+    # ------------------------------------------------------------------ call
+    @torch.no_grad()
+    def __call__(self, frames, out_dtype=torch.float32, plan=None):
+        """frames: PIL RGB images, uint8 [H, W, 3] arrays, or one uint8 [n, H, W, 3] array.  -> (a list of [3, 14, 14 L] tensors of
+        out_dtype (float32 or bfloat16) on the device, views of one buffer, in the order of the frames; tgt_sizes, a host int array [n, 2]
+        of (patch rows, patch columns))."""
+        arrays = self._as_arrays(frames)
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("x2i_amd ImageFrontEnd: out_dtype must be float32 or bfloat16 (got %r)" % (out_dtype,))
+        groups = {}                                             # (w, h) -> frame indices, in the order of first appearance
+        for i, a in enumerate(arrays):
+            groups.setdefault((a.shape[1], a.shape[0]), []).append(i)
+        sizes = {wh: self.best_size(*wh) for wh in groups}
+        for (w, h), (ow, oh) in sizes.items():
+            ib.check_sizes(w, h, ow, oh)
+        nbytes = sum(a.size for a in arrays)
+        if plan is None:
+            plan = self._plan
+            if plan is None or plan.nbytes < nbytes or plan.device != self.device:
+                plan = self._plan = self.plan(nbytes)
+        if plan.nbytes < nbytes or plan.device != self.device:
+            raise ValueError("x2i_amd ImageFrontEnd: the plan holds %d bytes on %s; the call holds %d bytes of frames on %s"
+                             % (plan.nbytes, plan.device, nbytes, self.device))
+        if self.device.type != "cuda":
+            raise ib.X2IError("x2i_amd: ImageFrontEnd runs on the GPU only (the module is on %s); there is no CPU fallback" % (self.device,))
+        tabs = {wh: self.tables(wh[0], sizes[wh][0]) + self.tables(wh[1], sizes[wh][1]) for wh in groups}
+        elems = {wh: 3 * sizes[wh][0] * sizes[wh][1] for wh in groups}
+        out = torch.empty(sum(elems[wh] * len(idx) for wh, idx in groups.items()), dtype=out_dtype, device=self.device)
+        if plan.busy:
+            plan.sent.synchronize()                            # the previous call's transfers out of the staging buffer (long done, as a rule)
+        stage = plan.stage.numpy()
+        views, src, dst = [None] * len(arrays), 0, 0
+        for (w, h), idx in groups.items():
+            (ow, oh), n, fb = sizes[(w, h)], len(idx), 3 * w * h
+            pinned = stage[src:src + n * fb].reshape(n, h, w, 3)
+            for j, i in enumerate(idx):
+                pinned[j] = arrays[i]
+            plan.dev[src:src + n * fb].copy_(plan.stage[src:src + n * fb], non_blocking=True)
+            hb, hc, vb, vc = tabs[(w, h)]
+            L14 = oh // PATCH * ow
+            ib.frontend(plan.dev[src:src + n * fb], w, h, 3 * w, fb, n, ow, oh, hb, hc, vb, vc, self.lut, out[dst:dst + n * elems[(w, h)]],
+                        elems[(w, h)], L14)
+            for j, i in enumerate(idx):
+                views[i] = out[dst + j * elems[(w, h)]:dst + (j + 1) * elems[(w, h)]].view(3, PATCH, L14)
+            src, dst = src + n * fb, dst + n * elems[(w, h)]
+        plan.sent.record()
+        plan.busy = True
+        tgt = np.array([(sizes[(a.shape[1], a.shape[0])][1] // PATCH, sizes[(a.shape[1], a.shape[0])][0] // PATCH) for a in arrays])
+        return views, tgt

@@ -92,6 +92,12 @@ def build_parser(family):
                         "processor's WhisperFeatureExtractor (handoff.HipLogMel), so that a waveform reaches the device as samples and the "
                         "features never exist on the host; independent of --hip_audio, which takes the device features as they are; "
                         "MiniCPM-o only")
+    p.add_argument("--hip_image", action="store_true",
+                   help="compute the vision tower's input on the HIP path: the image front end (x2i_amd/image.py) in place of the "
+                        "processor's MiniCPMVImageProcessor (handoff.HipImage) for images that are not sliced -- a video's frames: Pillow's "
+                        "BICUBIC resize, the normalisation and the strip layout in one launch per group of equally sized frames, bit for bit "
+                        "the processor's values, so that the frames reach the device as bytes; a call with a sliced image goes to the "
+                        "original; independent of the other --hip_* flags; MiniCPM-o only")
     p.add_argument("--hip_generate", action="store_true",
                    help="run the MLLM's greedy 128-token generate() with the decoder stack on the HIP path over the prompt and over the "
                         "generated tokens (key/value cache, x2i_amd/qwen.py decode_step); serves --use_answer; Qwen2.5-VL only")

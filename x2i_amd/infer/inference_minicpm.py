@@ -26,7 +26,7 @@ class MiniCPMConditioner:
     dependence on the reference's patched generate() returning `.hidden_states`.  full_generate: the reference's form."""
 
     def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None, processor=None, hip_vision=False, hip_resampler=False,
-                 hip_audio=False, hip_decoder=False, use_answer=False, hip_mel=False):
+                 hip_audio=False, hip_decoder=False, use_answer=False, hip_mel=False, hip_image=False):
         if hip_decoder and not (prefill_only and not use_answer):     # (refused before a checkpoint is read)
             raise ValueError("--hip_decoder serves the prompt pass only: not with --full_generate or --use_answer")
         if model is None:
@@ -69,6 +69,12 @@ class MiniCPMConditioner:
         if hip_mel:
             from ..handoff import HipLogMel
             self.mel = HipLogMel(self.processor, device).install()
+        # hip_image: the pixel_values of images that are not sliced (a video's frames) on the HIP path (x2i_amd/image.py) in place of the
+        # processor's image processor: the processor hands on device tensors, bit for bit the host's values
+        self.image = None
+        if hip_image:
+            from ..handoff import HipImage
+            self.image = HipImage(self.processor, device).install()
 
     def hidden_states(self, inputs):
         """processor outputs -> [B, C, S, H]"""
@@ -127,6 +133,7 @@ def main(argv=None):
                                                                                               hip_resampler=args.hip_resampler,
                                                                                               hip_audio=args.hip_audio,
                                                                                               hip_mel=args.hip_mel,
+                                                                                              hip_image=args.hip_image,
                                                                                               hip_decoder=args.hip_decoder,
                                                                                               use_answer=args.use_answer)
     Harness(args, "minicpm", cond, device).run_tasks(tasks(args))
