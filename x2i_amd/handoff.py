@@ -838,7 +838,8 @@ class HipLogMel(_Patch):
 
 class _HipImageProcessor:
     """What HipImage puts in a processor's `image_processor`: every attribute is the original's (get_slice_image_placeholder, version,
-    max_slice_nums, ...), and a call in the form the MiniCPM-o processor uses, on images none of which is sliced, runs ImageFrontEnd"""
+    max_slice_nums, ...), and a call in the form the MiniCPM-o processor uses runs ImageFrontEnd: on images none of which is sliced, or,
+    for a HipImage(slices=True), on sliced images too"""
 
     def __init__(self, original, front, owner):
         self.__dict__.update(_ip=original, _front=front, _owner=owner, _feature=type(original.preprocess([[]])))
@@ -847,7 +848,7 @@ class _HipImageProcessor:
         return getattr(self._ip, name)
 
     def _route(self, images, args, kw):
-        """The nested list of RGB PIL images of a call that is served, else the reason it is not"""
+        """(the nested list of RGB PIL images, the call's max_slice_nums) of a call that is served, else the reason it is not"""
         from PIL import Image
         ip = self._ip
         if args or not set(kw) <= {"do_pad", "max_slice_nums", "return_tensors"}:
@@ -863,12 +864,18 @@ class _HipImageProcessor:
         for im in (im for g in images for im in g):
             if not isinstance(im, Image.Image) or im.mode != "RGB":
                 return "an input that is not an RGB image of 8 bits per channel"
-            if ip.get_sliced_grid(im.size, slices) is not None:
-                return "an image that is sliced"
-            why = self._front.served(*im.size)              # a side over 70 patches, a scale whose LDS plan does not fit
+            if not self._owner.slices:
+                if ip.get_sliced_grid(im.size, slices) is not None:
+                    return "an image that is sliced"
+                why = self._front.served(*im.size)          # a side over 70 patches, a scale whose LDS plan does not fit
+            else:
+                grid = ip.get_sliced_grid(im.size, slices)
+                if (None if grid is None else tuple(grid)) != self._front.sliced_grid(im.size[0], im.size[1], slices):
+                    return "a slicing grid other than the front end's"
+                why = self._front.served(im.size[0], im.size[1], slices)
             if why is not None:
                 return why
-        return [list(g) for g in images]
+        return [list(g) for g in images], (slices if self._owner.slices else 1)
 
     def __call__(self, images, *args, **kw):
         import numpy as np
@@ -878,11 +885,16 @@ class _HipImageProcessor:
             self._owner.last_reason = routed
             return self._ip(images, *args, **kw)
         self._owner.calls += 1
+        routed, slices = routed
         flat = [im for g in routed for im in g]
-        values, tgt = self._front(flat)
+        if slices > 1:                                      # per image [source image, crops ...], in a row like the original's
+            values, tgt = self._front.sliced(flat, slices)
+        else:
+            values, tgt = self._front(flat)
+            values = [[v] for v in values]
         pixel_values, image_sizes, tgt_sizes, at = [], [], [], 0
         for g in routed:
-            pixel_values.append(values[at:at + len(g)])
+            pixel_values.append([v for vs in values[at:at + len(g)] for v in vs])
             image_sizes.append([im.size for im in g])
             tgt_sizes.append(np.vstack(tgt[at:at + len(g)]))
             at += len(g)
@@ -901,15 +913,19 @@ class HipImage(_Patch):
     the original gives them, nothing read back.  The WHOLE call goes to the original where an image would be sliced under the call's
     max_slice_nums, is not an RGB PIL image, has a side over 70 patches or a scale the kernel refuses, or the call has another form;
     `calls` and `fallbacks` count the two routes and `last_reason` says why the last fallback happened.  remove() restores the original.
-    Also a context manager.  Independent of HipSiglip and the other hand-offs."""
+    Also a context manager.  Independent of HipSiglip and the other hand-offs.
+    slices=True (not the default) also serves a call with images that are sliced under the call's max_slice_nums: per image the source image
+    and the crops of the processor's grid, row by row, in one list like the original's, `tgt_sizes` one row per entry; the crops cost one
+    more launch per group of equally sized images (include/frontend/tiles/x2i_image_tiles.h).  Every other refusal stays."""
 
-    def __init__(self, processor, device="cuda"):
+    def __init__(self, processor, device="cuda", slices=False):
         from .image import ImageFrontEnd
         ip = getattr(processor, "image_processor", None)
         if ip is None or not callable(ip) or not callable(getattr(ip, "get_sliced_grid", None)):
             raise RuntimeError("handoff: no MiniCPM-o image processor (processor.image_processor) found in %s" % type(processor).__name__)
         self.processor = processor
         self.front = ImageFrontEnd.from_hf(ip, device)
+        self.slices = bool(slices)
         self.calls = self.fallbacks = 0
         self.last_reason = None
         _Patch.__init__(self, processor, "image_processor", _HipImageProcessor(ip, self.front, self))

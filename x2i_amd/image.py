@@ -3,6 +3,10 @@ not sliced (max_slice_nums = 1, a video's frames) -- Pillow's BICUBIC resize to 
 layout [3, 14, 14 L] -- as one launch of libx2i_hip.so per group of equally sized frames (include/frontend/x2i_image.h, csrc/image.hip).
 The tower behind it is x2i_amd/siglip.py.
 
+An image that the processor slices (more than scale_resolution^2 pixels under max_slice_nums > 1) goes through `sliced`: the source image
+by the same launch, and the crops of the refine-size image by one launch of include/frontend/tiles/x2i_image_tiles.h (csrc/image_tiles.hip)
+per group, in the processor's order [source, crops row by row].
+
 The arithmetic (Pillow's integer resample with its 22-bit coefficients and the uint8 image between the two passes, a 256-entry table per
 channel for the normalisation) stands in the header; the result equals the processor's float32 values bit for bit.
 
@@ -16,7 +20,7 @@ import math
 import numpy as np
 import torch
 
-from . import image_binding as ib
+from . import image_binding as ib, image_tiles_binding as itb
 
 PATCH = ib.PATCH
 
@@ -101,6 +105,40 @@ class ImageFrontEnd:
         fit = lambda v: max(round(v / PATCH) * PATCH, PATCH)   # noqa: E731
         return fit(width), fit(height)
 
+    def sliced_grid(self, w, h, max_slice_nums):
+        """The processor's get_sliced_grid((w, h), max_slice_nums): (gx, gy), or None for an image that is not sliced"""
+        sr = self.scale_resolution
+        multiple = min(math.ceil(w * h / (sr * sr)), int(max_slice_nums))
+        if multiple <= 1:
+            return None
+        best, err = (1, 1), float("inf")
+        for n in (multiple - 1, multiple, multiple + 1):
+            if n == 1 or n > max_slice_nums:
+                continue
+            for m in range(1, n + 1):                          # the first of equally near grids stays, as in the processor
+                if n % m == 0:
+                    e = abs(math.log(w / h) - math.log(m / (n // m)))
+                    if e < err:
+                        best, err = (m, n // m), e
+        return best
+
+    def refine_size(self, w, h, grid):
+        """The processor's get_refine_size((w, h), grid, allow_upscale=True): the grid's cell -- a float size, sides rounded to the grid
+        with Python's round (ties to even) -- fitted like an image of its own, times the grid"""
+        gx, gy = grid
+        fit = lambda v, g: max(round(v / g) * g, g)   # noqa: E731
+        cw, ch = self.best_size(fit(w, gx) / gx, fit(h, gy) / gy)
+        return cw * gx, ch * gy
+
+    def slice_plan(self, w, h, max_slice_nums=1):
+        """(source size, grid or None, crop size or None) of a w x h image.  The source image of a sliced image is
+        find_best_resize(allow_upscale=False); an image is sliced only where w h > scale_resolution^2, where that is best_size."""
+        grid = self.sliced_grid(w, h, max_slice_nums)
+        if grid is None:
+            return self.best_size(w, h), None, None
+        rw, rh = self.refine_size(w, h, grid)
+        return self.best_size(w, h), grid, (rw // grid[0], rh // grid[1])
+
     def tables(self, n_in, n_out):
         """(bound, coef) of one axis on the device, made once per (n_in, n_out); (None, None) where the axis does not resize"""
         if n_in == n_out:
@@ -110,11 +148,13 @@ class ImageFrontEnd:
             t = self._tables[(n_in, n_out)] = tuple(torch.from_numpy(a).to(self.device) for a in axis_tables(n_in, n_out))
         return t
 
-    def served(self, w, h):
+    def served(self, w, h, max_slice_nums=1):
         """None where frames of w x h pixels are served, else the reason they are not (the kernel's own refusal)"""
         try:
-            ow, oh = self.best_size(w, h)
+            (ow, oh), grid, crop = self.slice_plan(w, h, max_slice_nums)
             ib.check_sizes(w, h, ow, oh)
+            if grid is not None:
+                itb.check_sizes(w, h, crop[0] * grid[0], crop[1] * grid[1], crop[0], crop[1])
         except ib.X2IError as e:
             return str(e)
         return None
@@ -158,16 +198,29 @@ class ImageFrontEnd:
     def __call__(self, frames, out_dtype=torch.float32, plan=None):
         """frames: PIL RGB images, uint8 [H, W, 3] arrays, or one uint8 [n, H, W, 3] array.  -> (a list of [3, 14, 14 L] tensors of
         out_dtype (float32 or bfloat16) on the device, views of one buffer, in the order of the frames; tgt_sizes, a host int array [n, 2]
-        of (patch rows, patch columns))."""
+        of (patch rows, patch columns)).  No frame is sliced (max_slice_nums = 1)."""
+        values, tgt = self.sliced(frames, 1, out_dtype, plan)
+        return [v[0] for v in values], np.vstack(tgt)
+
+    @torch.no_grad()
+    def sliced(self, frames, max_slice_nums=9, out_dtype=torch.float32, plan=None):
+        """The processor's get_sliced_images per frame.  -> (per frame the list [source image, crops row by row] of [3, 14, 14 L] tensors
+        of out_dtype on the device, views of one buffer -- the source image alone for a frame that is not sliced; per frame a host int
+        array [slices, 2] of (patch rows, patch columns)).  A group of equally sized frames costs one launch for the source images and,
+        where they are sliced, one for the crops."""
         arrays = self._as_arrays(frames)
         if out_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("x2i_amd ImageFrontEnd: out_dtype must be float32 or bfloat16 (got %r)" % (out_dtype,))
+        if int(max_slice_nums) < 1:
+            raise ValueError("x2i_amd ImageFrontEnd: max_slice_nums = %r must be at least 1" % (max_slice_nums,))
         groups = {}                                             # (w, h) -> frame indices, in the order of first appearance
         for i, a in enumerate(arrays):
             groups.setdefault((a.shape[1], a.shape[0]), []).append(i)
-        sizes = {wh: self.best_size(*wh) for wh in groups}
-        for (w, h), (ow, oh) in sizes.items():
+        plans = {wh: self.slice_plan(wh[0], wh[1], int(max_slice_nums)) for wh in groups}
+        for (w, h), ((ow, oh), grid, crop) in plans.items():
             ib.check_sizes(w, h, ow, oh)
+            if grid is not None:
+                itb.check_sizes(w, h, crop[0] * grid[0], crop[1] * grid[1], crop[0], crop[1])
         nbytes = sum(a.size for a in arrays)
         if plan is None:
             plan = self._plan
@@ -178,27 +231,40 @@ class ImageFrontEnd:
                              % (plan.nbytes, plan.device, nbytes, self.device))
         if self.device.type != "cuda":
             raise ib.X2IError("x2i_amd: ImageFrontEnd runs on the GPU only (the module is on %s); there is no CPU fallback" % (self.device,))
-        tabs = {wh: self.tables(wh[0], sizes[wh][0]) + self.tables(wh[1], sizes[wh][1]) for wh in groups}
-        elems = {wh: 3 * sizes[wh][0] * sizes[wh][1] for wh in groups}
-        out = torch.empty(sum(elems[wh] * len(idx) for wh, idx in groups.items()), dtype=out_dtype, device=self.device)
+        elems = {}                                              # (w, h) -> elements of a frame's source image, of one crop, crops per frame
+        for wh, ((ow, oh), grid, crop) in plans.items():
+            elems[wh] = (3 * ow * oh, 0, 0) if grid is None else (3 * ow * oh, 3 * crop[0] * crop[1], grid[0] * grid[1])
+            for n_in, n_out in ((wh[0], ow), (wh[1], oh)) + (() if grid is None else ((wh[0], crop[0] * grid[0]), (wh[1], crop[1] * grid[1]))):
+                self.tables(n_in, n_out)                        # every table is made, and its accumulator bound checked, before any launch
+        out = torch.empty(sum((e + c * k) * len(groups[wh]) for wh, (e, c, k) in elems.items()), dtype=out_dtype, device=self.device)
         if plan.busy:
             plan.sent.synchronize()                            # the previous call's transfers out of the staging buffer (long done, as a rule)
         stage = plan.stage.numpy()
-        views, src, dst = [None] * len(arrays), 0, 0
+        views, tgt, src, dst = [None] * len(arrays), [None] * len(arrays), 0, 0
         for (w, h), idx in groups.items():
-            (ow, oh), n, fb = sizes[(w, h)], len(idx), 3 * w * h
+            ((ow, oh), grid, crop), n, fb = plans[(w, h)], len(idx), 3 * w * h
+            e, c, k = elems[(w, h)]
             pinned = stage[src:src + n * fb].reshape(n, h, w, 3)
             for j, i in enumerate(idx):
                 pinned[j] = arrays[i]
             plan.dev[src:src + n * fb].copy_(plan.stage[src:src + n * fb], non_blocking=True)
-            hb, hc, vb, vc = tabs[(w, h)]
+            dev = plan.dev[src:src + n * fb]
             L14 = oh // PATCH * ow
-            ib.frontend(plan.dev[src:src + n * fb], w, h, 3 * w, fb, n, ow, oh, hb, hc, vb, vc, self.lut, out[dst:dst + n * elems[(w, h)]],
-                        elems[(w, h)], L14)
+            ib.frontend(dev, w, h, 3 * w, fb, n, ow, oh, *self.tables(w, ow), *self.tables(h, oh), self.lut, out[dst:dst + n * e], e, L14)
             for j, i in enumerate(idx):
-                views[i] = out[dst + j * elems[(w, h)]:dst + (j + 1) * elems[(w, h)]].view(3, PATCH, L14)
-            src, dst = src + n * fb, dst + n * elems[(w, h)]
+                views[i] = [out[dst + j * e:dst + (j + 1) * e].view(3, PATCH, L14)]
+                tgt[i] = [(oh // PATCH, ow // PATCH)]
+            dst += n * e
+            if grid is not None:
+                (cw, ch), (gx, gy) = crop, grid
+                C14 = ch // PATCH * cw
+                itb.tiles(dev, w, h, 3 * w, fb, n, cw * gx, ch * gy, cw, ch, *self.tables(w, cw * gx), *self.tables(h, ch * gy), self.lut,
+                          out[dst:dst + n * k * c], k * c, c, C14, itb.STRIP)
+                for j, i in enumerate(idx):
+                    views[i] += [out[dst + (j * k + t) * c:dst + (j * k + t + 1) * c].view(3, PATCH, C14) for t in range(k)]
+                    tgt[i] += [(ch // PATCH, cw // PATCH)] * k
+                dst += n * k * c
+            src += n * fb
         plan.sent.record()
         plan.busy = True
-        tgt = np.array([(sizes[(a.shape[1], a.shape[0])][1] // PATCH, sizes[(a.shape[1], a.shape[0])][0] // PATCH) for a in arrays])
-        return views, tgt
+        return views, [np.array(t) for t in tgt]

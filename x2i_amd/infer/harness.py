@@ -50,6 +50,10 @@ def build_parser(family):
         p.add_argument("--internvl_path", type=str, default=None)
     elif family == "minicpm":
         p.add_argument("--minicpm_path", type=str, default="openbmb/MiniCPM-o-2_6")
+        p.add_argument("--max_slice_nums", type=int, default=1,
+                       help="the max_slice_nums handed to the MiniCPM-o processor (the reference's value is 1: no image is sliced; the "
+                            "processor's own default is 9).  Above 1 an image over 448 x 448 pixels becomes a source image and a grid of "
+                            "crops; with --hip_image these come from the HIP path too (handoff.HipImage(slices=True))")
     p.add_argument("--proj_path", type=str, default=None, help="projector checkpoint (diffusion_pytorch_model.bin)")
     p.add_argument("--flux_path", type=str, default="shuttleai/shuttle-3-diffusion")
     p.add_argument("--use_answer", type=bool, default=False)  # type=bool kept as in the reference (any non-empty string -> True)
@@ -97,7 +101,9 @@ def build_parser(family):
                         "processor's MiniCPMVImageProcessor (handoff.HipImage) for images that are not sliced -- a video's frames: Pillow's "
                         "BICUBIC resize, the normalisation and the strip layout in one launch per group of equally sized frames, bit for bit "
                         "the processor's values, so that the frames reach the device as bytes; a call with a sliced image goes to the "
-                        "original; independent of the other --hip_* flags; MiniCPM-o only")
+                        "original unless --max_slice_nums is above 1, which serves the source image and the crops of the slicing grid too "
+                        "(include/frontend/tiles/x2i_image_tiles.h).  InternVL2.5: the conditioner's 448 x 448 tile from "
+                        "x2i_amd/internvl_image.py (InternVLImageFrontEnd), bit for bit the host's tile; independent of the other --hip_* flags")
     p.add_argument("--hip_generate", action="store_true",
                    help="run the MLLM's greedy 128-token generate() with the decoder stack on the HIP path over the prompt and over the "
                         "generated tokens (key/value cache, x2i_amd/qwen.py decode_step); serves --use_answer; Qwen2.5-VL only")

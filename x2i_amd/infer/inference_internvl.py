@@ -37,7 +37,8 @@ class InternVLConditioner:
     (whose generate() returns token ids); full_generate expects the reference's locally modified modeling_internvl_chat.py, whose
     generate() is one forward returning every layer's hidden states (model_internvl/internvl/modeling_internvl_chat.py:314-363)."""
 
-    def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None, hip_vision=False, hip_decoder=False, use_answer=False):
+    def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None, hip_vision=False, hip_decoder=False, use_answer=False,
+                 hip_image=False):
         if hip_decoder and not (prefill_only and not use_answer):     # (refused before a checkpoint is read)
             raise ValueError("--hip_decoder serves the prompt pass only: not with --full_generate or --use_answer")
         if model is None:
@@ -61,6 +62,12 @@ class InternVLConditioner:
         if hip_vision:
             from ..handoff import HipInternVision
             self.vision = HipInternVision(self.model).install()
+        # hip_image: the 448 x 448 tile of an image on the HIP path (x2i_amd/internvl_image.py): the 128 x 128 shrink stays on the host, its
+        # resize to the tile and the normalisation run on the device, bit for bit the tile computed below without the flag
+        self.image = None
+        if hip_image:
+            from ..internvl_image import InternVLImageFrontEnd
+            self.image = InternVLImageFrontEnd(448, device=device)
 
     def hidden_states(self, pixel_values, input_ids, attention_mask):
         if self.prompt is not None:
@@ -71,19 +78,24 @@ class InternVLConditioner:
         hs = self.model.generate(pixel_values=pixel_values, input_ids=input_ids, attention_mask=attention_mask)
         return torch.stack(tuple(hs), dim=1)
 
+    def image_tiles(self, images):
+        """bf16 [images, 3, 448, 448] on the device: per image a 128 x 128 resize, then a single 448 x 448 ImageNet-normalised tile
+        (inference_internvl.py:171)"""
+        from PIL import Image
+        import numpy as np
+        small = [Image.open(p).convert("RGB").resize((128, 128)) for p in images]
+        if self.image is not None:      # max_num = 1: one tile per image; bf16 as one rounding of the float32 value, like .to(bfloat16) below
+            return self.image.tiles(small, max_num=1, out_dtype=torch.bfloat16)[0]
+        tiles = []
+        for im in small:
+            a = torch.from_numpy(np.asarray(im.resize((448, 448)))).float().div(255).permute(2, 0, 1)
+            mean, std = torch.tensor([0.485, 0.456, 0.406])[:, None, None], torch.tensor([0.229, 0.224, 0.225])[:, None, None]
+            tiles.append((a - mean) / std)
+        return torch.stack(tiles).to(self.device, torch.bfloat16)
+
     @torch.no_grad()
     def __call__(self, videos=None, images=None, audios=None, text_prompt=None):
-        pixel_values = None
-        if images:
-            from PIL import Image
-            import numpy as np
-            tiles = []
-            for p in images:  # 128x128 resize then a single 448x448 ImageNet-normalised tile (inference_internvl.py:171)
-                im = Image.open(p).convert("RGB").resize((128, 128)).resize((448, 448))
-                a = torch.from_numpy(np.asarray(im)).float().div(255).permute(2, 0, 1)
-                mean, std = torch.tensor([0.485, 0.456, 0.406])[:, None, None], torch.tensor([0.229, 0.224, 0.225])[:, None, None]
-                tiles.append((a - mean) / std)
-            pixel_values = torch.stack(tiles).to(self.device, torch.bfloat16)
+        pixel_values = self.image_tiles(images) if images else None
         # one 448 x 448 tile per image; the context tokens the features are merged into come with the query (as the chat model's own chat()
         # does, the id of the context token is set on the model before generate() looks for it)
         q = build_query(text_prompt, [1] * len(images or []), getattr(self.model, "num_image_token", NUM_IMAGE_TOKEN))
@@ -111,7 +123,7 @@ def main(argv=None):
     cond = SyntheticConditioner(kind, device) if args.synthetic else InternVLConditioner(args.internvl_path, device,
                                                                                          prefill_only=not args.full_generate,
                                                                                          hip_vision=args.hip_vision, hip_decoder=args.hip_decoder,
-                                                                                         use_answer=args.use_answer)
+                                                                                         use_answer=args.use_answer, hip_image=args.hip_image)
     Harness(args, kind, cond, device).run_tasks(tasks(args))
 
 

@@ -26,7 +26,7 @@ class MiniCPMConditioner:
     dependence on the reference's patched generate() returning `.hidden_states`.  full_generate: the reference's form."""
 
     def __init__(self, path, device, prefill_only=True, model=None, tokenizer=None, processor=None, hip_vision=False, hip_resampler=False,
-                 hip_audio=False, hip_decoder=False, use_answer=False, hip_mel=False, hip_image=False):
+                 hip_audio=False, hip_decoder=False, use_answer=False, hip_mel=False, hip_image=False, max_slice_nums=1):
         if hip_decoder and not (prefill_only and not use_answer):     # (refused before a checkpoint is read)
             raise ValueError("--hip_decoder serves the prompt pass only: not with --full_generate or --use_answer")
         if model is None:
@@ -71,10 +71,15 @@ class MiniCPMConditioner:
             self.mel = HipLogMel(self.processor, device).install()
         # hip_image: the pixel_values of images that are not sliced (a video's frames) on the HIP path (x2i_amd/image.py) in place of the
         # processor's image processor: the processor hands on device tensors, bit for bit the host's values
+        # max_slice_nums: what the processor is called with (1, the reference's value: no image is sliced).  Above 1 the hand-off serves
+        # the sliced images too: the source image and the crops of the slicing grid (include/frontend/tiles/x2i_image_tiles.h)
+        self.max_slice_nums = int(max_slice_nums)
+        if self.max_slice_nums < 1:
+            raise ValueError("--max_slice_nums must be at least 1 (got %d)" % self.max_slice_nums)
         self.image = None
         if hip_image:
             from ..handoff import HipImage
-            self.image = HipImage(self.processor, device).install()
+            self.image = HipImage(self.processor, device, slices=self.max_slice_nums > 1).install()
 
     def hidden_states(self, inputs):
         """processor outputs -> [B, C, S, H]"""
@@ -105,7 +110,7 @@ class MiniCPMConditioner:
         prompt = self.processor.tokenizer.apply_chat_template([{"role": "user", "content": text}], tokenize=False,
                                                               add_generation_prompt=True)
         inputs = self.processor(text=[prompt], images=[image_list] if image_list else None,
-                                audios=[audio_list] if audio_list else None, max_slice_nums=1, use_image_id=False,
+                                audios=[audio_list] if audio_list else None, max_slice_nums=self.max_slice_nums, use_image_id=False,
                                 chunk_input=True, return_tensors="pt", max_length=32768, sampling_rate=16000,
                                 add_special_tokens=True).to(self.device)
         inputs.pop("image_sizes")
@@ -134,6 +139,7 @@ def main(argv=None):
                                                                                               hip_audio=args.hip_audio,
                                                                                               hip_mel=args.hip_mel,
                                                                                               hip_image=args.hip_image,
+                                                                                              max_slice_nums=args.max_slice_nums,
                                                                                               hip_decoder=args.hip_decoder,
                                                                                               use_answer=args.use_answer)
     Harness(args, "minicpm", cond, device).run_tasks(tasks(args))
