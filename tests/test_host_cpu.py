@@ -70,6 +70,55 @@ def test_no_cpu_fallback():
                       torch.zeros(64, dtype=torch.bfloat16), 1e-6)
 
 
+def test_pointer_and_count_wrappers_refuse_strided_mistyped_and_missized_tensors():
+    """ops.ln_affine, ops.softmax_rows_ and ops.adamw_ hand the library a bare pointer and an element count: a non-contiguous tensor, one of
+    another dtype or of another size is refused by name before the device is looked at, so before any launch"""
+    from x2i_amd import ops
+    from x2i_amd._lib import X2IError
+    bf, f = torch.bfloat16, torch.float32
+    X, w, b = torch.zeros((4, 64), dtype=bf), torch.ones(64, dtype=bf), torch.zeros(64, dtype=bf)
+    wide = torch.zeros((4, 128), dtype=bf)
+    cases = [(dict(X=wide[:, :64]), "X must be contiguous"), (dict(X=X.float()), "X must be torch.bfloat16"),
+             (dict(X=X.t()), "X must be contiguous"),
+             (dict(out=wide[:, :64]), "out must be contiguous"), (dict(out=torch.zeros((4, 64), dtype=f)), "out must be torch.bfloat16"),
+             (dict(out=torch.zeros((5, 64), dtype=bf)), "out must hold 256 elements"), (dict(out=torch.zeros((2, 64), dtype=bf)), "out must hold 256"),
+             (dict(weight=torch.ones(128, dtype=bf)[::2]), "weight must be contiguous"), (dict(weight=w.float()), "weight must be torch.bfloat16"),
+             (dict(weight=torch.ones(32, dtype=bf)), "weight must hold 64"), (dict(bias=torch.zeros(72, dtype=bf)), "bias must hold 64"),
+             (dict(bias=b.float()), "bias must be torch.bfloat16")]
+    for kw, msg in cases:
+        args = dict(X=X, weight=w, bias=b, eps=1e-6)
+        args.update(kw)
+        with pytest.raises(X2IError, match=msg):
+            ops.ln_affine(**args)
+    with pytest.raises(X2IError, match="must live on the GPU"):        # a well-formed call still has no CPU fallback
+        ops.ln_affine(X, w, b, 1e-6, out=torch.zeros((2, 2, 64), dtype=bf))
+
+    for x, msg in ((wide[:, :64], "x must be contiguous"), (X.float(), "x must be torch.bfloat16"), (X.t(), "x must be contiguous"),
+                   (X[::2], "x must be contiguous")):
+        with pytest.raises(X2IError, match=msg):
+            ops.softmax_rows_(x, 0.25)
+    with pytest.raises(X2IError, match="must live on the GPU"):
+        ops.softmax_rows_(X, 0.25)
+
+    n = 300
+    p, g, m, v = torch.zeros((3, 100), dtype=bf), torch.zeros(n), torch.zeros(n), torch.zeros(n)
+    flat = torch.zeros(2 * n + 1)
+    hyp = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, step=1)
+    cases = [(dict(p=torch.zeros((3, 200), dtype=bf)[:, :100]), "p must be contiguous"), (dict(p=p.float()), "p must be torch.bfloat16"),
+             (dict(g=flat[1::2][:n]), "g must be contiguous"), (dict(g=g.double()), "g must be torch.float32"), (dict(g=g.to(bf)), "g must be torch.float32"),
+             (dict(g=flat[1:n]), "g must hold 300 elements"), (dict(m=flat[:n + 1]), "m must hold 300"), (dict(m=m.to(bf)), "m must be torch.float32"),
+             (dict(m=flat[0:2 * n:2]), "m must be contiguous"), (dict(v=flat[:n - 1]), "v must hold 300"), (dict(v=v.half()), "v must be torch.float32"),
+             (dict(v=flat[0:2 * n:2]), "v must be contiguous"), (dict(coef=torch.ones(2, dtype=bf)), "coef must be torch.float32"),
+             (dict(coef=torch.ones(4)[::2]), "coef must be contiguous"), (dict(coef=torch.ones(0)), "coef must hold the clip coefficient")]
+    for kw, msg in cases:
+        args = dict(p=p, g=g, m=m, v=v)
+        args.update(kw)
+        with pytest.raises(X2IError, match=msg):
+            ops.adamw_(args["p"], args["g"], args["m"], args["v"], coef=args.get("coef"), **hyp)
+    with pytest.raises(X2IError, match="must live on the GPU"):        # slices of flat storage at an odd offset are what FlatAdamW passes
+        ops.adamw_(p, flat[1:n + 1], flat[n + 1:], m, coef=torch.ones(2), **hyp)
+
+
 def test_product_package_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "x2i_amd")
     for dirpath, _, files in os.walk(pkg):

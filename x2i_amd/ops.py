@@ -165,6 +165,18 @@ def _req(t, dtype, name):
         raise _lib.X2IError("x2i_amd: %s must be %s (got %s)" % (name, dtype, t.dtype))
 
 
+def _req_dense(t, dtype, name, numel=None):
+    """A launch that receives a bare pointer and an element count: `t` must have the dtype, be contiguous and (with `numel`) hold exactly
+    that many elements.  The device is NOT looked at here (the callers do, with _req, once every operand's layout has passed), so that a
+    wrong tensor is refused by name with or without a GPU, and before any launch."""
+    if t.dtype != dtype:
+        raise _lib.X2IError("x2i_amd: %s must be %s (got %s)" % (name, dtype, t.dtype))
+    if not t.is_contiguous():
+        raise _lib.X2IError("x2i_amd: %s must be contiguous (got shape %s with strides %s)" % (name, tuple(t.shape), tuple(t.stride())))
+    if numel is not None and t.numel() != numel:
+        raise _lib.X2IError("x2i_amd: %s must hold %d elements (got %d, shape %s)" % (name, numel, t.numel(), tuple(t.shape)))
+
+
 def pad128(n):
     return (n + 127) // 128 * 128
 
@@ -304,11 +316,21 @@ def ln_modulate(X, Y, B, S, D, S0, shift0, scale0, shift1, scale1, mod_bs, eps=1
 
 
 def ln_affine(X, weight, bias, eps, out=None):
+    """out = LayerNorm(X) * weight + bias over the last dimension of a contiguous bf16 X; `out` (default: a new tensor shaped like X) is
+    contiguous bf16 with X's element count.  The launch gets bare pointers and numel // D rows: anything else is refused here."""
     lib = _lib.load()
-    _req(X, torch.bfloat16, "X")
+    if X.dim() < 1:
+        raise _lib.X2IError("x2i_amd: X must have at least one dimension")
     D = X.shape[-1]
+    _req_dense(X, torch.bfloat16, "X")
+    for t, name, n in ((weight, "weight", D), (bias, "bias", D), (out, "out", X.numel())):
+        if t is not None:            # (a missing weight or bias reaches the library as a null pointer, which it refuses)
+            _req_dense(t, torch.bfloat16, name, n)
+    for t, name in ((X, "X"), (weight, "weight"), (bias, "bias"), (out, "out")):
+        if t is not None:
+            _req(t, torch.bfloat16, name)
     out = torch.empty_like(X) if out is None else out
-    check(lib.x2i_ln_affine_bf16(_p(X), _p(out), X.numel() // D, D, _p(weight), _p(bias), eps, _stream()), "ln_affine")
+    check(lib.x2i_ln_affine_bf16(_p(X), _p(out), X.numel() // max(D, 1), D, _p(weight), _p(bias), eps, _stream()), "ln_affine")
     return out
 
 
@@ -596,9 +618,12 @@ def groupnorm_nhwc_from_moments(x, moments, weight, bias, G, eps, act=ACT_NONE, 
 def softmax_rows_(x, scale=1.0):
     """In-place softmax(scale * x) over the last dimension of a contiguous bf16 tensor."""
     lib = _lib.load()
+    if x.dim() < 1:
+        raise _lib.X2IError("x2i_amd: x must have at least one dimension")
+    _req_dense(x, torch.bfloat16, "x")   # (the launch gets a bare pointer and numel // cols rows: a strided view would be written elsewhere)
     _req(x, torch.bfloat16, "x")
     cols = x.shape[-1]
-    check(lib.x2i_softmax_rows_bf16(_p(x), x.numel() // cols, cols, scale, _stream()), "softmax_rows")
+    check(lib.x2i_softmax_rows_bf16(_p(x), x.numel() // max(cols, 1), cols, scale, _stream()), "softmax_rows")
     return x
 
 
@@ -835,6 +860,18 @@ def clip_coef(sumsq, max_norm):
 
 
 def adamw_(p, g, m, v, *, lr, beta1, beta2, eps, weight_decay, step, coef=None):
+    """One AdamW step in place on a contiguous bf16 parameter p (any shape) with contiguous f32 g, m, v of p's element count (slices of flat
+    storage); coef: None or an f32 device tensor whose first element scales the gradient.  The launch gets bare pointers and p.numel()."""
+    _req_dense(p, torch.bfloat16, "p")
+    for t, name in ((g, "g"), (m, "m"), (v, "v")):
+        _req_dense(t, torch.float32, name, p.numel())
+    if coef is not None:
+        _req_dense(coef, torch.float32, "coef")
+        if coef.numel() < 1:
+            raise _lib.X2IError("x2i_amd: coef must hold the clip coefficient (got an empty tensor)")
+    for t, name, dt in ((p, "p", torch.bfloat16), (g, "g", torch.float32), (m, "m", torch.float32), (v, "v", torch.float32), (coef, "coef", torch.float32)):
+        if t is not None:
+            _req(t, dt, name)
     check(_lib.load().x2i_adamw_bf16(_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
                                      1.0 - beta1 ** step, 1.0 - beta2 ** step, _p(coef), _stream()), "adamw")
     return p

@@ -225,6 +225,6 @@ class Resampler(PackedModule):
             resampler_ops.kv_split(KV[:, :D], KV[:, D:], K, VT, Bc, L, Lpad, H)
             resampler_ops.attention(Q, K, VT, ATT, Bc, H, NQ, L, Lpad, DK ** -0.5, D, NQ * D, plan.n_keys[b0:b0 + Bc])
             ops.gemm(ATT, att.out_proj.weight, att.out_proj.bias, out=Y, M=Bc * NQ)
-            ops.ln_affine(Y[:Bc * NQ], self.ln_post.weight, self.ln_post.bias, eps, out=Z)
+            ops.ln_affine(Y[:Bc * NQ], self.ln_post.weight, self.ln_post.bias, eps, out=Z[:Bc * NQ])
             ops.gemm(Z, self._projT, None, out=out, M=Bc * NQ, c_offset=b0 * NQ * D)
         return out
