@@ -671,12 +671,22 @@ class HipVision(_Patch):
         from .qwen_vision import Qwen2_5VisionTower
         self.visual = find_visual(model)
         self.tower = Qwen2_5VisionTower.from_hf(self.visual)
-        self.calls = 0
+        self.calls = self.in_place = 0
         _Patch.__init__(self, self.visual, "forward", self._forward)
 
     def _forward(self, hidden_states, grid_thw=None, **kw):
+        """Rows that ARE the [:, :1176] view of the tower's padded workspace for this grid (HipQwenImage(tower=...) wrote them there, bf16)
+        are not copied: the tower runs from its workspace, and `in_place` counts it.  Any other input takes the copying forward."""
         self.calls += 1
-        return self.tower(hidden_states, grid_thw=grid_thw)
+        tower = self.tower
+        if (isinstance(grid_thw, torch.Tensor) and hidden_states.dtype == torch.bfloat16 and hidden_states.device == tower.device
+                and hidden_states.dim() == 2 and hidden_states.stride() == (tower.Kp, 1)):
+            plan = tower._plan_for(tuple(tuple(int(v) for v in g) for g in grid_thw.tolist()))     # the one host read, as forward's
+            if hidden_states.data_ptr() == tower.pixel_workspace(plan).data_ptr() and tuple(hidden_states.shape) == (plan.S, tower.patch_dim):
+                self.in_place += 1
+                return tower.forward_from_workspace(plan)
+            return tower(hidden_states, plan=plan)
+        return tower(hidden_states, grid_thw=grid_thw)
 
 
 def find_vpm(model):
@@ -929,6 +939,118 @@ class HipImage(_Patch):
         self.calls = self.fallbacks = 0
         self.last_reason = None
         _Patch.__init__(self, processor, "image_processor", _HipImageProcessor(ip, self.front, self))
+
+
+class _HipQwenImageProcessor:
+    """What HipQwenImage puts in a processor's `image_processor`: every attribute is the original's, and a call in the form the Qwen2.5-VL
+    processor uses (images=, return_tensors="pt" and overrides that change nothing) runs QwenImageFrontEnd"""
+
+    def __init__(self, original, front, owner):
+        self.__dict__.update(_ip=original, _front=front, _owner=owner, _feature=self._feature_type(original))
+
+    def __getattr__(self, name):
+        return getattr(self._ip, name)
+
+    @staticmethod
+    def _feature_type(ip):
+        """The batch-feature type the original returns: the one its class's module (or a base class's) names BatchFeature"""
+        import sys
+        for klass in type(ip).__mro__:
+            t = getattr(sys.modules.get(klass.__module__), "BatchFeature", None)
+            if isinstance(t, type):
+                return t
+        from transformers.feature_extraction_utils import BatchFeature
+        return BatchFeature
+
+    def _route(self, images, args, kw):
+        """The list of RGB PIL images / uint8 arrays of a call that is served, else the reason it is not"""
+        import numpy as np
+        from PIL import Image
+        ip = self._ip
+        if args:
+            return "another form of call"
+        if kw.get("videos") is not None:
+            return "videos= is passed"
+        for k, v in kw.items():
+            if k == "return_tensors":
+                if v is not None and str(getattr(v, "value", v)) != "pt":
+                    return "return_tensors = %r" % (v,)
+            elif k != "videos" and v is not None and not (hasattr(ip, k) and _same_setting(getattr(ip, k), v)):
+                return "a per-call override the front end does not model: %s" % k
+        if isinstance(images, (Image.Image, np.ndarray)):
+            images = [images]
+        if isinstance(images, (list, tuple)) and len(images) and all(isinstance(g, (list, tuple)) for g in images):
+            images = [im for g in images for im in g]
+        if not isinstance(images, (list, tuple)) or not len(images):
+            return "an empty or unknown batch"
+        for im in images:
+            if isinstance(im, Image.Image):
+                if im.mode != "RGB":
+                    return "an input that is not an RGB image of 8 bits per channel"
+                w, h = im.size
+            elif isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.shape[0] and im.shape[1]:
+                h, w = im.shape[:2]
+            else:
+                return "an input that is not an RGB image of 8 bits per channel"
+            why = self._front.served(w, h)                  # smart_resize's aspect ratio, a side over 11760, a scale whose LDS plan does not fit
+            if why is not None:
+                return why
+        return list(images)
+
+    def __call__(self, images=None, *args, **kw):
+        routed = self._route(images, args, kw)
+        if isinstance(routed, str):
+            self._owner.fallbacks += 1
+            self._owner.last_reason = routed
+            return self._ip(images, *args, **kw)
+        self._owner.calls += 1
+        front, tower = self._front, self._owner.tower
+        if tower is None:
+            rows, grid = front(routed)
+        else:                                               # bf16 rows straight into the tower's padded workspace of this grid
+            sizes = [(im.size[1], im.size[0]) if hasattr(im, "size") and not hasattr(im, "shape") else im.shape[:2] for im in routed]
+            key = tuple((1, H // 14, W // 14) for H, W in (front.smart_resize(h, w) for h, w in sizes))
+            plan = tower._plan_for(key)
+            rows, grid = front(routed, out_dtype=torch.bfloat16, out=tower.pixel_workspace(plan), row_stride=tower.Kp)
+        # the library's feature type converts the host grid the way the original's return does; the device rows go in afterwards, in the
+        # original's key order
+        feat = self._feature(data={"image_grid_thw": grid}, tensor_type=kw.get("return_tensors"))
+        feat.data = {"pixel_values": rows, "image_grid_thw": feat.data["image_grid_thw"]}
+        return feat
+
+
+def _same_setting(have, given):
+    """Whether a per-call override equals the processor's own setting (sizes compare as dicts, lists as tuples)"""
+    norm = lambda v: dict(v) if hasattr(v, "keys") else (tuple(v) if isinstance(v, (list, tuple)) else v)     # noqa: E731
+    try:
+        return bool(norm(have) == norm(given))
+    except Exception:
+        return False
+
+
+class HipQwenImage(_Patch):
+    """The image front end in front of the Qwen2.5-VL vision tower on the HIP path (x2i_amd/qwen_image.py: QwenImageFrontEnd with the
+    processor's own mean, std and pixel bounds on `device`).  install() replaces `image_processor` ON THE PROCESSOR INSTANCE by an object that
+    forwards every attribute to the original and serves the call the Qwen2.5-VL processor makes (images=, return_tensors="pt"): the library's
+    batch-feature type with `pixel_values` float32 [S, 1176] ON THE DEVICE and `image_grid_thw` as the original gives it, nothing read back.
+    The WHOLE call goes to the original where an image is not an RGB PIL image or a uint8 [H, W, 3] array, a size is refused (aspect ratio
+    over 200, a side over 11760, a scale the kernel's LDS plan does not fit), per-call overrides are present that differ from the
+    processor's settings (do_resize=False, another size, resample, patch_size, ...), or videos= is passed; `calls` and `fallbacks` count
+    the two routes and `last_reason` says why the last fallback happened.  remove() restores the original.  Also a context manager.
+    tower: a Qwen2_5VisionTower (HipVision(model).tower).  The rows are then written as bf16 straight into the tower's padded workspace of the
+    call's grid and `pixel_values` IS that workspace's [:, :1176] view, which HipVision recognises and does not copy; bf16 is the one
+    rounding the tower's own copy makes, so the tower computes the same bits."""
+
+    def __init__(self, processor, device="cuda", tower=None):
+        from .qwen_image import QwenImageFrontEnd
+        ip = getattr(processor, "image_processor", None)
+        if ip is None or not callable(ip) or not hasattr(ip, "image_mean") or not hasattr(ip, "merge_size"):
+            raise RuntimeError("handoff: no Qwen2.5-VL image processor (processor.image_processor) found in %s" % type(processor).__name__)
+        self.processor, self.tower = processor, tower
+        self.front = QwenImageFrontEnd.from_hf(ip, device)
+        self.calls = self.fallbacks = 0
+        self.last_reason = None
+        _Patch.__init__(self, processor, "image_processor", _HipQwenImageProcessor(ip, self.front, self))
 
 
 def find_extract_feature(model):

@@ -103,7 +103,10 @@ def build_parser(family):
                         "the processor's values, so that the frames reach the device as bytes; a call with a sliced image goes to the "
                         "original unless --max_slice_nums is above 1, which serves the source image and the crops of the slicing grid too "
                         "(include/frontend/tiles/x2i_image_tiles.h).  InternVL2.5: the conditioner's 448 x 448 tile from "
-                        "x2i_amd/internvl_image.py (InternVLImageFrontEnd), bit for bit the host's tile; independent of the other --hip_* flags")
+                        "x2i_amd/internvl_image.py (InternVLImageFrontEnd), bit for bit the host's tile.  Qwen2.5-VL: the patch rows [S, 1176] of "
+                        "Qwen2VLImageProcessor from x2i_amd/qwen_image.py (handoff.HipQwenImage, "
+                        "include/frontend/rows/qwen/x2i_image_rows.h), bit for bit the Pillow backend's values; with --hip_vision they are "
+                        "written as bf16 straight into the tower's padded workspace; independent of the other --hip_* flags")
     p.add_argument("--hip_generate", action="store_true",
                    help="run the MLLM's greedy 128-token generate() with the decoder stack on the HIP path over the prompt and over the "
                         "generated tokens (key/value cache, x2i_amd/qwen.py decode_step); serves --use_answer; Qwen2.5-VL only")

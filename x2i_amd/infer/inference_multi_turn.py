@@ -16,7 +16,7 @@ class MultiTurnConditioner:
     """model / processor: hand in loaded ones (a test's tiny model and stub processor) and `path` is not read."""
 
     def __init__(self, path, device, hip_generate=False, hip_head=False, model=None, processor=None, hip_w8=False, keep_cache=False,
-                 hip_sample=False, hip_sample_seed=0):
+                 hip_sample=False, hip_sample_seed=0, hip_image=False):
         if hip_w8 and not hip_generate:         # (before the checkpoint is read)
             raise ValueError("--hip_w8 runs the decode steps of --hip_generate's loop on e4m3 weights: not without --hip_generate")
         if hip_sample and not (hip_generate and hip_head):
@@ -38,6 +38,12 @@ class MultiTurnConditioner:
             if not hip_sample:
                 HipGenerate.refuse_sampling(self.model.generation_config)
             self.generate = HipGenerate(self.model, hip_head=hip_head, w8=hip_w8, keep_cache=keep_cache, sample=hip_sample, seed=hip_sample_seed)
+        # hip_image: the vision tower's input from the HIP path (handoff.HipQwenImage) in place of the processor's Qwen2VLImageProcessor;
+        # the 256 x 256 resize of a turn's images stays on the host in front of it
+        self.image = None
+        if hip_image:
+            from ..handoff import HipQwenImage
+            self.image = HipQwenImage(self.processor, device).install()
 
     @torch.no_grad()
     def __call__(self, images=None, text_prompt=None, **_):
@@ -105,7 +111,8 @@ def main(argv=None):
     if args.synthetic:
         return synthetic_turns(args, kind, device)
     cond = MultiTurnConditioner(args.qwen_path, device, hip_generate=args.hip_generate, hip_head=args.hip_head, hip_w8=args.hip_w8,
-                                keep_cache=args.hip_keep_cache, hip_sample=args.hip_sample, hip_sample_seed=sample_seed(args))
+                                keep_cache=args.hip_keep_cache, hip_sample=args.hip_sample, hip_sample_seed=sample_seed(args),
+                                hip_image=args.hip_image)
     h = Harness(args, kind, lambda **kw: cond(**kw)[0], device)
     turn = 0
     while True:

@@ -15,14 +15,16 @@ class QwenVLConditioner:
     1 fps / 128*128 pixels, generate(max_new_tokens=128, output_hidden_states=True) -- infer/inference_qwenvl.py:136-180."""
 
     def __init__(self, path, device, use_answer=False, prefill_only=True, hip_decoder=False, hip_vision=False, hip_generate=False, hip_head=False,
-                 hip_w8=False, hip_sample=False, hip_sample_seed=0):
+                 hip_w8=False, hip_sample=False, hip_sample_seed=0, hip_image=False, model=None, processor=None):
         if hip_w8 and not hip_generate:         # (before the checkpoint is read)
             raise ValueError("--hip_w8 runs the decode steps of --hip_generate's loop on e4m3 weights: not without --hip_generate")
         if hip_sample and not (hip_generate and hip_head):
             raise ValueError("--hip_sample draws the tokens inside --hip_generate --hip_head's captured step: not without both")
-        from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
-        self.model = Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
-        self.processor = AutoProcessor.from_pretrained(path)
+        if model is None or processor is None:  # model / processor: hand in loaded ones (a test's stand-ins) and `path` is not read
+            from transformers import AutoProcessor, Qwen2_5_VLForConditionalGeneration
+            model = model if model is not None else Qwen2_5_VLForConditionalGeneration.from_pretrained(path, torch_dtype=torch.bfloat16).eval().to(device)
+            processor = processor if processor is not None else AutoProcessor.from_pretrained(path)
+        self.model, self.processor = model, processor
         self.device, self.use_answer = device, use_answer
         # the prompt-pass states are all the reference keeps unless --use_answer: take them from ONE forward, written by
         # hooks straight into the [B,C,S,H] buffer (x2i_amd/handoff.py), instead of a 128-token generate() + torch.cat
@@ -52,6 +54,15 @@ class QwenVLConditioner:
         if hip_vision:
             from ..handoff import HipVision
             self.vision = HipVision(self.model).install()
+
+        # hip_image: the tower's input on the HIP path (x2i_amd/qwen_image.py) in place of the processor's Qwen2VLImageProcessor: smart_resize,
+        # Pillow's BICUBIC resize, the normalisation and the patch rows [S, 1176] in one launch per run of equally sized images, bit for bit
+        # the processor's values.  The reference's own 128 x 128 resize stays on the host in front of it (49 KB to upload per image).  With
+        # hip_vision the rows are written as bf16 straight into the tower's padded workspace, which HipVision then does not copy.
+        self.image = None
+        if hip_image:
+            from ..handoff import HipQwenImage
+            self.image = HipQwenImage(self.processor, device, tower=self.vision.tower if self.vision is not None else None).install()
 
     @torch.no_grad()
     def __call__(self, videos=None, images=None, audios=None, text_prompt=None):
@@ -116,7 +127,7 @@ def main(argv=None):
                                                                                             hip_decoder=args.hip_decoder, hip_vision=args.hip_vision,
                                                                                             hip_generate=args.hip_generate, hip_head=args.hip_head,
                                                                                             hip_w8=args.hip_w8, hip_sample=args.hip_sample,
-                                                                                            hip_sample_seed=sample_seed(args))
+                                                                                            hip_sample_seed=sample_seed(args), hip_image=args.hip_image)
     Harness(args, kind, cond, device).run_tasks(tasks(args))
 
 

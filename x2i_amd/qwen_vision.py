@@ -236,13 +236,10 @@ class Qwen2_5VisionTower(PackedModule):
         last_hidden_state bf16 [S, hidden_size] in WINDOW order, as the library has it.  With a plan (self.plan(grid_thw)) the call only
         enqueues: no host read, no synchronisation, two allocations (the two results).  Without one, grid_thw is read once and the plan of
         the last grid is kept."""
-        from transformers.modeling_outputs import BaseModelOutputWithPooling
         if plan is None:
             if grid_thw is None:
                 raise ValueError("Qwen2_5VisionTower: pass grid_thw or a plan")
             plan = self._plan_for(tuple(tuple(int(v) for v in g) for g in grid_thw.tolist()))     # the one host read
-        c = self.config
-        D, L, unit = c.hidden_size, len(self.blocks), self.spatial_merge_unit
         S = plan.S
         if plan.device != self.device or not hasattr(plan, "ws"):
             raise ValueError("x2i_amd Qwen2_5VisionTower: the plan was made on %s; the module is on %s and runs on the GPU only" % (plan.device, self.device))
@@ -250,9 +247,27 @@ class Qwen2_5VisionTower(PackedModule):
             raise ValueError("x2i_amd Qwen2_5VisionTower: pixel rows must be [S, C*T*P*P] = [%d, %d] for grid %r (got %s)" % (S, self.patch_dim, plan.grid, tuple(pixel_rows.shape)))
         if pixel_rows.device != self.device:
             raise ops._lib.X2IError("x2i_amd: pixel rows must live on the model's device (got %s)" % pixel_rows.device)
+        plan.ws["PX"][:, :self.patch_dim].copy_(pixel_rows)
+        return self.forward_from_workspace(plan)
+
+    def pixel_workspace(self, plan):
+        """The tower's padded pixel rows of a plan: bf16 [S, Kp = 1216], of which forward_from_workspace reads everything.  Columns
+        1176 .. 1215 were zeroed once, when the plan was made, and must stay zero: a front end writes [:, :1176] only
+        (x2i_amd/qwen_image.py: out=this, row_stride=1216, out_dtype=bfloat16)."""
+        if plan.device != self.device or not hasattr(plan, "ws"):
+            raise ValueError("x2i_amd Qwen2_5VisionTower: the plan was made on %s; the module is on %s and runs on the GPU only" % (plan.device, self.device))
+        return plan.ws["PX"]
+
+    @torch.no_grad()
+    def forward_from_workspace(self, plan):
+        """Everything of forward after its copy of the pixel rows: the rows are those that stand in pixel_workspace(plan), already bf16.
+        Only enqueues, like forward with a plan."""
+        from transformers.modeling_outputs import BaseModelOutputWithPooling
+        c = self.config
+        D, L, unit = c.hidden_size, len(self.blocks), self.spatial_merge_unit
+        S = plan.S
         ws = plan.ws
         PX, X0, XA, NRM, M1, M2 = (ws[k] for k in ("PX", "X0", "XA", "NRM", "M1", "M2"))
-        PX[:, :self.patch_dim].copy_(pixel_rows)
         ops.gemm(PX, self._fused["pe"], out=X0, M=S)
         torch.index_select(X0, 0, plan.perm, out=XA)      # into window order: a torch gather
         last = torch.empty((S, D), device=self.device, dtype=torch.bfloat16)
