@@ -1,16 +1,13 @@
-// The two passes of the image front ends (Pillow's 8-bit BICUBIC resize, the normalisation as a table lookup) as one kernel, shared by
-// csrc/image.hip (x2i_image_frontend: the resized image is the output) and csrc/image_tiles.hip (x2i_image_tiles: the resized image is cut
-// into a grid of crops).  The arithmetic stands in include/frontend/x2i_image.h; what differs between the two entry points is the workgroup
-// map and the store, and a whole image is the grid of one crop.  The passes themselves are device functions, which csrc/image_rows.hip
-// (x2i_image_rows: Qwen2.5-VL's patch rows) calls from a kernel of its own with another store order.  Included by those three files only.
+// What the three image front ends share.  The two passes (Pillow's 8-bit BICUBIC resize, the normalisation as a table lookup) are device
+// functions here; image_passes_kernel, which stores a resized image as a grid of crops, lives in csrc/image.hip alone and is reached
+// through image_passes_launch by csrc/image.hip (x2i_image_frontend: a whole image is the grid of one crop) and csrc/image_tiles.hip
+// (x2i_image_tiles); csrc/image_rows.hip (x2i_image_rows: Qwen2.5-VL's patch rows) calls the passes from a kernel of its own with another
+// store order.  The arithmetic stands in include/frontend/x2i_image.h.  The checks the three entry points make alike, and the fill of
+// ImageArgs, are host functions at the end.  Included by those three files only.
 #pragma once
 #include "x2i_common.h"
 
 #include <math.h>
-
-namespace {
-
-constexpr int PATCH = 14, PREC = 22, MAX_PATCHES = 70, LDS_BYTES = 65536, MAX_IN = 65535;
 
 struct ImageArgs {
   const uint8_t* frames;
@@ -28,6 +25,13 @@ struct ImageArgs {
   int gx;               // crops per row of crops
   int tpc;              // column tiles per crop: the last one of a crop is partial at the crop's edge
 };
+
+// csrc/image.hip: one launch of image_passes_kernel for n frames, gx * gy crops each.  a: everything but tpc set.
+void image_passes_launch(ImageArgs a, int n, int gy, bool planar, bool bf16, hipStream_t stream);
+
+namespace {
+
+constexpr int PATCH = 14, PREC = 22, MAX_PATCHES = 70, LDS_BYTES = 65536, MAX_IN = 65535;
 
 __device__ __forceinline__ int clip8(unsigned acc) {
   const int v = ((int)acc) >> PREC;
@@ -93,38 +97,6 @@ __device__ __forceinline__ int vertical_tap_value(const ImageArgs& a, const uint
   return clip8(s);
 }
 
-// grid (crops per row * column tiles per crop, patch rows of the resized image, frames), 256 threads.  Phase 1: the horizontal pass (or a
-// copy) of input rows row0 .. row0 + nrows for the tile's columns, uint8 [nrows][ld] in LDS (horizontal_pass_to_lds).  Phase 2: the
-// vertical pass (or a copy) from LDS, one thread per (channel, row, column) with the column fastest, so that a wave stores consecutive
-// elements of one output row.  The tables are those of the whole resized image: a crop's edge columns and rows take their taps from input
-// pixels on either side of the edge.  PLANAR: a crop is stored as [3][crop_h][crop_w], else as the strip [3][14][14 L].
-template <bool BF16, bool PLANAR>
-__global__ __launch_bounds__(256) void image_passes_kernel(const ImageArgs a) {
-  extern __shared__ uint8_t img[];
-  const int tid = threadIdx.x, ph = blockIdx.y;
-  const long long f = blockIdx.z;
-  const int cj = blockIdx.x / a.tpc;                         // the crop's column in the grid
-  const int cc = (blockIdx.x - cj * a.tpc) * a.tile * PATCH; // the tile's first column within the crop
-  const int c0 = cj * a.crop_w + cc;                         // ... and within the resized image
-  const int cw = min(a.tile * PATCH, a.crop_w - cc);
-  int row0, nrows;
-  patch_row_span(a, ph, &row0, &nrows);
-  horizontal_pass_to_lds(a, a.frames + f * a.frame_pitch + (long long)row0 * a.row_pitch, nrows, c0, cw, img);
-  __syncthreads();
-  const int pr = a.crop_h / PATCH, ci = ph / pr, pc = ph - ci * pr;   // the crop's row in the grid, the patch row within the crop
-  const long long base = f * a.ofs + (long long)(ci * a.gx + cj) * a.ots;
-  for (int i = tid; i < 3 * PATCH * cw; i += 256) {
-    const int cr = i / cw, col = i - cr * cw, c = cr / PATCH, r = cr - c * PATCH;
-    const float val = a.lut[c * 256 + vertical_tap_value(a, img, ph, r, col, c, row0, nrows)];
-    const long long o = PLANAR ? base + ((long long)c * a.crop_h + PATCH * pc + r) * a.ors + cc + col
-                               : base + (long long)(c * PATCH + r) * a.ors + (long long)pc * a.crop_w + cc + col;
-    if (BF16)
-      ((bf16_t*)a.out)[o] = f32_to_bf16(val);
-    else
-      ((float*)a.out)[o] = val;
-  }
-}
-
 // Pillow's window of output xx: (xmin, xmax), and the axis's ksize
 struct Axis {
   double scale, support;
@@ -164,23 +136,75 @@ inline bool image_lds_plan(int in_h, int out_h, int vk, int* rows_, int* tile_, 
   return (long long)rows * *ld_ <= LDS_BYTES;
 }
 
-// a: everything but tpc set.  One launch for n frames, gx * gy crops each.
-inline void image_passes_launch(ImageArgs a, int n, int gy, bool planar, bool bf16, hipStream_t stream) {
-  const int cp = a.crop_w / PATCH;
-  a.tpc = (cp + a.tile - 1) / a.tile;
-  const dim3 grid(a.gx * a.tpc, gy * (a.crop_h / PATCH), n);
-  const size_t lds = (size_t)a.rows * a.ld;
-  if (planar) {
-    if (bf16)
-      hipLaunchKernelGGL((image_passes_kernel<true, true>), grid, dim3(256), lds, stream, a);
-    else
-      hipLaunchKernelGGL((image_passes_kernel<false, true>), grid, dim3(256), lds, stream, a);
-  } else {
-    if (bf16)
-      hipLaunchKernelGGL((image_passes_kernel<true, false>), grid, dim3(256), lds, stream, a);
-    else
-      hipLaunchKernelGGL((image_passes_kernel<false, false>), grid, dim3(256), lds, stream, a);
-  }
+// The arguments the three entry points take alike, under the names of include/frontend/x2i_image.h
+struct ImageCall {
+  const void* frames;
+  long long frame_pitch, row_pitch;
+  int in_w, in_h, out_w, out_h;
+  const void *hbound, *hcoef;
+  int hk;
+  const void *vbound, *vcoef;
+  int vk;
+  const void* lut;
+  void* out;
+  int out_bf16;
+};
+
+// The checks of an entry point `what`, in the order every entry point makes them: image_check_pointers, its own count,
+// image_check_input_size, its own output sizes, image_check_tables, its own output strides, image_plan_args.  X2I_OK or the error recorded.
+inline int image_check_pointers(const char* what, const ImageCall& c) {
+  if (!c.frames || !c.lut || !c.out) return x2i_set_error(X2I_ERR_ARG, "%s: null pointer (frames, lut or out)", what);
+  return X2I_OK;
+}
+
+inline int image_check_input_size(const char* what, const ImageCall& c) {
+  if (c.in_w < 1 || c.in_w > MAX_IN || c.in_h < 1 || c.in_h > MAX_IN)
+    return x2i_set_error(X2I_ERR_SHAPE, "%s: in_w=%d and in_h=%d must be in 1..65535", what, c.in_w, c.in_h);
+  return X2I_OK;
+}
+
+// The pitches, hk / vk against the axes' ksize, the tables exactly where an axis resizes
+inline int image_check_tables(const char* what, const ImageCall& c) {
+  if (c.row_pitch < 3LL * c.in_w || c.frame_pitch < (long long)(c.in_h - 1) * c.row_pitch + 3LL * c.in_w)
+    return x2i_set_error(X2I_ERR_SHAPE, "%s: row_pitch=%lld must be at least 3 * in_w and frame_pitch=%lld at least (in_h - 1) * row_pitch + 3 * in_w",
+                         what, c.row_pitch, c.frame_pitch);
+  const int want_hk = c.in_w != c.out_w ? Axis(c.in_w, c.out_w).ksize : 0, want_vk = c.in_h != c.out_h ? Axis(c.in_h, c.out_h).ksize : 0;
+  if (c.hk != want_hk)
+    return x2i_set_error(X2I_ERR_SHAPE, "%s: hk=%d, the tables of in_w=%d -> out_w=%d have ksize %d", what, c.hk, c.in_w, c.out_w, want_hk);
+  if (c.vk != want_vk)
+    return x2i_set_error(X2I_ERR_SHAPE, "%s: vk=%d, the tables of in_h=%d -> out_h=%d have ksize %d", what, c.vk, c.in_h, c.out_h, want_vk);
+  if ((c.hk != 0) != (c.hbound != nullptr) || (c.hk != 0) != (c.hcoef != nullptr))
+    return x2i_set_error(X2I_ERR_ARG, "%s: hbound and hcoef must be given exactly where in_w != out_w", what);
+  if ((c.vk != 0) != (c.vbound != nullptr) || (c.vk != 0) != (c.vcoef != nullptr))
+    return x2i_set_error(X2I_ERR_ARG, "%s: vbound and vcoef must be given exactly where in_h != out_h", what);
+  return X2I_OK;
+}
+
+// The LDS plan (checked before the alignment, so that a refused scale is reported as such whatever the pointers are), the alignment, and
+// *a filled for a whole image stored as the one crop of a 1 x 1 grid: all but the output strides ofs and ors, which are the entry point's
+// own, and tpc, which belongs to the launch
+inline int image_plan_args(const char* what, const ImageCall& c, ImageArgs* a) {
+  int rows, tile, ld;
+  if (!image_lds_plan(c.in_h, c.out_h, c.vk, &rows, &tile, &ld))
+    return x2i_set_error(X2I_ERR_SHAPE, "%s: the LDS plan does not fit: in_h=%d -> out_h=%d needs %d rows of %d bytes for one patch of columns, at most %d bytes",
+                         what, c.in_h, c.out_h, rows, ld, LDS_BYTES);
+  const uintptr_t tabs = (uintptr_t)c.hbound | (uintptr_t)c.hcoef | (uintptr_t)c.vbound | (uintptr_t)c.vcoef | (uintptr_t)c.lut;
+  if ((tabs & 3) || (((uintptr_t)c.out) & (c.out_bf16 ? 1 : 3)))
+    return x2i_set_error(X2I_ERR_ALIGN, "%s: the tables and lut must be 4-byte aligned, out aligned to its element size", what);
+  a->frames = (const uint8_t*)c.frames;
+  a->frame_pitch = c.frame_pitch;
+  a->row_pitch = c.row_pitch;
+  a->hb = (const int*)c.hbound;
+  a->hc = (const int*)c.hcoef;
+  a->vb = (const int*)c.vbound;
+  a->vc = (const int*)c.vcoef;
+  a->lut = (const float*)c.lut;
+  a->out = c.out;
+  a->ofs = 0, a->ots = 0;
+  a->in_w = c.in_w, a->in_h = c.in_h, a->out_w = c.out_w, a->out_h = c.out_h, a->hk = c.hk, a->vk = c.vk;
+  a->tile = tile, a->rows = rows, a->ld = ld;
+  a->crop_w = c.out_w, a->crop_h = c.out_h, a->gx = 1;
+  return X2I_OK;
 }
 
 }  // namespace

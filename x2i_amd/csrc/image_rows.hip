@@ -64,60 +64,31 @@ int x2i_image_rows(const void* frames, int64_t frame_pitch, int64_t row_pitch, i
                    int32_t vk, const void* lut, void* out, int64_t out_item_stride, int64_t out_row_stride, int32_t out_bf16,
                    x2i_stream_t stream) {
   const char* what = "image_rows";
-  if (!frames || !lut || !out) return x2i_set_error(X2I_ERR_ARG, "%s: null pointer (frames, lut or out)", what);
+  const ImageCall c = {frames, frame_pitch, row_pitch, in_w, in_h, out_w, out_h, hbound, hcoef, hk, vbound, vcoef, vk, lut, out, out_bf16};
+  if (int rc = image_check_pointers(what, c)) return rc;
   if (n_items < 1 || t_in < 1 || (long long)n_items * t_in > 65535)
     return x2i_set_error(X2I_ERR_SHAPE, "%s: n_items=%d and t_in=%d must be at least 1 and n_items * t_in in 1..65535", what, n_items, t_in);
-  if (in_w < 1 || in_w > MAX_IN || in_h < 1 || in_h > MAX_IN)
-    return x2i_set_error(X2I_ERR_SHAPE, "%s: in_w=%d and in_h=%d must be in 1..65535", what, in_w, in_h);
+  if (int rc = image_check_input_size(what, c)) return rc;
   if (out_w < UNIT || out_w % UNIT || out_w > MAX_OUT)
     return x2i_set_error(X2I_ERR_SHAPE, "%s: out_w=%d must be a multiple of 28 in 28..11760", what, out_w);
   if (out_h < UNIT || out_h % UNIT || out_h > MAX_OUT)
     return x2i_set_error(X2I_ERR_SHAPE, "%s: out_h=%d must be a multiple of 28 in 28..11760", what, out_h);
-  if (row_pitch < 3LL * in_w || frame_pitch < (long long)(in_h - 1) * row_pitch + 3LL * in_w)
-    return x2i_set_error(X2I_ERR_SHAPE, "%s: row_pitch=%lld must be at least 3 * in_w and frame_pitch=%lld at least (in_h - 1) * row_pitch + 3 * in_w",
-                         what, (long long)row_pitch, (long long)frame_pitch);
-  const int want_hk = in_w != out_w ? Axis(in_w, out_w).ksize : 0, want_vk = in_h != out_h ? Axis(in_h, out_h).ksize : 0;
-  if (hk != want_hk) return x2i_set_error(X2I_ERR_SHAPE, "%s: hk=%d, the tables of in_w=%d -> out_w=%d have ksize %d", what, hk, in_w, out_w, want_hk);
-  if (vk != want_vk) return x2i_set_error(X2I_ERR_SHAPE, "%s: vk=%d, the tables of in_h=%d -> out_h=%d have ksize %d", what, vk, in_h, out_h, want_vk);
-  if ((hk != 0) != (hbound != nullptr) || (hk != 0) != (hcoef != nullptr))
-    return x2i_set_error(X2I_ERR_ARG, "%s: hbound and hcoef must be given exactly where in_w != out_w", what);
-  if ((vk != 0) != (vbound != nullptr) || (vk != 0) != (vcoef != nullptr))
-    return x2i_set_error(X2I_ERR_ARG, "%s: vbound and vcoef must be given exactly where in_h != out_h", what);
+  if (int rc = image_check_tables(what, c)) return rc;
   // rows of an item: at most 32768 * 840 * 840; the product with out_row_stride is never formed (it could pass 2^63)
   const long long item_rows = (long long)((t_in + 1) / 2) * (out_h / PATCH) * (out_w / PATCH);
   if (out_row_stride < ROW || out_item_stride / out_row_stride < item_rows)
     return x2i_set_error(X2I_ERR_SHAPE, "%s: out_row_stride=%lld must be at least 1176 and out_item_stride=%lld at least grid_t * gh * gw = %lld times "
                          "out_row_stride", what, (long long)out_row_stride, (long long)out_item_stride, item_rows);
-  // the LDS plan (checked before the alignment, so that a refused scale is reported as such whatever the pointers are)
-  int rows, tile, ld;
-  if (!image_lds_plan(in_h, out_h, vk, &rows, &tile, &ld))
-    return x2i_set_error(X2I_ERR_SHAPE, "%s: the LDS plan does not fit: in_h=%d -> out_h=%d needs %d rows of %d bytes for one patch of columns, at most %d bytes",
-                         what, in_h, out_h, rows, ld, LDS_BYTES);
-  const uintptr_t tabs = (uintptr_t)hbound | (uintptr_t)hcoef | (uintptr_t)vbound | (uintptr_t)vcoef | (uintptr_t)lut;
-  if ((tabs & 3) || (((uintptr_t)out) & (out_bf16 ? 1 : 3)))
-    return x2i_set_error(X2I_ERR_ALIGN, "%s: the tables and lut must be 4-byte aligned, out aligned to its element size", what);
   RowsArgs ra;
   ImageArgs& a = ra.im;
-  a.frames = (const uint8_t*)frames;
-  a.frame_pitch = frame_pitch;
-  a.row_pitch = row_pitch;
-  a.hb = (const int*)hbound;
-  a.hc = (const int*)hcoef;
-  a.vb = (const int*)vbound;
-  a.vc = (const int*)vcoef;
-  a.lut = (const float*)lut;
-  a.out = out;
-  a.ofs = 0, a.ots = 0;
+  if (int rc = image_plan_args(what, c, &a)) return rc;
   a.ors = out_row_stride;
-  a.in_w = in_w, a.in_h = in_h, a.out_w = out_w, a.out_h = out_h, a.hk = hk, a.vk = vk;
-  a.tile = tile, a.rows = rows, a.ld = ld;
-  a.crop_w = out_w, a.crop_h = out_h, a.gx = 1;
   const int gw = out_w / PATCH;
-  a.tpc = (gw + tile - 1) / tile;
+  a.tpc = (gw + a.tile - 1) / a.tile;
   ra.ois = out_item_stride;
   ra.t_in = t_in;
   const dim3 grid(a.tpc, out_h / PATCH, n_items * t_in);
-  const size_t lds = (size_t)rows * ld;
+  const size_t lds = (size_t)a.rows * a.ld;
   if (out_bf16)
     hipLaunchKernelGGL((image_rows_kernel<true>), grid, dim3(256), lds, (hipStream_t)stream, ra);
   else

@@ -1,7 +1,8 @@
 // The image front end for a resized image cut into a uniform grid of crops (include/frontend/tiles/x2i_image_tiles.h): the slices of
-// MiniCPMVImageProcessor.preprocess (strip layout) and the 448 x 448 tiles of InternVL2.5's load_image (planar layout).  The two passes are
-// those of csrc/image.hip (image_passes.h); new here are the workgroup map per crop, the per-crop output base and the planar store.  One
-// launch for n frames of one input size, one resize target and one grid; the launcher enqueues on the caller's stream and returns.
+// MiniCPMVImageProcessor.preprocess (strip layout) and the 448 x 448 tiles of InternVL2.5's load_image (planar layout).  The kernel is
+// csrc/image.hip's image_passes_kernel, reached through image_passes_launch (image_passes.h): its workgroup map per crop, per-crop output
+// base and planar store serve this entry point, which keeps its own size, layout and stride rules.  One launch for n frames of one input
+// size, one resize target and one grid; the launcher enqueues on the caller's stream and returns.
 #include "image_passes.h"
 #include "../../include/frontend/tiles/x2i_image_tiles.h"
 
@@ -16,10 +17,10 @@ int x2i_image_tiles(const void* frames, int64_t frame_pitch, int64_t row_pitch, 
                     const void* vcoef, int32_t vk, const void* lut, void* out, int64_t out_frame_stride, int64_t out_tile_stride,
                     int64_t out_row_stride, int32_t layout, int32_t out_bf16, x2i_stream_t stream) {
   const char* what = "image_tiles";
-  if (!frames || !lut || !out) return x2i_set_error(X2I_ERR_ARG, "%s: null pointer (frames, lut or out)", what);
+  const ImageCall c = {frames, frame_pitch, row_pitch, in_w, in_h, out_w, out_h, hbound, hcoef, hk, vbound, vcoef, vk, lut, out, out_bf16};
+  if (int rc = image_check_pointers(what, c)) return rc;
   if (n < 1 || n > 65535) return x2i_set_error(X2I_ERR_SHAPE, "%s: n=%d must be in 1..65535", what, n);
-  if (in_w < 1 || in_w > MAX_IN || in_h < 1 || in_h > MAX_IN)
-    return x2i_set_error(X2I_ERR_SHAPE, "%s: in_w=%d and in_h=%d must be in 1..65535", what, in_w, in_h);
+  if (int rc = image_check_input_size(what, c)) return rc;
   if (tile_w < PATCH || tile_w % PATCH || tile_w > PATCH * MAX_PATCHES)
     return x2i_set_error(X2I_ERR_SHAPE, "%s: tile_w=%d must be a multiple of 14 in 14..980", what, tile_w);
   if (tile_h < PATCH || tile_h % PATCH || tile_h > PATCH * MAX_PATCHES)
@@ -30,44 +31,15 @@ int x2i_image_tiles(const void* frames, int64_t frame_pitch, int64_t row_pitch, 
     return x2i_set_error(X2I_ERR_SHAPE, "%s: out_h=%d must be 1..12 times tile_h=%d", what, out_h, tile_h);
   const int gx = out_w / tile_w, gy = out_h / tile_h;
   if (layout != 0 && layout != 1) return x2i_set_error(X2I_ERR_ARG, "%s: layout=%d must be 0 (strip) or 1 (planar)", what, layout);
-  if (row_pitch < 3LL * in_w || frame_pitch < (long long)(in_h - 1) * row_pitch + 3LL * in_w)
-    return x2i_set_error(X2I_ERR_SHAPE, "%s: row_pitch=%lld must be at least 3 * in_w and frame_pitch=%lld at least (in_h - 1) * row_pitch + 3 * in_w",
-                         what, (long long)row_pitch, (long long)frame_pitch);
-  const int want_hk = in_w != out_w ? Axis(in_w, out_w).ksize : 0, want_vk = in_h != out_h ? Axis(in_h, out_h).ksize : 0;
-  if (hk != want_hk) return x2i_set_error(X2I_ERR_SHAPE, "%s: hk=%d, the tables of in_w=%d -> out_w=%d have ksize %d", what, hk, in_w, out_w, want_hk);
-  if (vk != want_vk) return x2i_set_error(X2I_ERR_SHAPE, "%s: vk=%d, the tables of in_h=%d -> out_h=%d have ksize %d", what, vk, in_h, out_h, want_vk);
-  if ((hk != 0) != (hbound != nullptr) || (hk != 0) != (hcoef != nullptr))
-    return x2i_set_error(X2I_ERR_ARG, "%s: hbound and hcoef must be given exactly where in_w != out_w", what);
-  if ((vk != 0) != (vbound != nullptr) || (vk != 0) != (vcoef != nullptr))
-    return x2i_set_error(X2I_ERR_ARG, "%s: vbound and vcoef must be given exactly where in_h != out_h", what);
+  if (int rc = image_check_tables(what, c)) return rc;
   const long long row_min = layout ? tile_w : (long long)(tile_h / PATCH) * tile_w, rows_per_tile = layout ? 3LL * tile_h : 3LL * PATCH;
   if (out_row_stride < row_min || out_tile_stride < rows_per_tile * out_row_stride || out_frame_stride < (long long)gx * gy * out_tile_stride)
     return x2i_set_error(X2I_ERR_SHAPE, "%s: layout %d needs out_row_stride=%lld at least %lld, out_tile_stride=%lld at least %lld * out_row_stride and "
                          "out_frame_stride=%lld at least %d * out_tile_stride", what, layout, (long long)out_row_stride, row_min,
                          (long long)out_tile_stride, rows_per_tile, (long long)out_frame_stride, gx * gy);
-  // the LDS plan of the whole resize (checked before the alignment, so that a refused scale is reported as such whatever the pointers are)
-  int rows, tile, ld;
-  if (!image_lds_plan(in_h, out_h, vk, &rows, &tile, &ld))
-    return x2i_set_error(X2I_ERR_SHAPE, "%s: the LDS plan does not fit: in_h=%d -> out_h=%d needs %d rows of %d bytes for one patch of columns, at most %d bytes",
-                         what, in_h, out_h, rows, ld, LDS_BYTES);
-  const uintptr_t tabs = (uintptr_t)hbound | (uintptr_t)hcoef | (uintptr_t)vbound | (uintptr_t)vcoef | (uintptr_t)lut;
-  if ((tabs & 3) || (((uintptr_t)out) & (out_bf16 ? 1 : 3)))
-    return x2i_set_error(X2I_ERR_ALIGN, "%s: the tables and lut must be 4-byte aligned, out aligned to its element size", what);
-  ImageArgs a;
-  a.frames = (const uint8_t*)frames;
-  a.frame_pitch = frame_pitch;
-  a.row_pitch = row_pitch;
-  a.hb = (const int*)hbound;
-  a.hc = (const int*)hcoef;
-  a.vb = (const int*)vbound;
-  a.vc = (const int*)vcoef;
-  a.lut = (const float*)lut;
-  a.out = out;
-  a.ofs = out_frame_stride;
-  a.ors = out_row_stride;
-  a.ots = out_tile_stride;
-  a.in_w = in_w, a.in_h = in_h, a.out_w = out_w, a.out_h = out_h, a.hk = hk, a.vk = vk;
-  a.tile = tile, a.rows = rows, a.ld = ld;
+  ImageArgs a;      // the LDS plan is that of the whole resize
+  if (int rc = image_plan_args(what, c, &a)) return rc;
+  a.ofs = out_frame_stride, a.ors = out_row_stride, a.ots = out_tile_stride;
   a.crop_w = tile_w, a.crop_h = tile_h, a.gx = gx;
   image_passes_launch(a, n, gy, layout == 1, out_bf16 != 0, (hipStream_t)stream);
   return x2i_check_launch(what);

@@ -72,19 +72,113 @@ class ImagePlan:
     """The buffers of calls on at most `nbytes` bytes of frames (ImageFrontEnd.plan)"""
 
 
-class ImageFrontEnd:
+class StagedFrontEnd:
+    """What the three image front ends (ImageFrontEnd, qwen_image.QwenImageFrontEnd, internvl_image.InternVLImageFrontEnd) share: the
+    device, the check of mean and std, the coefficient tables, the staging plan and the staging sequence of a call.  A front end adds its
+    normalisation table `lut`, its size rules, its grouping rule and its launches.  Refusals name the class that raised them."""
+
+    _noun = "frames"                                            # what the "plan holds" refusal calls the input of a call
+
+    def __init__(self, mean, std, device):
+        mean, std = [float(v) for v in mean], [float(v) for v in std]
+        if len(mean) != 3 or len(std) != 3 or not all(std):
+            raise ValueError("x2i_amd %s: mean and std must hold three values, std none of them zero (got %r, %r)" % (type(self).__name__, mean, std))
+        self.mean, self.std, self.device = mean, std, torch.device(device)
+        self._tables = {}
+        self._plan = None
+
+    def tables(self, n_in, n_out):
+        """(bound, coef) of one axis on the device, made once per (n_in, n_out); (None, None) where the axis does not resize"""
+        if n_in == n_out:
+            return None, None
+        t = self._tables.get((n_in, n_out))
+        if t is None:
+            t = self._tables[(n_in, n_out)] = tuple(torch.from_numpy(a).to(self.device) for a in axis_tables(n_in, n_out))
+        return t
+
+    def plan(self, nbytes):
+        """The pinned staging buffer and the device frame buffer of calls on at most nbytes bytes of frames"""
+        nbytes = int(nbytes)
+        if nbytes < 1:
+            raise ValueError("x2i_amd %s: a plan needs at least one byte of frames (got %d)" % (type(self).__name__, nbytes))
+        p = ImagePlan()
+        cuda = self.device.type == "cuda"
+        p.nbytes, p.device = nbytes, self.device
+        p.stage = torch.empty(nbytes, dtype=torch.uint8, pin_memory=cuda)
+        p.dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        p.sent = torch.cuda.Event() if cuda else None
+        p.busy = False
+        return p
+
+    @staticmethod
+    def _as_arrays(frames):
+        """A list of uint8 [H, W, 3] arrays of PIL RGB images, arrays, or one [n, H, W, 3] array.  (A static function, whose refusals name
+        ImageFrontEnd for all three front ends.)"""
+        if isinstance(frames, np.ndarray) and frames.ndim == 4:
+            frames = list(frames)
+        out = []
+        for f in frames:
+            if not isinstance(f, np.ndarray):
+                if getattr(f, "mode", None) != "RGB":
+                    raise ValueError("x2i_amd ImageFrontEnd: a frame must be a PIL image of mode RGB or a uint8 [H, W, 3] array (got %r)"
+                                     % (getattr(f, "mode", type(f).__name__),))
+                f = np.asarray(f)
+            if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or not f.shape[0] or not f.shape[1]:
+                raise ValueError("x2i_amd ImageFrontEnd: a frame must be a uint8 [H, W, 3] array (got %s %s)" % (f.dtype, f.shape))
+            out.append(f)
+        if not out:
+            raise ValueError("x2i_amd ImageFrontEnd: frames must be a non-empty list")
+        return out
+
+    def _check_out_dtype(self, out_dtype):
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("x2i_amd %s: out_dtype must be float32 or bfloat16 (got %r)" % (type(self).__name__, out_dtype))
+
+    def _plan_of_call(self, plan, nbytes):
+        """The plan a call on nbytes bytes runs with: the caller's, else the kept one, made anew where it is too small or on another device.
+        ValueError for a plan that does not hold the call, X2IError on a device that is not a GPU."""
+        if plan is None:
+            plan = self._plan
+            if plan is None or plan.nbytes < nbytes or plan.device != self.device:
+                plan = self._plan = self.plan(nbytes)
+        if plan.nbytes < nbytes or plan.device != self.device:
+            raise ValueError("x2i_amd %s: the plan holds %d bytes on %s; the call holds %d bytes of %s on %s"
+                             % (type(self).__name__, plan.nbytes, plan.device, nbytes, self._noun, self.device))
+        if self.device.type != "cuda":
+            raise ib.X2IError("x2i_amd: %s runs on the GPU only (the module is on %s); there is no CPU fallback" % (type(self).__name__, self.device))
+        return plan
+
+    def _staged(self, plan, groups):
+        """groups: [(the front end's own record of a group, its equally sized arrays)].  A generator over the groups: each is copied into
+        the pinned buffer behind the groups before it, its asynchronous transfer is started and (the record, the frames on the device) is
+        yielded for the caller to launch on; behind the last group the event of the call is recorded.  Run it to its end, as a for loop
+        over it alone does."""
+        if plan.busy:
+            plan.sent.synchronize()                            # the previous call's transfers out of the staging buffer (long done, as a rule)
+        stage, src = plan.stage.numpy(), 0
+        for record, arrays in groups:
+            (h, w), n = arrays[0].shape[:2], len(arrays)
+            end = src + n * 3 * w * h
+            pinned = stage[src:end].reshape(n, h, w, 3)
+            for j, a in enumerate(arrays):
+                pinned[j] = a
+            dev = plan.dev[src:end]
+            dev.copy_(plan.stage[src:end], non_blocking=True)
+            yield record, dev
+            src = end
+        plan.sent.record()
+        plan.busy = True
+
+
+class ImageFrontEnd(StagedFrontEnd):
     """frames -> ([float32 [3, 14, 14 L] on the device], tgt_sizes).  mean, std: three values each; scale_resolution: the processor's."""
 
     def __init__(self, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), scale_resolution=448, device="cuda"):
-        mean, std = [float(v) for v in mean], [float(v) for v in std]
-        if len(mean) != 3 or len(std) != 3 or not all(std):
-            raise ValueError("x2i_amd ImageFrontEnd: mean and std must hold three values, std none of them zero (got %r, %r)" % (mean, std))
+        super().__init__(mean, std, device)
         if int(scale_resolution) < PATCH:
             raise ValueError("x2i_amd ImageFrontEnd: scale_resolution = %r must be at least the patch size 14" % (scale_resolution,))
-        self.scale_resolution, self.device = int(scale_resolution), torch.device(device)
-        self.lut = torch.from_numpy(norm_lut(mean, std)).to(self.device)
-        self._tables = {}
-        self._plan = None
+        self.scale_resolution = int(scale_resolution)
+        self.lut = torch.from_numpy(norm_lut(self.mean, self.std)).to(self.device)
 
     @classmethod
     def from_hf(cls, image_processor, device="cuda"):
@@ -139,15 +233,6 @@ class ImageFrontEnd:
         rw, rh = self.refine_size(w, h, grid)
         return self.best_size(w, h), grid, (rw // grid[0], rh // grid[1])
 
-    def tables(self, n_in, n_out):
-        """(bound, coef) of one axis on the device, made once per (n_in, n_out); (None, None) where the axis does not resize"""
-        if n_in == n_out:
-            return None, None
-        t = self._tables.get((n_in, n_out))
-        if t is None:
-            t = self._tables[(n_in, n_out)] = tuple(torch.from_numpy(a).to(self.device) for a in axis_tables(n_in, n_out))
-        return t
-
     def served(self, w, h, max_slice_nums=1):
         """None where frames of w x h pixels are served, else the reason they are not (the kernel's own refusal)"""
         try:
@@ -158,40 +243,6 @@ class ImageFrontEnd:
         except ib.X2IError as e:
             return str(e)
         return None
-
-    # ------------------------------------------------------------------ plan
-    def plan(self, nbytes):
-        """The pinned staging buffer and the device frame buffer of calls on at most nbytes bytes of frames"""
-        nbytes = int(nbytes)
-        if nbytes < 1:
-            raise ValueError("x2i_amd ImageFrontEnd: a plan needs at least one byte of frames (got %d)" % nbytes)
-        p = ImagePlan()
-        cuda = self.device.type == "cuda"
-        p.nbytes, p.device = nbytes, self.device
-        p.stage = torch.empty(nbytes, dtype=torch.uint8, pin_memory=cuda)
-        p.dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        p.sent = torch.cuda.Event() if cuda else None
-        p.busy = False
-        return p
-
-    @staticmethod
-    def _as_arrays(frames):
-        """A list of uint8 [H, W, 3] arrays of PIL RGB images, arrays, or one [n, H, W, 3] array"""
-        if isinstance(frames, np.ndarray) and frames.ndim == 4:
-            frames = list(frames)
-        out = []
-        for f in frames:
-            if not isinstance(f, np.ndarray):
-                if getattr(f, "mode", None) != "RGB":
-                    raise ValueError("x2i_amd ImageFrontEnd: a frame must be a PIL image of mode RGB or a uint8 [H, W, 3] array (got %r)"
-                                     % (getattr(f, "mode", type(f).__name__),))
-                f = np.asarray(f)
-            if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or not f.shape[0] or not f.shape[1]:
-                raise ValueError("x2i_amd ImageFrontEnd: a frame must be a uint8 [H, W, 3] array (got %s %s)" % (f.dtype, f.shape))
-            out.append(f)
-        if not out:
-            raise ValueError("x2i_amd ImageFrontEnd: frames must be a non-empty list")
-        return out
 
     # ------------------------------------------------------------------ call
     @torch.no_grad()
@@ -209,8 +260,7 @@ class ImageFrontEnd:
         array [slices, 2] of (patch rows, patch columns)).  A group of equally sized frames costs one launch for the source images and,
         where they are sliced, one for the crops."""
         arrays = self._as_arrays(frames)
-        if out_dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("x2i_amd ImageFrontEnd: out_dtype must be float32 or bfloat16 (got %r)" % (out_dtype,))
+        self._check_out_dtype(out_dtype)
         if int(max_slice_nums) < 1:
             raise ValueError("x2i_amd ImageFrontEnd: max_slice_nums = %r must be at least 1" % (max_slice_nums,))
         groups = {}                                             # (w, h) -> frame indices, in the order of first appearance
@@ -221,34 +271,17 @@ class ImageFrontEnd:
             ib.check_sizes(w, h, ow, oh)
             if grid is not None:
                 itb.check_sizes(w, h, crop[0] * grid[0], crop[1] * grid[1], crop[0], crop[1])
-        nbytes = sum(a.size for a in arrays)
-        if plan is None:
-            plan = self._plan
-            if plan is None or plan.nbytes < nbytes or plan.device != self.device:
-                plan = self._plan = self.plan(nbytes)
-        if plan.nbytes < nbytes or plan.device != self.device:
-            raise ValueError("x2i_amd ImageFrontEnd: the plan holds %d bytes on %s; the call holds %d bytes of frames on %s"
-                             % (plan.nbytes, plan.device, nbytes, self.device))
-        if self.device.type != "cuda":
-            raise ib.X2IError("x2i_amd: ImageFrontEnd runs on the GPU only (the module is on %s); there is no CPU fallback" % (self.device,))
+        plan = self._plan_of_call(plan, sum(a.size for a in arrays))
         elems = {}                                              # (w, h) -> elements of a frame's source image, of one crop, crops per frame
         for wh, ((ow, oh), grid, crop) in plans.items():
             elems[wh] = (3 * ow * oh, 0, 0) if grid is None else (3 * ow * oh, 3 * crop[0] * crop[1], grid[0] * grid[1])
             for n_in, n_out in ((wh[0], ow), (wh[1], oh)) + (() if grid is None else ((wh[0], crop[0] * grid[0]), (wh[1], crop[1] * grid[1]))):
                 self.tables(n_in, n_out)                        # every table is made, and its accumulator bound checked, before any launch
         out = torch.empty(sum((e + c * k) * len(groups[wh]) for wh, (e, c, k) in elems.items()), dtype=out_dtype, device=self.device)
-        if plan.busy:
-            plan.sent.synchronize()                            # the previous call's transfers out of the staging buffer (long done, as a rule)
-        stage = plan.stage.numpy()
-        views, tgt, src, dst = [None] * len(arrays), [None] * len(arrays), 0, 0
-        for (w, h), idx in groups.items():
+        views, tgt, dst = [None] * len(arrays), [None] * len(arrays), 0
+        for ((w, h), idx), dev in self._staged(plan, [(item, [arrays[i] for i in item[1]]) for item in groups.items()]):
             ((ow, oh), grid, crop), n, fb = plans[(w, h)], len(idx), 3 * w * h
             e, c, k = elems[(w, h)]
-            pinned = stage[src:src + n * fb].reshape(n, h, w, 3)
-            for j, i in enumerate(idx):
-                pinned[j] = arrays[i]
-            plan.dev[src:src + n * fb].copy_(plan.stage[src:src + n * fb], non_blocking=True)
-            dev = plan.dev[src:src + n * fb]
             L14 = oh // PATCH * ow
             ib.frontend(dev, w, h, 3 * w, fb, n, ow, oh, *self.tables(w, ow), *self.tables(h, oh), self.lut, out[dst:dst + n * e], e, L14)
             for j, i in enumerate(idx):
@@ -264,7 +297,4 @@ class ImageFrontEnd:
                     views[i] += [out[dst + (j * k + t) * c:dst + (j * k + t + 1) * c].view(3, PATCH, C14) for t in range(k)]
                     tgt[i] += [(ch // PATCH, cw // PATCH)] * k
                 dst += n * k * c
-            src += n * fb
-        plan.sent.record()
-        plan.busy = True
         return views, [np.array(t) for t in tgt]

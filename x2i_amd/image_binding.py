@@ -62,10 +62,15 @@ def lds_plan(in_h, out_h):
     return rows, tile, pitch(tile)
 
 
-def check_sizes(in_w, in_h, out_w, out_h):
-    """X2IError for sizes the kernel does not serve (what the launcher refuses for the same sizes)"""
+def check_input_size(in_w, in_h):
+    """X2IError for an input size that none of the three image entry points serves"""
     if not (1 <= in_w <= MAX_IN and 1 <= in_h <= MAX_IN):
         raise X2IError("x2i_amd: in_w=%d and in_h=%d must be in 1..65535" % (in_w, in_h))
+
+
+def check_sizes(in_w, in_h, out_w, out_h):
+    """X2IError for sizes the kernel does not serve (what the launcher refuses for the same sizes)"""
+    check_input_size(in_w, in_h)
     for name, v in (("out_w", out_w), ("out_h", out_h)):
         if v < PATCH or v % PATCH or v > PATCH * MAX_PATCHES:
             raise X2IError("x2i_amd: %s=%d must be a multiple of 14 in 14..980" % (name, v))
@@ -86,15 +91,16 @@ def _table(bound, coef, n_out, k, name):
                        % (name, n_out, n_out, k, tuple(bound.shape), tuple(coef.shape)))
 
 
-def _frontend_args(frames, in_w, in_h, row_pitch, frame_pitch, n, out_w, out_h, hbound, hcoef, vbound, vcoef, lut, out, out_frame_stride,
-                   out_row_stride):
-    """The one place the arguments of x2i_image_frontend are put together (field order of include/frontend/x2i_image.h)"""
+def _shared_args(frames, lut, out, sizes, in_w, in_h, row_pitch, frame_pitch, n, out_w, out_h, hbound, hcoef, vbound, vcoef):
+    """What x2i_image_frontend, x2i_image_tiles and x2i_image_rows check alike about their arguments, in the order their refusals fire: the
+    dtypes; sizes(), the entry point's own size rules; the tables of both axes; lut; contiguity; the n frames within `frames`.
+    -> (hk, vk, what sizes() returned)"""
     ops._req(frames, torch.uint8, "frames")
     ops._req(lut, torch.float32, "lut")
     if out.dtype not in (torch.float32, torch.bfloat16):
         raise X2IError("x2i_amd: out must be float32 or bfloat16 (got %s)" % out.dtype)
     ops._req(out, out.dtype, "out")
-    check_sizes(in_w, in_h, out_w, out_h)
+    own = sizes()
     hk, vk = ksize(in_w, out_w), ksize(in_h, out_h)
     _table(hbound, hcoef, out_w, hk, "horizontal")
     _table(vbound, vcoef, out_h, vk, "vertical")
@@ -105,6 +111,14 @@ def _frontend_args(frames, in_w, in_h, row_pitch, frame_pitch, n, out_w, out_h, 
     if n < 1 or row_pitch < 3 * in_w or frame_pitch < (in_h - 1) * row_pitch + 3 * in_w or frames.numel() < (n - 1) * frame_pitch + (in_h - 1) * row_pitch + 3 * in_w:
         raise X2IError("x2i_amd: frames holds %d bytes; %d frames of %d x %d with row_pitch %d and frame_pitch %d do not fit"
                        % (frames.numel(), n, in_w, in_h, row_pitch, frame_pitch))
+    return hk, vk, own
+
+
+def _frontend_args(frames, in_w, in_h, row_pitch, frame_pitch, n, out_w, out_h, hbound, hcoef, vbound, vcoef, lut, out, out_frame_stride,
+                   out_row_stride):
+    """The one place the arguments of x2i_image_frontend are put together (field order of include/frontend/x2i_image.h)"""
+    hk, vk, _ = _shared_args(frames, lut, out, lambda: check_sizes(in_w, in_h, out_w, out_h), in_w, in_h, row_pitch, frame_pitch, n, out_w, out_h,
+                             hbound, hcoef, vbound, vcoef)
     L14 = out_h // PATCH * out_w
     if out_row_stride < L14 or out_frame_stride < 3 * PATCH * out_row_stride or out.numel() < (n - 1) * out_frame_stride + (3 * PATCH - 1) * out_row_stride + L14:
         raise X2IError("x2i_amd: out holds %d elements; %d frames of [3, 14, %d] with row stride %d and frame stride %d do not fit"

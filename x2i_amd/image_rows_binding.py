@@ -29,8 +29,7 @@ def check_sizes(in_w, in_h, out_w, out_h, n_items=1, t_in=1):
     """(grid_t, gh, gw) of an item; X2IError for sizes the kernel does not serve (what the launcher refuses for the same sizes)"""
     if n_items < 1 or t_in < 1 or n_items * t_in > MAX_FRAMES:
         raise X2IError("x2i_amd: n_items=%d and t_in=%d must be at least 1 and n_items * t_in in 1..65535" % (n_items, t_in))
-    if not (1 <= in_w <= ib.MAX_IN and 1 <= in_h <= ib.MAX_IN):
-        raise X2IError("x2i_amd: in_w=%d and in_h=%d must be in 1..65535" % (in_w, in_h))
+    ib.check_input_size(in_w, in_h)
     for name, v in (("out_w", out_w), ("out_h", out_h)):
         if v < UNIT or v % UNIT or v > MAX_OUT:
             raise X2IError("x2i_amd: %s=%d must be a multiple of 28 in 28..11760" % (name, v))
@@ -41,23 +40,8 @@ def check_sizes(in_w, in_h, out_w, out_h, n_items=1, t_in=1):
 def _rows_args(frames, in_w, in_h, row_pitch, frame_pitch, n_items, t_in, out_w, out_h, hbound, hcoef, vbound, vcoef, lut, out,
                out_item_stride, out_row_stride):
     """The one place the arguments of x2i_image_rows are put together (field order of include/frontend/rows/qwen/x2i_image_rows.h)"""
-    ops._req(frames, torch.uint8, "frames")
-    ops._req(lut, torch.float32, "lut")
-    if out.dtype not in (torch.float32, torch.bfloat16):
-        raise X2IError("x2i_amd: out must be float32 or bfloat16 (got %s)" % out.dtype)
-    ops._req(out, out.dtype, "out")
-    grid_t, gh, gw = check_sizes(in_w, in_h, out_w, out_h, n_items, t_in)
-    hk, vk = ib.ksize(in_w, out_w), ib.ksize(in_h, out_h)
-    ib._table(hbound, hcoef, out_w, hk, "horizontal")
-    ib._table(vbound, vcoef, out_h, vk, "vertical")
-    if tuple(lut.shape) != (3, 256) or not lut.is_contiguous():
-        raise X2IError("x2i_amd: lut must be a contiguous [3, 256] tensor (got %s)" % (tuple(lut.shape),))
-    if not frames.is_contiguous() or not out.is_contiguous():
-        raise X2IError("x2i_amd: frames and out are flat buffers and must be contiguous")
-    n = n_items * t_in
-    if row_pitch < 3 * in_w or frame_pitch < (in_h - 1) * row_pitch + 3 * in_w or frames.numel() < (n - 1) * frame_pitch + (in_h - 1) * row_pitch + 3 * in_w:
-        raise X2IError("x2i_amd: frames holds %d bytes; %d frames of %d x %d with row_pitch %d and frame_pitch %d do not fit"
-                       % (frames.numel(), n, in_w, in_h, row_pitch, frame_pitch))
+    hk, vk, (grid_t, gh, gw) = ib._shared_args(frames, lut, out, lambda: check_sizes(in_w, in_h, out_w, out_h, n_items, t_in), in_w, in_h, row_pitch,
+                                               frame_pitch, n_items * t_in, out_w, out_h, hbound, hcoef, vbound, vcoef)
     rows = grid_t * gh * gw
     if (out_row_stride < ROW or out_item_stride < rows * out_row_stride
             or out.numel() < (n_items - 1) * out_item_stride + (rows - 1) * out_row_stride + ROW):

@@ -29,8 +29,7 @@ load = _lib.extension("frontend/tiles/x2i_image_tiles.h", _EXPORTS)
 
 def check_sizes(in_w, in_h, out_w, out_h, tile_w, tile_h):
     """(gx, gy) of the grid; X2IError for sizes the kernel does not serve (what the launcher refuses for the same sizes)"""
-    if not (1 <= in_w <= ib.MAX_IN and 1 <= in_h <= ib.MAX_IN):
-        raise X2IError("x2i_amd: in_w=%d and in_h=%d must be in 1..65535" % (in_w, in_h))
+    ib.check_input_size(in_w, in_h)
     for name, v in (("tile_w", tile_w), ("tile_h", tile_h)):
         if v < PATCH or v % PATCH or v > PATCH * MAX_PATCHES:
             raise X2IError("x2i_amd: %s=%d must be a multiple of 14 in 14..980" % (name, v))
@@ -52,24 +51,11 @@ def tile_extent(tile_w, tile_h, layout, out_row_stride):
 def _tiles_args(frames, in_w, in_h, row_pitch, frame_pitch, n, out_w, out_h, tile_w, tile_h, hbound, hcoef, vbound, vcoef, lut, out,
                 out_frame_stride, out_tile_stride, out_row_stride, layout):
     """The one place the arguments of x2i_image_tiles are put together (field order of include/frontend/tiles/x2i_image_tiles.h)"""
-    ops._req(frames, torch.uint8, "frames")
-    ops._req(lut, torch.float32, "lut")
-    if out.dtype not in (torch.float32, torch.bfloat16):
-        raise X2IError("x2i_amd: out must be float32 or bfloat16 (got %s)" % out.dtype)
-    ops._req(out, out.dtype, "out")
-    if layout not in (STRIP, PLANAR):
-        raise X2IError("x2i_amd: layout=%r must be 0 (strip) or 1 (planar)" % (layout,))
-    gx, gy = check_sizes(in_w, in_h, out_w, out_h, tile_w, tile_h)
-    hk, vk = ib.ksize(in_w, out_w), ib.ksize(in_h, out_h)
-    ib._table(hbound, hcoef, out_w, hk, "horizontal")
-    ib._table(vbound, vcoef, out_h, vk, "vertical")
-    if tuple(lut.shape) != (3, 256) or not lut.is_contiguous():
-        raise X2IError("x2i_amd: lut must be a contiguous [3, 256] tensor (got %s)" % (tuple(lut.shape),))
-    if not frames.is_contiguous() or not out.is_contiguous():
-        raise X2IError("x2i_amd: frames and out are flat buffers and must be contiguous")
-    if n < 1 or row_pitch < 3 * in_w or frame_pitch < (in_h - 1) * row_pitch + 3 * in_w or frames.numel() < (n - 1) * frame_pitch + (in_h - 1) * row_pitch + 3 * in_w:
-        raise X2IError("x2i_amd: frames holds %d bytes; %d frames of %d x %d with row_pitch %d and frame_pitch %d do not fit"
-                       % (frames.numel(), n, in_w, in_h, row_pitch, frame_pitch))
+    def sizes():
+        if layout not in (STRIP, PLANAR):
+            raise X2IError("x2i_amd: layout=%r must be 0 (strip) or 1 (planar)" % (layout,))
+        return check_sizes(in_w, in_h, out_w, out_h, tile_w, tile_h)
+    hk, vk, (gx, gy) = ib._shared_args(frames, lut, out, sizes, in_w, in_h, row_pitch, frame_pitch, n, out_w, out_h, hbound, hcoef, vbound, vcoef)
     row_min, rows, extent = tile_extent(tile_w, tile_h, layout, out_row_stride)
     if (out_row_stride < row_min or out_tile_stride < rows * out_row_stride or out_frame_stride < gx * gy * out_tile_stride
             or out.numel() < (n - 1) * out_frame_stride + (gx * gy - 1) * out_tile_stride + extent):

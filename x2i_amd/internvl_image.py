@@ -12,7 +12,7 @@ A run of consecutive, equally sized images costs two launches: the crops of the 
 import torch
 
 from . import image_tiles_binding as itb
-from .image import ImageFrontEnd
+from .image import StagedFrontEnd
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
@@ -49,21 +49,18 @@ def closest_ratio(w, h, max_num=12, image_size=448, min_num=1):
     return best
 
 
-class InternVLImageFrontEnd:
+class InternVLImageFrontEnd(StagedFrontEnd):
     """images -> (pixel_values [sum of tiles, 3, image_size, image_size] on the device, num_patches_list)"""
 
+    _noun = "images"
+
     def __init__(self, image_size=448, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda"):
-        mean, std = [float(v) for v in mean], [float(v) for v in std]
-        if len(mean) != 3 or len(std) != 3 or not all(std):
-            raise ValueError("x2i_amd InternVLImageFrontEnd: mean and std must hold three values, std none of them zero (got %r, %r)" % (mean, std))
+        super().__init__(mean, std, device)
         image_size = int(image_size)
         if image_size < itb.PATCH or image_size % itb.PATCH or image_size > itb.PATCH * itb.MAX_PATCHES:
             raise ValueError("x2i_amd InternVLImageFrontEnd: image_size = %d must be a multiple of 14 in 14..980" % image_size)
-        self.image_size, self.device = image_size, torch.device(device)
-        self.lut = tensor_lut(mean, std).to(self.device)
-        self._base = ImageFrontEnd(device=device)              # the coefficient tables and the staging buffers
-        self.tables, self.plan = self._base.tables, self._base.plan
-        self._plan = None
+        self.image_size = image_size
+        self.lut = tensor_lut(self.mean, self.std).to(self.device)
 
     def grid(self, w, h, max_num=12):
         """(gx, gy) of a w x h image"""
@@ -76,48 +73,31 @@ class InternVLImageFrontEnd:
     def tiles(self, images, max_num=12, use_thumbnail=True, out_dtype=torch.float32, plan=None):
         """images: PIL RGB images or uint8 [H, W, 3] arrays.  -> (pixel_values of out_dtype (float32 or bfloat16), per image the crops in
         the order (i % gx, i // gx) and then the thumbnail where there is more than one crop; num_patches_list, the tiles per image)"""
-        arrays = ImageFrontEnd._as_arrays(images)
-        if out_dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("x2i_amd InternVLImageFrontEnd: out_dtype must be float32 or bfloat16 (got %r)" % (out_dtype,))
+        arrays = self._as_arrays(images)
+        self._check_out_dtype(out_dtype)
         S = self.image_size
         grids = [self.grid(a.shape[1], a.shape[0], max_num) for a in arrays]
         counts = [gx * gy + int(bool(use_thumbnail) and gx * gy > 1) for gx, gy in grids]
         for a, (gx, gy) in zip(arrays, grids):
             itb.check_sizes(a.shape[1], a.shape[0], S * gx, S * gy, S, S)
             itb.check_sizes(a.shape[1], a.shape[0], S, S, S, S)
-        nbytes = sum(a.size for a in arrays)
-        if plan is None:
-            plan = self._plan
-            if plan is None or plan.nbytes < nbytes or plan.device != self.device:
-                plan = self._plan = self.plan(nbytes)
-        if plan.nbytes < nbytes or plan.device != self.device:
-            raise ValueError("x2i_amd InternVLImageFrontEnd: the plan holds %d bytes on %s; the call holds %d bytes of images on %s"
-                             % (plan.nbytes, plan.device, nbytes, self.device))
-        if self.device.type != "cuda":
-            raise itb.X2IError("x2i_amd: InternVLImageFrontEnd runs on the GPU only (the module is on %s); there is no CPU fallback" % (self.device,))
+        plan = self._plan_of_call(plan, sum(a.size for a in arrays))
         tile = 3 * S * S
         out = torch.empty(sum(counts) * tile, dtype=out_dtype, device=self.device)
-        if plan.busy:
-            plan.sent.synchronize()                            # the previous call's transfers out of the staging buffer
-        stage = plan.stage.numpy()
-        i, src, dst = 0, 0, 0
-        while i < len(arrays):
-            h, w = arrays[i].shape[:2]
-            n = 1
-            while i + n < len(arrays) and arrays[i + n].shape == arrays[i].shape:      # a run of equally sized images: one grid, one stride
-                n += 1
-            (gx, gy), per, fb = grids[i], counts[i], 3 * w * h
-            pinned = stage[src:src + n * fb].reshape(n, h, w, 3)
-            for j in range(n):
-                pinned[j] = arrays[i + j]
-            dev = plan.dev[src:src + n * fb]
-            dev.copy_(plan.stage[src:src + n * fb], non_blocking=True)
+        runs = []                                               # (first image, images) of a run of equally sized images: one grid, one stride
+        for i, a in enumerate(arrays):
+            if runs and arrays[runs[-1][0]].shape == a.shape:
+                runs[-1][1] += 1
+            else:
+                runs.append([i, 1])
+        dst = 0
+        for (i, n), dev in self._staged(plan, [((i, n), arrays[i:i + n]) for i, n in runs]):
+            (h, w), (gx, gy), per = arrays[i].shape[:2], grids[i], counts[i]
+            fb = 3 * w * h
             itb.tiles(dev, w, h, 3 * w, fb, n, S * gx, S * gy, S, S, *self.tables(w, S * gx), *self.tables(h, S * gy), self.lut,
                       out[dst:dst + n * per * tile], per * tile, tile, S, itb.PLANAR)
             if per > gx * gy:                                 # the thumbnails: the last tile of every image of the run
                 itb.tiles(dev, w, h, 3 * w, fb, n, S, S, S, S, *self.tables(w, S), *self.tables(h, S), self.lut,
                           out[dst + gx * gy * tile:dst + n * per * tile], per * tile, tile, S, itb.PLANAR)
-            i, src, dst = i + n, src + n * fb, dst + n * per * tile
-        plan.sent.record()
-        plan.busy = True
+            dst += n * per * tile
         return out.view(sum(counts), 3, S, S), counts

@@ -22,29 +22,24 @@ import numpy as np
 import torch
 
 from . import image as im, image_binding as ib, image_rows_binding as irb
-from .image import ImageFrontEnd, ImagePlan
+from .image import ImagePlan, StagedFrontEnd
 
 PATCH, MERGE, TEMPORAL, ROW = irb.PATCH, 2, 2, irb.ROW
 FACTOR = PATCH * MERGE
 _BICUBIC = 3                                                     # PIL.Image.BICUBIC, PILImageResampling.BICUBIC
 
 
-class QwenImageFrontEnd:
+class QwenImageFrontEnd(StagedFrontEnd):
     """images -> (pixel_rows [S, 1176] on the device, image_grid_thw int64 [n, 3] on the host).  mean, std: three values each;
     min_pixels, max_pixels: the processor's size["shortest_edge"] and size["longest_edge"]."""
 
     def __init__(self, mean=(0.48145466, 0.4578275, 0.40821073), std=(0.26862954, 0.26130258, 0.27577711), min_pixels=56 * 56,
                  max_pixels=28 * 28 * 1280, device="cuda"):
-        mean, std = [float(v) for v in mean], [float(v) for v in std]
-        if len(mean) != 3 or len(std) != 3 or not all(std):
-            raise ValueError("x2i_amd QwenImageFrontEnd: mean and std must hold three values, std none of them zero (got %r, %r)" % (mean, std))
+        super().__init__(mean, std, device)
         if not 0 < int(min_pixels) <= int(max_pixels):
             raise ValueError("x2i_amd QwenImageFrontEnd: need 0 < min_pixels <= max_pixels (got %r, %r)" % (min_pixels, max_pixels))
-        self.mean, self.std = mean, std
-        self.min_pixels, self.max_pixels, self.device = int(min_pixels), int(max_pixels), torch.device(device)
-        self.lut = torch.from_numpy(im.norm_lut(mean, std)).to(self.device)
-        self._tables = {}
-        self._plan = None
+        self.min_pixels, self.max_pixels = int(min_pixels), int(max_pixels)
+        self.lut = torch.from_numpy(im.norm_lut(self.mean, self.std)).to(self.device)
 
     @classmethod
     def from_hf(cls, image_processor, device="cuda"):
@@ -84,15 +79,6 @@ class QwenImageFrontEnd:
             hb, wb = math.ceil(h * beta / FACTOR) * FACTOR, math.ceil(w * beta / FACTOR) * FACTOR
         return hb, wb
 
-    def tables(self, n_in, n_out):
-        """(bound, coef) of one axis on the device, made once per (n_in, n_out); (None, None) where the axis does not resize"""
-        if n_in == n_out:
-            return None, None
-        t = self._tables.get((n_in, n_out))
-        if t is None:
-            t = self._tables[(n_in, n_out)] = tuple(torch.from_numpy(a).to(self.device) for a in im.axis_tables(n_in, n_out))
-        return t
-
     def served(self, w, h):
         """None where images of w x h pixels are served, else the reason they are not (smart_resize's refusal or the kernel's own)"""
         try:
@@ -102,13 +88,10 @@ class QwenImageFrontEnd:
             return str(e)
         return None
 
-    plan = ImageFrontEnd.plan                                   # the pinned staging buffer and the device frame buffer, as ImageFrontEnd's
-
     # ------------------------------------------------------------------ call
     def _run(self, groups, out_dtype, plan, out, row_stride, resize):
         """groups: [(arrays of one size, n_items, t_in)] in the order of their rows -> (rows [S, 1176] view, [(grid_t, gh, gw)] per item)"""
-        if out_dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("x2i_amd QwenImageFrontEnd: out_dtype must be float32 or bfloat16 (got %r)" % (out_dtype,))
+        self._check_out_dtype(out_dtype)
         row_stride = int(row_stride)
         if row_stride < ROW:
             raise ValueError("x2i_amd QwenImageFrontEnd: row_stride = %d must be at least 1176" % row_stride)
@@ -120,16 +103,7 @@ class QwenImageFrontEnd:
             todo.append((arrays, n_items, t_in, w, h, ow, oh, S, grid_t * gh * gw))
             grids += [(grid_t, gh, gw)] * n_items
             S += n_items * grid_t * gh * gw
-        nbytes = sum(a.size for g in groups for a in g[0])
-        if plan is None:
-            plan = self._plan
-            if plan is None or plan.nbytes < nbytes or plan.device != self.device:
-                plan = self._plan = self.plan(nbytes)
-        if plan.nbytes < nbytes or plan.device != self.device:
-            raise ValueError("x2i_amd QwenImageFrontEnd: the plan holds %d bytes on %s; the call holds %d bytes of frames on %s"
-                             % (plan.nbytes, plan.device, nbytes, self.device))
-        if self.device.type != "cuda":
-            raise ib.X2IError("x2i_amd: QwenImageFrontEnd runs on the GPU only (the module is on %s); there is no CPU fallback" % (self.device,))
+        plan = self._plan_of_call(plan, sum(a.size for g in groups for a in g[0]))
         need = (S - 1) * row_stride + ROW
         if out is None:
             out = torch.empty(S * row_stride, dtype=out_dtype, device=self.device)
@@ -140,20 +114,9 @@ class QwenImageFrontEnd:
         flat = out.view(-1)
         for _, _, _, w, h, ow, oh, _, _ in todo:                # every table is made, and its accumulator bound checked, before any launch
             self.tables(w, ow), self.tables(h, oh)
-        if plan.busy:
-            plan.sent.synchronize()                            # the previous call's transfers out of the staging buffer (long done, as a rule)
-        stage, src = plan.stage.numpy(), 0
-        for arrays, n_items, t_in, w, h, ow, oh, row0, item_rows in todo:
-            n, fb = len(arrays), 3 * w * h
-            pinned = stage[src:src + n * fb].reshape(n, h, w, 3)
-            for j, a in enumerate(arrays):
-                pinned[j] = a
-            plan.dev[src:src + n * fb].copy_(plan.stage[src:src + n * fb], non_blocking=True)
-            irb.rows(plan.dev[src:src + n * fb], w, h, 3 * w, fb, n_items, t_in, ow, oh, *self.tables(w, ow), *self.tables(h, oh), self.lut,
+        for (_, n_items, t_in, w, h, ow, oh, row0, item_rows), dev in self._staged(plan, [(t, t[0]) for t in todo]):
+            irb.rows(dev, w, h, 3 * w, 3 * w * h, n_items, t_in, ow, oh, *self.tables(w, ow), *self.tables(h, oh), self.lut,
                      flat[row0 * row_stride:], item_rows * row_stride, row_stride)
-            src += n * fb
-        plan.sent.record()
-        plan.busy = True
         return flat.as_strided((S, ROW), (row_stride, 1)), np.array(grids, dtype=np.int64).reshape(-1, 3)
 
     @torch.no_grad()
@@ -162,7 +125,7 @@ class QwenImageFrontEnd:
         row_stride elements apart, in the order of the images; image_grid_thw, a host int64 array [n, 3] of (1, gh, gw)).  out: a
         contiguous buffer of out_dtype on the device to write into (of at least (S - 1) * row_stride + 1176 elements; nothing but the
         rows' 1176 columns is written), else one is allocated."""
-        arrays = ImageFrontEnd._as_arrays(images)
+        arrays = self._as_arrays(images)
         runs = []
         for a in arrays:                                        # runs of adjacent images of one size
             if runs and runs[-1][0].shape == a.shape and len(runs[-1]) < irb.MAX_FRAMES:
@@ -176,7 +139,7 @@ class QwenImageFrontEnd:
         """frames: one list of equally sized uint8 frames (PIL RGB images or [H, W, 3] arrays), T of them.  -> (rows [ceil(T / 2) gh gw, 1176],
         the host int64 array [[ceil(T / 2), gh, gw]]): temporal slot tp of step t holds frame min(2 t + tp, T - 1).  resize=False takes the
         frames at their own size (a multiple of 28 on both sides)."""
-        arrays = ImageFrontEnd._as_arrays(frames)
+        arrays = self._as_arrays(frames)
         if any(a.shape != arrays[0].shape for a in arrays):
             raise ValueError("x2i_amd QwenImageFrontEnd: the frames of a clip must have one size (got %r)" % (sorted({a.shape[:2] for a in arrays}),))
         return self._run([(arrays, 1, len(arrays))], out_dtype, plan, out, row_stride, resize)
