@@ -176,8 +176,9 @@ def load():
     return lib
 
 
-def extension(header_name, exports):
+def extension(header_name, exports, root="include"):
     """The load() of an extension header's binding module: a callable that returns the library of load() with the header's prototypes set.
+    header_name: the header's path below `root` (include/, or abi/ for the headers that stand outside the closed sets of include/).
     exports: name -> argtypes, all returning int; such entry points are not in _EXPORTS (include/x2i.h's table is closed under its ABI
     version), so they get their argtypes on the CDLL object the first time the callable is used, again whenever load() returns another
     object, and a missing symbol means a stale build."""
@@ -191,8 +192,8 @@ def extension(header_name, exports):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:
-                    raise X2IError("x2i_amd: %s does not export %s (include/%s) (stale build? run `python -m x2i_amd.build`)"
-                                   % (LIB_PATH, name, header_name))
+                    raise X2IError("x2i_amd: %s does not export %s (%s/%s) (stale build? run `python -m x2i_amd.build`)"
+                                   % (LIB_PATH, name, root, header_name))
                 fn.argtypes = argtypes
                 fn.restype = C.c_int
             bound = lib

@@ -34,7 +34,8 @@ def _hipcc():
 def _newest_header():
     hs = (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(HERE, "..", "include", "*.h"))
           + glob.glob(os.path.join(HERE, "..", "include", "ext", "**", "*.h"), recursive=True)      # (** also matches no directory)
-          + glob.glob(os.path.join(HERE, "..", "include", "frontend", "**", "*.h"), recursive=True))
+          + glob.glob(os.path.join(HERE, "..", "include", "frontend", "**", "*.h"), recursive=True)
+          + glob.glob(os.path.join(HERE, "..", "abi", "**", "*.h"), recursive=True))                # the headers outside include/'s closed sets
     return max(os.path.getmtime(h) for h in hs)
 
 

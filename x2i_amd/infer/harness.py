@@ -131,6 +131,12 @@ def build_parser(family):
     p.add_argument("--hip_sample_seed", type=int, default=None,
                    help="with --hip_sample: the seed of the draws (default: --seed where it is given, otherwise 0)")
     p.add_argument("--decode", action="store_true", help="with --synthetic: also run the (random-weight) VAE decoder and save images")
+    p.add_argument("--hip_image_out", action="store_true",
+                   help="run the two ends of the VAE decode on the HIP path (x2i_amd/image_out.py, abi/backend/x2i_image_out.h): the packed "
+                        "latents go straight into the decoder's input (no unpack, divide, add and padded copy on torch), its NHWC output "
+                        "becomes uint8 pixels on the device, 3 bytes per pixel reach pinned host memory in one asynchronous copy, and a "
+                        "background thread saves the files while the next batch samples; the same .jpg bytes as without the flag.  Needs a "
+                        "VAE: with --synthetic, add --decode")
     return p
 
 
@@ -229,6 +235,32 @@ class Harness:
             None if args.synthetic else load_vae(args.flux_path, device))
         self.conditioner = conditioner
         self.outputs = args.outputs or "./outputs_%s" % kind
+        self.image_out = self.writer = None
+        if getattr(args, "hip_image_out", False):
+            if self.vae is None:
+                raise ValueError("--hip_image_out runs the ends of the VAE decode: with --synthetic it needs --decode")
+            if self.rank == 0:
+                from ..image_out import ImageBackEnd, ImageWriter
+                self.image_out, self.writer = ImageBackEnd(self.vae, self.device), ImageWriter()
+
+    def _save_hip(self, latents, height, width, paths):
+        """--hip_image_out: the decode and the copy are enqueued, the writer thread saves `paths` once they arrive.  After a save that
+        failed nothing more is enqueued: the writer's own exception is raised here, before the decode"""
+        if self.writer.failed:
+            self.writer.flush()
+        self.writer.put(self.image_out.submit(latents, height, width), paths)
+
+    def flush_outputs(self, quiet=False):
+        """--hip_image_out: wait for the writer thread and raise what it met (quiet: on the way out of another error, which stays the one
+        that is raised; the writer's is printed)"""
+        if self.writer is not None:
+            try:
+                self.writer.flush()
+            except Exception as e:
+                if not quiet:
+                    raise
+                import sys
+                print("x2i_amd: while another error was being raised, the image writer also reported %r" % (e,), file=sys.stderr)
 
     @torch.no_grad()
     def embeds(self, **inputs):
@@ -261,6 +293,9 @@ class Harness:
             return latents
         if self.vae is None:
             torch.save(latents.cpu(), os.path.join(out_dir, filename + "_latents.pt"))
+            return latents
+        if self.image_out is not None:
+            self._save_hip(latents, height, width, [os.path.join(out_dir, "%s%s.jpg" % (filename, "" if B == 1 else "_b%d" % i)) for i in range(B)])
             return latents
         vsf = 2 ** len(self.vae.config.block_out_channels)  # :209
         x = FluxPipeline._unpack_latents(latents, height, width, vsf)
@@ -327,6 +362,9 @@ class Harness:
             for i, fn in enumerate(filenames):
                 torch.save(latents[i:i + 1].cpu(), os.path.join(out_dir, fn + "_latents.pt"))
             return
+        if self.image_out is not None:
+            self._save_hip(latents, height, width, [os.path.join(out_dir, fn + ".jpg") for fn in filenames])
+            return
         vsf = 2 ** len(self.vae.config.block_out_channels)
         x = FluxPipeline._unpack_latents(latents, height, width, vsf)
         x = (x / self.vae.config.scaling_factor) + self.vae.config.shift_factor
@@ -338,7 +376,15 @@ class Harness:
     def run_tasks(self, tasks):
         """tasks: {name: [dict(filename=..., **conditioner_inputs)]}; runs the ones selected by --task.  --synthetic keeps the
         one-job-per-call form with a synthetic batch of --batch samples; with a real MLLM the jobs of a task are packed --batch at a
-        time into one sampling call (generate_jobs)."""
+        time into one sampling call (generate_jobs).  Under --hip_image_out the files are complete when this returns, or raises."""
+        try:
+            self._run_tasks(tasks)
+        except BaseException:
+            self.flush_outputs(quiet=True)
+            raise
+        self.flush_outputs()
+
+    def _run_tasks(self, tasks):
         a = self.args
         for name, jobs in tasks.items():
             if a.task not in ("all", name):

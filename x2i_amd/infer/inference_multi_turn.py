@@ -90,6 +90,7 @@ def synthetic_turns(args, kind, device):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         h.generate(pooled, embeds, "multi_turn", "turn_%d" % turn, seed=0)
+        h.flush_outputs()              # (--hip_image_out: the turn's file is written before the turn is reported)
         torch.cuda.synchronize()
         st = h.pipeline.graph_stats
         print("turn %d: S_txt %4d  sampling %8.1f ms   (pipeline so far: %d eager, %d captures, %d replays)"
@@ -125,6 +126,7 @@ def main(argv=None):
         parts = [s.strip() for s in line.split("|")]
         pooled, embeds = h.embeds(text_prompt=parts[0], images=parts[1:] or None)
         h.generate(pooled, embeds, "multi_turn", "turn_%d" % turn, seed=0)
+        h.flush_outputs()
         print("assistant>", cond.history[-1]["content"][0]["text"])
         turn += 1
 

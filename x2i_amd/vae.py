@@ -447,11 +447,38 @@ class AutoencoderKL(nn.Module):
 
     @torch.no_grad()
     def decode(self, z, return_dict=True):
-        cfg, d = self.config, self.decoder
-        G = cfg.norm_num_groups
         B, Cz, H, W = z.shape
         x = torch.zeros((B, H, W, 64), device=z.device, dtype=torch.bfloat16)  # latent channels zero-padded to one K-step
         x[..., :Cz] = z.to(torch.bfloat16).permute(0, 2, 3, 1)
+        y = self._decode_nhwc(x)
+        img = y[..., :self.config.out_channels].permute(0, 3, 1, 2).contiguous()
+        if not return_dict:
+            return (img,)
+        return _Cfg(sample=img)
+
+    @torch.no_grad()
+    def decode_to_uint8(self, packed_latents, height, width, out=None, image_pitch=None, row_pitch=None, offset=0):
+        """The last lines of a sampling call in three stages on the device: packed latents bf16 [B, (h / 2)(w / 2), 4 latent_channels] as
+        FluxPipeline returns them under output_type="latent" -> the uint8 pixels VaeImageProcessor.postprocess(decode(_unpack_latents(...)
+        / scaling_factor + shift_factor), "pil") holds, byte for byte.  x2i_latents_to_vae writes conv_in's input (no unpack, divide, add,
+        zero fill or permuted copy on torch), the decoder body runs as in decode, x2i_image_to_u8 reads its NHWC output (no NCHW copy, no
+        float32 image).  height, width: the image's, as the pipeline took them.  Returns uint8 [B, H, W, 3] on the device, or with `out`
+        (a flat uint8 device buffer; pitches and offset in bytes, image_out_binding.image_to_u8) writes there and returns `out`."""
+        from . import image_out_binding as iob
+        cfg = self.config
+        vsf = 2 ** len(cfg.block_out_channels)            # the pipeline's vae_scale_factor: _unpack_latents' 2 * (height // vsf)
+        h, w = 2 * (int(height) // vsf), 2 * (int(width) // vsf)
+        if cfg.out_channels != 3:
+            raise ValueError("x2i_amd VAE decode_to_uint8: needs out_channels = 3 (RGB pixels), got %d" % cfg.out_channels)
+        x = iob.latents_to_vae(packed_latents, h, w, cfg.latent_channels, cfg.scaling_factor, cfg.shift_factor)
+        return iob.image_to_u8(self._decode_nhwc(x), out=out, image_pitch=image_pitch, row_pitch=row_pitch, offset=offset)
+
+    def _decode_nhwc(self, x):
+        """The decoder body of decode and decode_to_uint8: conv_in's input x bf16 [B, H, W, 64] (latent channels zero-padded to one K-step)
+        -> conv_out's output bf16 NHWC [B, 2^k H, 2^k W, 4 or 8], whose first out_channels channels are the image."""
+        cfg, d = self.config, self.decoder
+        G = cfg.norm_num_groups
+        B, H, W, _ = x.shape
         rev = list(reversed(cfg.block_out_channels))
         em = self.epilogue_moments   # the convs' epilogues leave the channel moments the next GroupNorm needs (no statistics pass over the tensor)
         w, b = d.conv_in.packed(cin_pad=64)
@@ -495,10 +522,7 @@ class AutoencoderKL(nn.Module):
         else:
             w, b = d.conv_out.packed(cout_pad=8)  # implicit GEMM, 3 -> 8 output channels so that rows are 16-byte aligned (A/B form)
             y = ops.conv2d_nhwc(n, w, b, H, W, rev[-1], 8, 3, 3, 1, 1)
-        img = y[..., :cfg.out_channels].permute(0, 3, 1, 2).contiguous()
-        if not return_dict:
-            return (img,)
-        return _Cfg(sample=img)
+        return y
 
     @classmethod
     def from_pretrained(cls, path, subfolder=None, torch_dtype=torch.bfloat16, device=None, **kw):
